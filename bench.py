@@ -1,6 +1,17 @@
 """bench.py -- benchmark of the MI355X CityLearn step engine (BASELINE.json's metric and configs).
 
-    python bench.py --gpus N --steps K --warmup W [--config headline|C2|C3|C4|C4-lean|C5]
+    python bench.py --gpus N --steps K --warmup W [--config headline|C2|C3|C4|C4-lean|C5] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, W warmup steps, ONE timed region of exactly K steps (`--reps` defaults to 1),
+the outputs if `--dump-outputs DIR` is given, the JSON line (`value`, `ms_per_step` = wall milliseconds of one timed step, ...).  Everything
+else the benchmark measures -- the repetitions' HIP-event pass and the kernel-time bracket behind `roofline`, the HBM-streaming and all-fp32
+side entries, the rocprofv3 traffic passes, mode B beside mode A, `extra_configs`, `cpu_baseline` and `dropin` -- runs only under `--full`
+(where `--reps` defaults to 5 and the `--no-*` options switch single parts off again).
+
+`--dump-outputs DIR`: what the timed path handed its caller after its last timed step (the engine's soc / degraded capacity / net / reward
+planes and district sums; the LSTM stage's indoor temperature and comfort reward under C3; the K-step returns of the fused rollout), rank 0's
+shard, one float32 `DIR/<name>.npy` each -- at most 64 MB in all: above that every array is cut to the same fraction of its elements, a
+fixed seeded sample (flattened, ascending index order).  Inputs are seeded, so equal arguments give equal inputs from run to run.
 
 `--gpus N` with N > 1 needs no launcher: when RANK / WORLD_SIZE are not in the environment this process starts the N ranks
 itself (one process per GPU, `citylearn_amd.parallel.launch_ranks`), forwards rank 0's JSON line and exits with the ranks'
@@ -66,6 +77,7 @@ ROUND_PREFIX = 'r06'             # profiles/ files this build's lines may cite (
 METRIC = 'building-timesteps/sec at 17 bldgs x 65536 envs; HBM GB/s vs roofline'
 PRECISIONS = {'chain': 'chain', 'fp32': False, 'f64': True}      # --precision -> StepEngine(f64_maps=...)
 CONFIGS = ('headline', 'C2', 'C3', 'C3-6', 'C4', 'C4-lean', 'C5', 'T9', 'C4-B', 'C4-lean-B')
+DUMP_BYTES = 64 * 10 ** 6        # --dump-outputs: cap on the bytes written in all (.npy headers included)
 
 
 # --------------------------------------------------------------------------------------------------- CPU baseline
@@ -279,9 +291,11 @@ def _barrier(dist):
     torch.cuda.default_stream().synchronize()
 
 
-def timed_reps(runner: Runner, reset_fn, warmup: int, steps: int, reps: int, dist, kernel_steps: int):
+def timed_reps(runner: Runner, reset_fn, warmup: int, steps: int, reps: int, dist, kernel_steps, snapshot=None):
     """`reps` x (exactly `steps` steps between barrier + synchronize): per-repetition (wall seconds, HIP-event seconds), and the
-    kernel time per step from HIP events around `kernel_steps` consecutive steps behind a lead-in chunk."""
+    kernel time per step from HIP events around `kernel_steps` consecutive steps behind a lead-in chunk.  `kernel_steps=None` (a plain
+    run): the timed repetitions alone -- no HIP-event pass, no kernel bracket; event seconds and kernel time are None.  `snapshot()` is
+    called once, right after the last timed repetition."""
     import torch
     stream = runner.stream
     out = []
@@ -294,7 +308,7 @@ def timed_reps(runner: Runner, reset_fn, warmup: int, steps: int, reps: int, dis
         runner.advance(0, warmup)
         stream.synchronize()
         go = runner.plan(warmup, steps)
-        for _ in range(reps):
+        for r in range(reps):
             if dist is not None:
                 _barrier(dist)
             torch.cuda.synchronize()
@@ -306,6 +320,11 @@ def timed_reps(runner: Runner, reset_fn, warmup: int, steps: int, reps: int, dis
             if dist is not None:
                 _barrier(dist)                       # the closing barrier of the bracket: after the clock is read -- a 30 us RCCL barrier inside
                                                      # a 20-step region would bill every rank 1.5 us per step for the collective's own latency
+            if snapshot is not None and r == reps - 1:
+                snapshot()
+            if kernel_steps is None:
+                out.append((wall, None))
+                continue
             # the same K steps once more between HIP events (diagnostic `timed_region_event_us_per_step`), OUTSIDE the wall-clock region: two
             # event records inside a 20-step region cost it ~3 us = 2 % (scripts/r05_k20_overhead.py, profiles/r05q_k20_overhead.log)
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -314,6 +333,8 @@ def timed_reps(runner: Runner, reset_fn, warmup: int, steps: int, reps: int, dis
             ev1.record(stream)
             stream.synchronize()
             out.append((wall, ev0.elapsed_time(ev1) / 1e3))
+        if kernel_steps is None:
+            return out, None
         # Kernel duration for the roofline: HIP events on the launch stream around `kernel_steps` consecutive steps of the same loop
         # (graphs of GRAPH_CHUNK steps, captured and replayed once beforehand) enqueued behind a lead-in chunk, so that the bracket
         # [ev0, ev1] holds kernel time only.  (Events around a timed repetition also hold the host's graph-submission gap between
@@ -329,6 +350,30 @@ def timed_reps(runner: Runner, reset_fn, warmup: int, steps: int, reps: int, dis
         stream.synchronize()
         kernel_s = ev0.elapsed_time(ev1) / 1e3 / n_k
     return out, kernel_s
+
+
+def write_outputs(arrays: dict, directory, budget: int = DUMP_BYTES) -> dict:
+    """`--dump-outputs`: every array as float32 `directory/<name>.npy`.  When they hold more than `budget` bytes, each is cut to the same
+    fraction of its elements: a sample fixed by the seed and the array's size, flattened, in ascending index order.  Returns {name: shape}."""
+    import numpy as np
+    directory = Path(directory)
+    directory.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    room = budget - 256 * len(arrays)                  # (an .npy header: 128 bytes for these shapes)
+    total = sum(a.nbytes for a in arrays.values())
+    shapes = {}
+    for name, a in arrays.items():
+        if total > room:
+            keep = np.random.default_rng(0).choice(a.size, int(a.size * room / total), replace=False)
+            a = a.reshape(-1)[np.sort(keep)]
+        np.save(directory / f'{name}.npy', a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
+def _engine_outputs(eng) -> dict:
+    """What a caller of the step engine reads after a step: battery state, per-building net consumption and reward, district sums."""
+    return {'soc': eng.soc, 'degraded_capacity': eng.degraded_capacity, 'net': eng.net, 'reward': eng.reward_bldg, 'district': eng.out_env}
 
 
 # --------------------------------------------------------------------------------------------------- workloads
@@ -456,6 +501,13 @@ class StepWorkload:
         to date where the district sums are finished deferred (C4 shard, `cl_tuning.finish = 3`); nothing to enqueue otherwise."""
         self.eng.finish()
 
+    def outputs(self) -> dict:
+        """Host copies of what the last step handed its caller (`--dump-outputs`); C3: the LSTM stage's indoor temperature and comfort too."""
+        out = _engine_outputs(self.eng)
+        if self.stage is not None:
+            out.update(indoor_temperature=self.stage.indoor_temp, comfort=self.stage.comfort)
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
     def bytes_per_unit(self) -> float:
         return self.eng.algorithmic_bytes_per_unit()
 
@@ -514,6 +566,10 @@ class RolloutWorkload:
     def reset(self):
         self.eng.reset()
         self.ret.zero_()
+
+    def outputs(self) -> dict:
+        """Host copies of what the last launch handed its caller (`--dump-outputs`): the engine's planes and the accumulated returns."""
+        return {k: v.cpu().numpy() for k, v in {**_engine_outputs(self.eng), 'returns': self.ret}.items()}
 
     def bytes_per_unit(self) -> float:
         return self.eng.algorithmic_bytes_per_unit() / self.K
@@ -679,44 +735,55 @@ def run_rank(args):
     cfg = args.config
     E = args.envs_per_gpu or DEFAULT_ENVS[cfg]
 
-    def measure(wl, warmup: int, steps: int, reps: int, kernel_steps: int):
+    def measure(wl, warmup: int, steps: int, reps: int, kernel_steps, snapshot=None):
         runner = Runner(wl.step_fn, wl.period, torch.cuda.Stream(device=device), use_graph, getattr(wl, 'flush', None))
-        rep, kernel_s = timed_reps(runner, wl.reset, warmup, steps, reps, dist, kernel_steps)
+        rep, kernel_s = timed_reps(runner, wl.reset, warmup, steps, reps, dist, kernel_steps, snapshot)
         walls = [reduce_max_seconds(w, dist, ctl_device) for w, _ in rep]         # MAX over ranks per repetition
-        evs = [reduce_max_seconds(e, dist, ctl_device) for _, e in rep]
         mine = statistics.median(w for w, _ in rep)
+        if kernel_steps is None:                                                   # (a plain run: no event pass, no kernel bracket)
+            return walls, None, None, gather_seconds(mine, dist, ctl_device), None
+        evs = [reduce_max_seconds(e, dist, ctl_device) for _, e in rep]
         return walls, evs, reduce_max_seconds(kernel_s, dist, ctl_device), gather_seconds(mine, dist, ctl_device), gather_seconds(kernel_s, dist, ctl_device)
 
     f64 = PRECISIONS[args.precision]                             # StepEngine's f64_maps: 'chain' (default) | False | True
     default_precision = args.precision == 'chain'
     wl = build_workload(cfg, E, device, rank, world, tuning, f64, args.kpi, args.table_hours)
     heavy = cfg in ('C3', 'C3-6', 'C5', 'C4-B', 'C4-lean-B')     # ~100 us .. 1 ms per step: fewer steps in the kernel-time bracket
-    walls, evs, launch_s, per_rank, per_rank_kernel = measure(wl, args.warmup, args.steps, args.reps, max(args.steps, 200 if heavy else 2000))
+    dumped = {}
+    snapshot = (lambda: dumped.update(wl.outputs())) if args.dump_outputs and rank == 0 else None
+    walls, evs, launch_s, per_rank, per_rank_kernel = measure(wl, args.warmup, args.steps, args.reps,
+                                                              max(args.steps, 200 if heavy else 2000) if args.full else None, snapshot)
     wall_med = statistics.median(walls)
-    roof = wl.roofline(launch_s)
-    roof['launch_us_how'] = ('HIP events on the launch stream around max(K, 2000) consecutive steps (pre-replayed 100-step hipGraphs) enqueued behind a '
-                             'lead-in chunk: kernel time only') if not heavy else 'HIP events on the launch stream around max(K, 200) consecutive steps behind a lead-in chunk'
-    roof['timed_region_event_us_per_step'] = [e / args.steps * 1e6 for e in evs]
-    if roof['bound'] == 'hbm':
-        pattern = {'headline': 'r*_bench_pmc_summary.json', 'C2': 'r*_c2_pmc_summary.json', 'C4': 'r*_c4_pmc_summary.json',
-                   'C4-lean': 'r*_c4lean_pmc_summary.json', 'T9': 'r*_kpi_t9_pmc_summary.json' if args.kpi else 'r*_t9_pmc_summary.json'}.get(cfg, 'none')
-        roof['traffic'], roof['traffic_source'] = _pmc_traffic(pattern, wl.kernels or '') if E == DEFAULT_ENVS[cfg] else (None, None)
-        if args.traffic_summary:
-            f = Path(args.traffic_summary)
-            c = json.loads(f.read_text())
-            if 'FETCH_SIZE' in c and 'WRITE_SIZE' in c and any(k and k in c.get('_kernel', {}).get('kernel', '') for k in (wl.kernels or '').split('+')):
-                roof['traffic'], roof['traffic_source'] = (2.0 * c['FETCH_SIZE']['mean'] + c['WRITE_SIZE']['mean']) * 1024.0, f.name
-    prec_args = ['--precision', args.precision]
-    if cfg == 'headline' and world == 1 and rank == 0 and not args.no_traffic_pass and E == DEFAULT_ENVS[cfg] and not args.kpi:
-        live, how = _live_traffic(wl.kernels or '', ['--table-hours', str(args.table_hours), *prec_args])
-        if live is not None:
-            roof['traffic_committed_file'] = {'traffic': roof.get('traffic'), 'source': roof.get('traffic_source')}
-            roof['traffic'], roof['traffic_source'] = live, how
-        else:
-            roof['traffic_live_error'] = how
-    if cfg == 'headline':
-        # (`bound` keeps the contract's vocabulary -- this path has no MFMA, so "hbm" -- but at THIS shape the bytes come out of the Infinity Cache)
-        roof['residency'] = 'infinity-cache (fabric bandwidth, not HBM)' if E * 17 * 52 < 256e6 else 'hbm'
+    if dumped:
+        shapes = write_outputs(dumped, args.dump_outputs)
+        dumped = None
+        print(f'bench.py: outputs of the last timed step in {args.dump_outputs}: ' + ', '.join(f'{k} {v}' for k, v in shapes.items()), file=sys.stderr)
+    roof = None
+    if args.full:
+        roof = wl.roofline(launch_s)
+        roof['launch_us_how'] = ('HIP events on the launch stream around max(K, 2000) consecutive steps (pre-replayed 100-step hipGraphs) enqueued behind a '
+                                 'lead-in chunk: kernel time only') if not heavy else 'HIP events on the launch stream around max(K, 200) consecutive steps behind a lead-in chunk'
+        roof['timed_region_event_us_per_step'] = [e / args.steps * 1e6 for e in evs]
+        if roof['bound'] == 'hbm':
+            pattern = {'headline': 'r*_bench_pmc_summary.json', 'C2': 'r*_c2_pmc_summary.json', 'C4': 'r*_c4_pmc_summary.json',
+                       'C4-lean': 'r*_c4lean_pmc_summary.json', 'T9': 'r*_kpi_t9_pmc_summary.json' if args.kpi else 'r*_t9_pmc_summary.json'}.get(cfg, 'none')
+            roof['traffic'], roof['traffic_source'] = _pmc_traffic(pattern, wl.kernels or '') if E == DEFAULT_ENVS[cfg] else (None, None)
+            if args.traffic_summary:
+                f = Path(args.traffic_summary)
+                c = json.loads(f.read_text())
+                if 'FETCH_SIZE' in c and 'WRITE_SIZE' in c and any(k and k in c.get('_kernel', {}).get('kernel', '') for k in (wl.kernels or '').split('+')):
+                    roof['traffic'], roof['traffic_source'] = (2.0 * c['FETCH_SIZE']['mean'] + c['WRITE_SIZE']['mean']) * 1024.0, f.name
+        prec_args = ['--precision', args.precision]
+        if cfg == 'headline' and world == 1 and rank == 0 and not args.no_traffic_pass and E == DEFAULT_ENVS[cfg] and not args.kpi:
+            live, how = _live_traffic(wl.kernels or '', ['--table-hours', str(args.table_hours), *prec_args])
+            if live is not None:
+                roof['traffic_committed_file'] = {'traffic': roof.get('traffic'), 'source': roof.get('traffic_source')}
+                roof['traffic'], roof['traffic_source'] = live, how
+            else:
+                roof['traffic_live_error'] = how
+        if cfg == 'headline':
+            # (`bound` keeps the contract's vocabulary -- this path has no MFMA, so "hbm" -- but at THIS shape the bytes come out of the Infinity Cache)
+            roof['residency'] = 'infinity-cache (fabric bandwidth, not HBM)' if E * 17 * 52 < 256e6 else 'hbm'
     units_per_step, n_bldg, spec, tables, what, env_pitch = wl.units_per_step, wl.eng.n_bldg, wl.spec, wl.tables, wl.what, wl.eng.env_pitch
 
     def streaming_entry(f64_s, with_traffic: bool):
@@ -744,7 +811,7 @@ def run_rank(args):
                 **({'traffic_live_error': s_live_error} if s_live_error else {}),
                 'value': world * s_units / launch}
 
-    if cfg == 'headline' and not args.no_streaming and E == ENVS_PER_GPU:
+    if args.full and cfg == 'headline' and not args.no_streaming and E == ENVS_PER_GPU:
         # `roofline` of the line = the HBM-TRUE figure (the field the metric calls "HBM GB/s vs roofline" must be an HBM
         # number): the step kernel on the same tables at 1 048 576 envs, measured live in this run like the metric shape -- HIP events on the launch
         # stream, counters from rocprofv3 child passes.  The launch the VALUE is timed on (17 x 65 536: its 58 MB working set sits in the
@@ -764,7 +831,7 @@ def run_rank(args):
                              'roofline is measured where the working set is 2.6 x the Infinity Cache -- same tables, same precision model, same run',
                      'metric_shape': metric_shape})
 
-    if cfg == 'headline' and default_precision and not args.kpi and not args.no_side_entries:
+    if args.full and cfg == 'headline' and default_precision and not args.kpi and not args.no_side_entries:
         # the all-fp32 battery map (`StepEngine(f64_maps=False)`): the throughput mode a user can opt into -- 1e-4 teacher-forced, but free-running it
         # drifts to 6.9 x the bar over config 1's year (tests/test_gpu_parity.py::test_full_year_free_running_every_step), which is why the
         # line is not quoted on it.  Its numbers at both shapes, same run:
@@ -785,7 +852,7 @@ def run_rank(args):
             side['hbm_streaming']['speedup_vs_default'] = roof['launch_us'] / fs['launch_us']
         roof['fp32_map'] = side
 
-    if cfg in ('C2', 'T9') and not args.no_side_entries and not args.kpi:
+    if args.full and cfg in ('C2', 'T9') and not args.no_side_entries and not args.kpi:
         # BASELINE config 2 (17 x 4 096 envs) is 2.7 MB per step: one launch per step is launch latency whatever the kernel does.
         # What a user who wants THROUGHPUT at this batch size gets is mode B -- 24 fused steps per launch, state in registers -- measured here beside mode A.
         wl = None
@@ -808,7 +875,7 @@ def run_rank(args):
     # N > 1 on a real node: BASELINE configs 4 and 5 measured in the same lease (their per-GPU shards, weak scaling like the headline) -- the
     # driver's scaling run is the only time anybody sees N > 1, so the line carries them as `extra_configs` (--no-extra-configs skips them)
     extra = {}
-    want_extra = (world > 1 and not oversubscribed and not args.no_extra_configs) or os.environ.get('CL_BENCH_EXTRA_CONFIGS') == '1'      # (the hook: 1-GPU tests)
+    want_extra = args.full and ((world > 1 and not oversubscribed and not args.no_extra_configs) or os.environ.get('CL_BENCH_EXTRA_CONFIGS') == '1')   # (the hook: 1-GPU tests)
     if cfg == 'headline' and want_extra:
         wl = None
         torch.cuda.empty_cache()
@@ -859,12 +926,14 @@ def run_rank(args):
             # ranks inside the RCCL communicator itself (`world_size_seen` is the gloo group every rank joins first); null when the control plane is gloo
             'rccl_world_size': None if dist is None else dist.rccl_world_size, 'control_backend': backend, **({'control_fallback': dist.control_fallback} if dist is not None and dist.control_fallback else {}),
             'rank_ms_per_step': [s / args.steps * 1e3 for s in per_rank],
+        }
+        if args.full:
             # kernel time only, per rank (HIP events around back-to-back steps): next to rank_ms_per_step it separates what the GPU took from
             # what the host's graph submission added -- 8 ranks share the host's usable cores
-            'rank_launch_us': [k * 1e6 for k in per_rank_kernel],
-            'rep_ms_per_step': [w / args.steps * 1e3 for w in walls],
-            'roofline': roof,
-        }
+            out['rank_launch_us'] = [k * 1e6 for k in per_rank_kernel]
+        out['rep_ms_per_step'] = [w / args.steps * 1e3 for w in walls]
+        if args.full:
+            out['roofline'] = roof
         if extra:
             out['extra_configs'] = extra
         if affinities is not None:
@@ -873,7 +942,7 @@ def run_rank(args):
             out['oversubscribed'] = True
             out['config']['note'] = (f'{world} ranks share {n_dev} GPU(s) (CL_BENCH_OVERSUBSCRIBE): exercises the multi-rank plumbing, NOT a scaling measurement; '
                                      'n_gpus = distinct devices')
-        if cfg == 'headline' and world == 1 and not args.no_cpu_baseline:
+        if args.full and cfg == 'headline' and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(spec, tables)
             out['dropin'] = dropin_timing(device, out['cpu_baseline'])
         print(json.dumps(out))
@@ -888,7 +957,7 @@ def parse_args(argv=None):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=None, help='timed steps K (default: 5000; 300 for C3, 200 for C5)')
     ap.add_argument('--warmup', type=int, default=None, help='untimed warmup steps W (default: 300; 30 for C3 / C5)')
-    ap.add_argument('--reps', type=int, default=5, help='timed repetitions of the K steps; the median is reported')
+    ap.add_argument('--reps', type=int, default=None, help='timed repetitions of the K steps; the median is reported (default: 1; 5 under --full)')
     ap.add_argument('--config', choices=CONFIGS, default='headline')
     ap.add_argument('--envs-per-gpu', type=int, default=None)
     ap.add_argument('--table-hours', type=int, choices=(720, 8760), default=8760,
@@ -910,6 +979,11 @@ def parse_args(argv=None):
     ap.add_argument('--f64-chain', action='store_true', help='= --precision chain (the default since round 6)')
     ap.add_argument('--kpi', action='store_true', help='CLD_KPI: update the streaming KPI accumulators every step (mode A-kpi of SURVEY 8d; step configs)')
     ap.add_argument('--launch-timeout', type=float, default=None, help='seconds after which self-spawned ranks are terminated')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path computed in its last timed step as DIR/<name>.npy (float32, at most 64 MB in all)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: kernel-time bracket and roofline, side entries, traffic passes, mode B, '
+                         'extra_configs, cpu_baseline, dropin (off: set up, warm up, time the K steps, dump, print the line)')
     args = ap.parse_args(argv)
     if args.fp32_map:
         args.precision = 'fp32'
@@ -922,6 +996,10 @@ def parse_args(argv=None):
         args.steps = {'C3': 300, 'C3-6': 200, 'C5': 200, 'C4-B': 100, 'C4-lean-B': 200}.get(args.config, 5000)
     if args.warmup is None:
         args.warmup = 30 if heavy else 300
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
+    if args.steps < 1 or args.warmup < 0 or args.reps < 1:
+        ap.error('--steps and --reps must be >= 1, --warmup >= 0')
     return args
 
 

@@ -42,6 +42,14 @@ def _copy_tree(src: Path, dst: Path, manifest: dict, rel_root: Path):
         manifest[str(out.relative_to(rel_root))] = hashlib.sha256(out.read_bytes()).hexdigest()
 
 
+def source_available(source: Path = SOURCE) -> bool:
+    """Whether the reference source tree is there and readable by this user (a tree this user may not enter counts as absent)."""
+    try:
+        return (source / 'citylearn' / 'citylearn.py').is_file()
+    except OSError:
+        return False
+
+
 def stage(source: Path = SOURCE, staged: Path = STAGED) -> dict:
     """Copy the pieces listed above and write MANIFEST.json (file -> sha256, version, when/where staged)."""
     if not (source / 'citylearn' / 'citylearn.py').is_file():

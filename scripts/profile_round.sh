@@ -24,15 +24,15 @@ chk() { python scripts/check_profiles.py "$@" >> $OUT/check.log || FAIL=1; }
 (timeout 1200 python -m pytest tests -m gpu -q > $OUT/gpu_suite.log 2>&1; echo "rc=$?" >> $OUT/gpu_suite.log); tail -4 $OUT/gpu_suite.log
 # ---- headline (default precision model = CLD_F64_CHAIN).  The line's `roofline` is the HBM-true 17 x 1 048 576 launch, `roofline.metric_shape` the
 # ---- cache-resident 17 x 65 536 launch `value` is timed on: rocprofv3 stats + counters for BOTH, each checked against its entry of the line
-python bench.py > $OUT/bench_line.json 2>$OUT/bench_line.err
-python bench.py --steps 20 --warmup 5 > $OUT/bench_line_driver_flags.json 2>/dev/null
-BENCH="python bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-streaming --no-traffic-pass --no-side-entries"
+python bench.py --full > $OUT/bench_line.json 2>$OUT/bench_line.err
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_line_driver_flags.json 2>/dev/null
+BENCH="python bench.py --full --steps 2000 --warmup 200 --no-cpu-baseline --no-streaming --no-traffic-pass --no-side-entries"
 trace bench $BENCH
 K=$(kernel_of $OUT/bench_line.json 0 metric)
-counters bench "$K" -- python bench.py --steps 300 --warmup 100 --no-cpu-baseline --no-graph --no-streaming --no-traffic-pass --no-side-entries
+counters bench "$K" -- python bench.py --full --steps 300 --warmup 100 --no-cpu-baseline --no-graph --no-streaming --no-traffic-pass --no-side-entries
 chk --duration-tol 0.05 --entry metric_shape $OUT/bench_line.json $OUT/${TAG}_bench_pmc_summary.json $OUT/bench_kernel_stats.csv
 # ---- HBM-streaming shape (17 x 1 048 576): the line's top-level roofline ----
-SB="python bench.py --envs-per-gpu 1048576 --no-cpu-baseline --no-streaming --no-traffic-pass --no-side-entries"
+SB="python bench.py --full --envs-per-gpu 1048576 --no-cpu-baseline --no-streaming --no-traffic-pass --no-side-entries"
 KS=$(kernel_of $OUT/bench_line.json)
 counters streaming "$KS" -- $SB --steps 30 --warmup 5 --reps 1 --no-graph
 $SB --steps 20 --warmup 5 --reps 3 --traffic-summary $OUT/${TAG}_streaming_pmc_summary.json > $OUT/bench_streaming_line.json 2>/dev/null
@@ -43,41 +43,41 @@ chk --duration-tol 0.05 $OUT/bench_line.json $OUT/streaming_kernel_stats.csv
 for c in C2 C3 C4 C4-lean C5 T9; do
   n=$(echo $c | tr 'A-Z' 'a-z' | tr -d '-')
   case $c in C2|C4|C4-lean|T9)
-    python bench.py --config $c --reps 1 --steps 500 > $OUT/tmp.json 2>/dev/null
-    counters $n "$(kernel_of $OUT/tmp.json)" -- python bench.py --config $c --steps 300 --warmup 50 --reps 1 --no-graph
-    python bench.py --config $c --traffic-summary $OUT/${TAG}_${n}_pmc_summary.json > $OUT/bench_$c.json 2>$OUT/bench_$c.err
+    python bench.py --full --config $c --reps 1 --steps 500 > $OUT/tmp.json 2>/dev/null
+    counters $n "$(kernel_of $OUT/tmp.json)" -- python bench.py --full --config $c --steps 300 --warmup 50 --reps 1 --no-graph
+    python bench.py --full --config $c --traffic-summary $OUT/${TAG}_${n}_pmc_summary.json > $OUT/bench_$c.json 2>$OUT/bench_$c.err
     chk $OUT/bench_$c.json $OUT/${TAG}_${n}_pmc_summary.json;;
-  *) python bench.py --config $c > $OUT/bench_$c.json 2>$OUT/bench_$c.err;;
+  *) python bench.py --full --config $c > $OUT/bench_$c.json 2>$OUT/bench_$c.err;;
   esac
-  trace $n python bench.py --config $c --reps 1
+  trace $n python bench.py --full --config $c --reps 1
   chk $OUT/bench_$c.json $OUT/${n}_kernel_stats.csv
 done
 # ---- BASELINE config 4 whole on one GPU: mode A with counters, mode B ----
 for c in C4 C4-lean; do
   n=$(echo $c | tr 'A-Z' 'a-z' | tr -d '-')_8192
-  python bench.py --config $c --envs-per-gpu 8192 --steps 500 --reps 1 > $OUT/tmp.json 2>/dev/null
-  counters $n "$(kernel_of $OUT/tmp.json)" -- python bench.py --config $c --envs-per-gpu 8192 --steps 200 --warmup 40 --reps 1 --no-graph
-  python bench.py --config $c --envs-per-gpu 8192 --steps 2000 --reps 3 --traffic-summary $OUT/${TAG}_${n}_pmc_summary.json > $OUT/bench_${c}_8192.json 2>/dev/null
-  trace $n python bench.py --config $c --envs-per-gpu 8192 --steps 2000 --reps 1
+  python bench.py --full --config $c --envs-per-gpu 8192 --steps 500 --reps 1 > $OUT/tmp.json 2>/dev/null
+  counters $n "$(kernel_of $OUT/tmp.json)" -- python bench.py --full --config $c --envs-per-gpu 8192 --steps 200 --warmup 40 --reps 1 --no-graph
+  python bench.py --full --config $c --envs-per-gpu 8192 --steps 2000 --reps 3 --traffic-summary $OUT/${TAG}_${n}_pmc_summary.json > $OUT/bench_${c}_8192.json 2>/dev/null
+  trace $n python bench.py --full --config $c --envs-per-gpu 8192 --steps 2000 --reps 1
   chk --duration-tol 0.05 $OUT/bench_${c}_8192.json $OUT/${TAG}_${n}_pmc_summary.json $OUT/${n}_kernel_stats.csv
 done
 for c in C4-B C4-lean-B; do
-  for E in 1024 8192; do python bench.py --config $c --envs-per-gpu $E > $OUT/bench_${c}_$E.json 2>/dev/null; done
+  for E in 1024 8192; do python bench.py --full --config $c --envs-per-gpu $E > $OUT/bench_${c}_$E.json 2>/dev/null; done
 done
-trace c4leanb python bench.py --config C4-lean-B --reps 1
-trace c4b python bench.py --config C4-B --reps 1
+trace c4leanb python bench.py --full --config C4-lean-B --reps 1
+trace c4b python bench.py --full --config C4-B --reps 1
 chk $OUT/bench_C4-B_1024.json $OUT/c4b_kernel_stats.csv
-for E in 1024 8192; do python bench.py --config C4-B --envs-per-gpu $E --precision fp32 > $OUT/bench_fp32_C4-B_$E.json 2>/dev/null; done
+for E in 1024 8192; do python bench.py --full --config C4-B --envs-per-gpu $E --precision fp32 > $OUT/bench_fp32_C4-B_$E.json 2>/dev/null; done
 # ---- the all-fp32 map (the opt-in throughput mode) and the float64 reference mode ----
-python bench.py --precision fp32 --no-cpu-baseline --no-traffic-pass > $OUT/bench_fp32.json 2>$OUT/bench_fp32.err
+python bench.py --full --precision fp32 --no-cpu-baseline --no-traffic-pass > $OUT/bench_fp32.json 2>$OUT/bench_fp32.err
 trace fp32 $BENCH --precision fp32
 chk --duration-tol 0.05 --entry metric_shape $OUT/bench_fp32.json $OUT/fp32_kernel_stats.csv
-for c in T9 C4 C4-lean C5; do python bench.py --config $c --precision fp32 > $OUT/bench_fp32_$c.json 2>/dev/null; done
-python bench.py --precision f64 --no-streaming --no-cpu-baseline --no-traffic-pass > $OUT/bench_f64_maps.json 2>/dev/null
+for c in T9 C4 C4-lean C5; do python bench.py --full --config $c --precision fp32 > $OUT/bench_fp32_$c.json 2>/dev/null; done
+python bench.py --full --precision f64 --no-streaming --no-cpu-baseline --no-traffic-pass > $OUT/bench_f64_maps.json 2>/dev/null
 # ---- streaming KPIs ----
-python bench.py --kpi --no-streaming --no-cpu-baseline --no-traffic-pass > $OUT/bench_kpi.json 2>/dev/null
-python bench.py --kpi --config T9 --no-cpu-baseline > $OUT/bench_kpi_T9.json 2>/dev/null
-python bench.py --kpi --config T9 --precision fp32 --no-cpu-baseline > $OUT/bench_kpi_T9_fp32.json 2>/dev/null
+python bench.py --full --kpi --no-streaming --no-cpu-baseline --no-traffic-pass > $OUT/bench_kpi.json 2>/dev/null
+python bench.py --full --kpi --config T9 --no-cpu-baseline > $OUT/bench_kpi_T9.json 2>/dev/null
+python bench.py --full --kpi --config T9 --precision fp32 --no-cpu-baseline > $OUT/bench_kpi_T9_fp32.json 2>/dev/null
 # ---- user-level timings ----
 for s in env_step_bench observe_bench ev_step_bench; do timeout 400 python scripts/$s.py > $OUT/${s}.log 2>$OUT/$s.err; done
 cat $OUT/check.log

@@ -16,8 +16,10 @@ ROOT = Path(__file__).resolve().parent.parent
 HARNESS = ROOT / 'oracle' / 'ref_harness'
 sys.path.insert(0, str(HARNESS))
 
-needs_reference = pytest.mark.skipif(not Path('/root/reference/citylearn/citylearn.py').is_file(),
-                                     reason='/root/reference exists only in the build container')
+import stage_reference  # noqa: E402
+
+needs_reference = pytest.mark.skipif(not stage_reference.source_available(),
+                                     reason='the reference source tree (stage_reference.SOURCE) is not readable here')
 
 
 @needs_reference

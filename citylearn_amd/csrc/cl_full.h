@@ -495,7 +495,7 @@ CL_DEV void full_accumulate(float (&q)[VEC], typename Vec<VEC>::type v) {
 // spends its time on (scripts/wave_timeline.py, 1024 x 1024: 2.1 us from entry to the first building's inputs, 1.9 us between
 // the first building's stores and the second one's inputs, next to 2 x 2.0 us of arithmetic).  As VGPR operands the parameters
 // also stop costing a v_mov per two-scalar instruction, and the SGPR file no longer spills.
-constexpr int CL_LP_WORDS = (CLP_F_LAST - CLP_F_FIRST + 1) + CL_NF;      // 64 + 16
+// (CL_LP_WORDS: cl_plan.h)
 
 // KPI (round 3, cl_step_full_kpi_kernel): the wave that steps a building also updates the building's streaming KPI accumulators
 // (CLD_KPI) -- net, baseline, expected and served energy are in its registers, the ten (outage steps: twelve) accumulator loads are
@@ -521,8 +521,7 @@ CL_DEV void full_step_body(const StepArgs& a, [[maybe_unused]] const ObsFusedArg
     constexpr int TILE = 64 * VEC;
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr bool SWAP = LP && CL_SWAP_GRID;             // (the LP instantiations are launched with grid = (building chunks, env tiles): district_reduce's note)
-    const int bx = SWAP ? blockIdx.y : blockIdx.x, by = SWAP ? blockIdx.x : blockIdx.y;
+    const int bx = blockIdx.x, by = blockIdx.y;
     const int env0 = bx * TILE + lane * VEC;
     const bool live = env0 < a.n_env;                     // n_env % 4 == 0 is enforced on the host
     const long long plane = (long long)a.n_bldg * a.n_env;
@@ -706,7 +705,7 @@ CL_DEV void full_step_body(const StepArgs& a, [[maybe_unused]] const ObsFusedArg
         }
     }
     if constexpr (OBS) obs_pad(*of, lds + (size_t)a.nw * NQ * TILE, TILE);
-    district_reduce<VEC, false, FOLDK, KPI, QLDS, SWAP>(a, lds, w, lane, env0, live, plane, rkind, q_net, q_cost, q_em, q_rw, a.nw, lds_fold);      // (LP, two envs per lane: the C4 shard's kernel, which may fold its chunk sums)
+    district_reduce<VEC, false, FOLDK, KPI, QLDS>(a, lds, w, lane, env0, live, plane, rkind, q_net, q_cost, q_em, q_rw, a.nw, lds_fold);      // (LP, two envs per lane: the C4 shard's kernel, which may fold its chunk sums)
     if constexpr (OBS) obs_flush(*of, lds + (size_t)a.nw * NQ * TILE, bx * TILE, min(TILE, a.n_env - bx * TILE));      // (district_reduce's first barrier came after every wave's tile writes; never chunked: host)
     if constexpr (KPI) {
         // baseline district series: the per-building baselines in cl_kpi_kernel's association (16 strided partial sums, added in order).

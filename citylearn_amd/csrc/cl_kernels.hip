@@ -9,9 +9,7 @@
 // run to run -- no atomics on the step path.
 #include "cl_trace.h"
 #include "cl_unit.h"
-#ifndef CL_SWAP_GRID
-#define CL_SWAP_GRID false      // chunk-major grids for the always-chunked kernels (district_reduce's SWAP note): measured, NOT the default; -DCL_SWAP_GRID=true: the A/B build
-#endif
+#include "cl_plan.h"
 #ifndef CL_LEAN_NT_LOADS
 #define CL_LEAN_NT_LOADS true          // A/B build flag: false = no non-temporal hint on any plane load of the latency-ordered lean kernels (lean_step_body's note)
 #endif
@@ -24,16 +22,6 @@
 #include <stdio.h>
 
 namespace {
-
-thread_local char g_err[512] = {0};
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
 
 int hip_fail(hipError_t e, const char* what) {
     return fail(CL_EHIP, "%s: %s", what, hipGetErrorString(e));
@@ -86,12 +74,7 @@ struct StepArgs {
     int fused_finish;   // building-chunked launches: the last chunk of an env tile folds the chunk partial sums itself (district_reduce)
 };
 
-constexpr int CL_OBS_FUSED_BLDG = 32;          // buildings a fused observation list can address (= the lean kernel's 2 x 16)
 constexpr int CL_OBS_FUSED_PER_BLDG = 4;      // observation columns per building the step launch writes itself
-
-// largest launch (env x building units) whose plane stores carry the non-temporal hint (see pstore)
-constexpr long long CL_NT_MAX_UNITS = 3ll << 20;
-constexpr long long CL_NT_STREAM_UNITS = 16ll << 20;      // ... and the smallest streaming-regime launch that takes it again
 
 template <int VEC> struct Vec;
 template <> struct Vec<1> { using type = float; };
@@ -209,7 +192,7 @@ CL_DEV void kpi_series_update(float* __restrict__ k, long long n_env, int t, flo
 //     (profiles/r04_c4_fold_breakdown.log; 13.0 / 7.8 us with the second launch, whose own 4 - 5 us mostly overlap the next step):
 //     double-buffered rows + marker only 13.7 / 8.1 -- step launches now run back to back, each starting into the previous one's
 //     draining stores; + load and stash 14.9 / 8.4; + add-up without the load 14.4 / 8.6; everything 15.3 / 9.0.
-// (`bx`, `by`: the workgroup's env tile and building chunk -- blockIdx.x / .y, or swapped: see CL_SWAP below)
+// (`bx`, `by`: the workgroup's env tile and building chunk -- blockIdx.x / .y)
 // (round 5) The exchange tile is [n_chunks][W] with W = 16, 32 or 64 district sums per workgroup row (`opw` rounded up; n_chunks x W <= 1024 =
 // one value per thread of the 16-wave workgroup: host): launches with FEWER, LARGER chunks defer too -- the whole BASELINE config 4 on one GPU
 // runs 8 chunks of 128 buildings (91 vs 103 us with 32 chunks of 32), where a workgroup row folds 64 sums, four per wave.
@@ -251,21 +234,20 @@ CL_DEV void fold_finish(const StepArgs& a, const float* lds_fold, int w, int lan
 // KPIS: the thread that writes an env's district net also feeds it to the env's streaming district accumulators (CLD_KPI, lean districts)
 // PRESTORED: the caller has kept the wave's partial sums in its LDS row all along (cl_full.h, the C4 shard's kernel: four accumulators fewer in
 // registers across the buildings of a wave) -- q_* are not read.
-// SWAP (round 5, measured and NOT the default: build with -DCL_SWAP_GRID=true): the launch's grid is (building chunks, env tiles) instead of
-// (env tiles, building chunks).  Workgroups go to the eight XCDs round-robin in x-major order: with the env tiles along x every XCD steps one
-// tile of EVERY chunk and fetches every building's parameter block and table row into its own L2 (C4 shard: 8 x 327 KB per step); with the
+// Grids are (env tiles, building chunks).  Round 5 measured the chunk-major grid, (building chunks, env tiles), and dropped it.  Workgroups go
+// to the eight XCDs round-robin in x-major order: with the env tiles along x every XCD steps one tile of EVERY chunk and fetches every building's parameter block and table row into its own L2 (C4 shard: 8 x 327 KB per step); with the
 // chunks along x an XCD owns a few chunks for all their env tiles.  The counters confirm the traffic -- C4 shard 64.68 -> 62.46 MB per step =
 // 1.039 x algorithmic -- and the clock says no: alternating builds on one box (profiles/r05e_*), thermal shard 13.12 - 13.15 us tile-major
 // against 13.66 - 13.76 us chunk-major, battery + PV shard 8.80 - 8.84 against 9.00 - 9.75 us, the whole thermal config (1024 x 8192) 101.0
 // against 109.9 us.  An XCD that owns four chunks touches 128 building rows of every plane instead of all 1024: its requests crowd a
 // fraction of the rows the memory system interleaves over, and 2 MB of parameter re-reads (L2 misses that the Infinity Cache serves) were
 // never on the critical path.
-template <int VEC, bool FLEX = false, bool FOLD = false, bool KPIS = false, bool PRESTORED = false, bool SWAP = false>
+template <int VEC, bool FLEX = false, bool FOLD = false, bool KPIS = false, bool PRESTORED = false>
 CL_DEV void district_reduce(const StepArgs& a, float* lds, int w, int lane, int env0, bool live, long long plane, int rkind,
                             const float (&q_net)[VEC], const float (&q_cost)[VEC], const float (&q_em)[VEC],
                             const float (&q_rw)[VEC], int stride, [[maybe_unused]] const float* lds_fold = nullptr) {
     constexpr int TILE = 64 * VEC;
-    const int bx = SWAP ? blockIdx.y : blockIdx.x, by = SWAP ? blockIdx.x : blockIdx.y;       // env tile, building chunk
+    const int bx = blockIdx.x, by = blockIdx.y;       // env tile, building chunk
     if constexpr (!PRESTORED) {
         float* mine = lds + (size_t)w * NQ * TILE + lane * VEC;
         vstore<VEC>(mine + 0 * TILE, q_net);
@@ -484,8 +466,7 @@ CL_DEV void district_reduce(const StepArgs& a, float* lds, int w, int lane, int 
 template <int VEC, bool FULL, bool DETAIL, bool FLEX = false, int PREC = 0, bool FOLD = false, bool CHECK = false>
 __global__ void __launch_bounds__(1024) cl_step_kernel(const StepArgs a) {
     constexpr bool F64 = PREC == 1;
-    constexpr bool SWAP = FOLD && CL_SWAP_GRID;            // (the FOLD instantiations are always launched building-chunked: grid = (chunks, env tiles))
-    const int bx = SWAP ? blockIdx.y : blockIdx.x, by = SWAP ? blockIdx.x : blockIdx.y;
+    const int bx = blockIdx.x, by = blockIdx.y;
     extern __shared__ __attribute__((aligned(16))) float lds[];     // [nw][NQ][64*VEC]
     constexpr int TILE = 64 * VEC;
     const int lane = threadIdx.x & 63;
@@ -656,7 +637,7 @@ __global__ void __launch_bounds__(1024) cl_step_kernel(const StepArgs a) {
             fold_stash(a, lds_fold, w, lane, fold_prev);
         }
     }
-    district_reduce<VEC, FLEX, FOLD, false, false, SWAP>(a, lds, w, lane, env0, live, plane, rkind, q_net, q_cost, q_em, q_rw, a.nw, lds_fold);
+    district_reduce<VEC, FLEX, FOLD>(a, lds, w, lane, env0, live, plane, rkind, q_net, q_cost, q_em, q_rw, a.nw, lds_fold);
 }
 
 // Building-chunked battery + PV districts (BASELINE config 4 with the 2022 device set), latency-ordered (round 5).  cl_step_kernel walks a
@@ -1625,49 +1606,10 @@ int check_ptr(const void* p, const char* name, bool required = true) {
     return CL_OK;
 }
 
-// Launch geometry.  Measured on MI355X (scripts/tune.py, profiles/): at ~1M units per launch the 16-wave
-// workgroup with 16-byte accesses (1 workgroup per CU, every wave one memory round trip) is fastest; the
-// full (thermal) kernel needs too many registers for VEC > 1.
-int pick_nw(int n_bldg, int /*vec*/) {
-    const int rounds = (n_bldg + 15) / 16;
-    int nw = (n_bldg + rounds - 1) / rounds;
-    if (n_bldg > 16 && n_bldg <= 32) nw = 16;            // e.g. 17 buildings: 16 waves, wave 0 takes two
-    return nw;
-}
-
-// envs per lane: wide (16 B) accesses once the batch is large enough to still give every CU a workgroup
-int pick_vec(int n_env, int n_bldg, bool unit_stride) {
-    if (!unit_stride) return 1;
-    // the narrowest pack that still gives at most one workgroup per CU (the lean kernels' launch shape): 49 152 envs at two envs per
-    // lane were 384 workgroups -- the general kernel, 9.8 us -- and are 192 latency-ordered ones at four (scripts/step_observe_bench.py)
-    if (n_env > 256 * 128) return 4;
-    if (n_env > 256 * 64) return 2;
-    (void)n_bldg;
-    return 1;
-}
-
 // Launch-geometry overrides travel with every call (cl_dims.tuning, include/citylearn_amd.h): the library holds no
 // mutable state besides the thread-local error string.
 const cl_tuning k_default_tuning = {};
-// launch K<..., NT> with NT = a.nt (expects grid, block, lds, s, a in scope)
-#define CL_LAUNCH_NT(K, ...) do { \
-    name_add(tun, #K "<" #__VA_ARGS__ ", %s>", a.nt ? "true" : "false"); \
-    if (a.nt) hipLaunchKernelGGL((K<__VA_ARGS__, true>), grid, block, lds, s, a); \
-    else hipLaunchKernelGGL((K<__VA_ARGS__, false>), grid, block, lds, s, a); } while (0)
-
 const cl_tuning& tuning_of(const cl_dims* d) { return d->tuning ? *d->tuning : k_default_tuning; }
-
-// cl_tuning.kernel_name (diagnostics): the instantiations a call launched, '+'-separated, spelled as rocprofv3 prints them
-void name_reset(const cl_tuning& tun) { if (tun.kernel_name) tun.kernel_name[0] = 0; }
-void name_add(const cl_tuning& tun, const char* fmt, ...) {
-    if (!tun.kernel_name) return;
-    size_t n = strnlen(tun.kernel_name, CL_KERNEL_NAME_LEN - 1);
-    if (n && n + 2 < CL_KERNEL_NAME_LEN) { tun.kernel_name[n++] = '+'; tun.kernel_name[n] = 0; }
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(tun.kernel_name + n, CL_KERNEL_NAME_LEN - n, fmt, ap);
-    va_end(ap);
-}
 
 }  // namespace
 
@@ -1701,44 +1643,73 @@ __global__ void cl_return_kernel(float* __restrict__ ret_env, const float* __res
     if (env < n_env) ret_env[env] += reward[env];
 }
 
-// the thermal kernels that write the compact observation themselves (cl_full.h OBS): more than 64 KB of dynamic LDS where the tile asks for it
-template <int PREC>
-int launch_full_obs(bool nt, dim3 grid, dim3 block, size_t lds, hipStream_t s, const StepArgs& a, const ObsFusedArgs& of, const cl_tuning& tun) {
-    name_add(tun, "cl_step_full_obs_kernel<%d, %s>", PREC, nt ? "true" : "false");
-    const void* fn = nt ? reinterpret_cast<const void*>(cl_step_full_obs_kernel<PREC, true>) : reinterpret_cast<const void*>(cl_step_full_obs_kernel<PREC, false>);
-    if (lds > 64 * 1024)
-        if (hipError_t e = ensure_dynamic_lds(fn, lds); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(cl_step_full_obs_kernel)");
-    if (nt) hipLaunchKernelGGL((cl_step_full_obs_kernel<PREC, true>), grid, block, lds, s, a, of);
-    else hipLaunchKernelGGL((cl_step_full_obs_kernel<PREC, false>), grid, block, lds, s, a, of);
-    return CL_OK;
-}
-template <int VEC, int PREC>
-int launch_tp_obs(bool nt, dim3 grid, dim3 block, size_t lds, hipStream_t s, const StepArgs& a, int tp, const ObsFusedArgs& of, const cl_tuning& tun) {
-    name_add(tun, "cl_step_full_tp_obs_kernel<%d, %d, %s>", VEC, PREC, nt ? "true" : "false");
-    if (lds > 150 * 1024) return fail(CL_EINVAL, "fused observation tile: %zu bytes of LDS", lds);
-    const void* fn = nt ? reinterpret_cast<const void*>(cl_step_full_tp_obs_kernel<VEC, PREC, true>) : reinterpret_cast<const void*>(cl_step_full_tp_obs_kernel<VEC, PREC, false>);
-    if (lds > 64 * 1024)
-        if (hipError_t e = ensure_dynamic_lds(fn, lds); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(cl_step_full_tp_obs_kernel)");
-    if (nt) hipLaunchKernelGGL((cl_step_full_tp_obs_kernel<VEC, PREC, true>), grid, block, lds, s, a, tp, of);
-    else hipLaunchKernelGGL((cl_step_full_tp_obs_kernel<VEC, PREC, false>), grid, block, lds, s, a, tp, of);
-    return CL_OK;
-}
-
-// cl_step_lean_chunk_kernel<VEC, NT, FOLD, PREC> from run-time launch parameters (VEC = 1 or 4); opts into more than 64 KB of dynamic LDS where the launch needs it
-template <int PREC>
-int launch_lean_chunk(int vec, bool nt, bool fold, dim3 grid, dim3 block, size_t lds, hipStream_t s, const StepArgs& a) {
-#define CL_LC(V, N, F) do { \
-        if (lds > 64 * 1024) { \
-            if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(cl_step_lean_chunk_kernel<V, N, F, PREC>), lds); e != hipSuccess) \
-                return hip_fail(e, "hipFuncSetAttribute(cl_step_lean_chunk_kernel)"); \
-        } \
-        hipLaunchKernelGGL((cl_step_lean_chunk_kernel<V, N, F, PREC>), grid, block, lds, s, a); } while (0)
-#define CL_LC_NF(V) do { if (nt) { if (fold) CL_LC(V, true, true); else CL_LC(V, true, false); } \
-                         else { if (fold) CL_LC(V, false, true); else CL_LC(V, false, false); } } while (0)
-    if (vec == 1) CL_LC_NF(1); else if (vec == 2) CL_LC_NF(2); else CL_LC_NF(4);
-#undef CL_LC_NF
+// The instantiation a plan launches, one switch over the kernel families (plan_name in cl_plan.h spells the same plan fields).  The fp32 lean
+// kernel without flexible loads is not here: it lives in the no-SLP unit (cl_tu_launch_lean).
+const void* step_kernel_fn(const StepPlan& p) {
+#define CL_K(...) reinterpret_cast<const void*>(__VA_ARGS__)
+#define CL_NT(K, ...) (p.nt ? CL_K(K<__VA_ARGS__, true>) : CL_K(K<__VA_ARGS__, false>))
+#define CL_V124(K) (p.vec == 1 ? CL_NT(K, 1) : p.vec == 2 ? CL_NT(K, 2) : CL_NT(K, 4))
+#define CL_LC(V, F, P) (p.nt ? CL_K(cl_step_lean_chunk_kernel<V, true, F, P>) : CL_K(cl_step_lean_chunk_kernel<V, false, F, P>))
+#define CL_LC_V(F, P) (p.vec == 1 ? CL_LC(1, F, P) : p.vec == 2 ? CL_LC(2, F, P) : CL_LC(4, F, P))
+#define CL_EM(NB, V, P) (p.nt ? CL_K(cl_step_envmajor_kernel<NB, true, V, P>) : CL_K(cl_step_envmajor_kernel<NB, false, V, P>))
+    switch (p.kernel) {
+    case CLK_STEP:
+        if (p.check)
+            return p.flex ? CL_K(cl_step_kernel<1, true, true, true, 0, false, true>) : p.prec == 2 ? CL_K(cl_step_kernel<1, true, true, false, 2, false, true>)
+                 : p.prec == 1 ? CL_K(cl_step_kernel<1, true, true, false, 1, false, true>) : CL_K(cl_step_kernel<1, true, true, false, 0, false, true>);
+        if (p.fold) return p.vec == 1 ? CL_K(cl_step_kernel<1, false, false, false, 0, true>) : CL_K(cl_step_kernel<4, false, false, false, 0, true>);
+        if (p.prec == 2)
+            return p.full ? (p.det ? CL_K(cl_step_kernel<1, true, true, false, 2>) : CL_K(cl_step_kernel<1, true, false, false, 2>))
+                 : p.vec == 1 ? CL_K(cl_step_kernel<1, false, false, false, 2>) : p.vec == 2 ? CL_K(cl_step_kernel<2, false, false, false, 2>)
+                 : CL_K(cl_step_kernel<4, false, false, false, 2>);
+        if (p.prec == 1)
+            return p.full ? (p.det ? CL_K(cl_step_kernel<1, true, true, false, 1>) : CL_K(cl_step_kernel<1, true, false, false, 1>))
+                 : p.vec == 1 ? CL_K(cl_step_kernel<1, false, false, false, 1>) : CL_K(cl_step_kernel<2, false, false, false, 1>);
+        if (p.flex)
+            return p.det ? (p.vec == 1 ? CL_K(cl_step_kernel<1, true, true, true>) : CL_K(cl_step_kernel<2, true, true, true>))
+                 : p.full ? (p.vec == 1 ? CL_K(cl_step_kernel<1, true, false, true>) : CL_K(cl_step_kernel<2, true, false, true>))
+                 : p.vec == 1 ? CL_K(cl_step_kernel<1, false, false, true>) : CL_K(cl_step_kernel<2, false, false, true>);
+        if (p.full)
+            return p.det ? (p.vec == 1 ? CL_K(cl_step_kernel<1, true, true>) : CL_K(cl_step_kernel<2, true, true>))
+                 : p.vec == 1 ? CL_K(cl_step_kernel<1, true, false>) : CL_K(cl_step_kernel<2, true, false>);
+        return p.vec == 1 ? CL_K(cl_step_kernel<1, false, false>) : p.vec == 2 ? CL_K(cl_step_kernel<2, false, false>) : CL_K(cl_step_kernel<4, false, false>);
+    case CLK_LEAN_CHUNK:
+        return p.prec == 2 ? (p.fold ? CL_LC_V(true, 2) : CL_LC_V(false, 2)) : (p.fold ? CL_LC_V(true, 0) : CL_LC_V(false, 0));
+    case CLK_LEAN:
+        if (p.prec == 1) return p.vec == 1 ? CL_NT(cl_step_lean_f64_kernel, 1) : CL_NT(cl_step_lean_f64_kernel, 2);
+        if (p.prec == 2)
+            return p.form == CLF_KPI ? CL_V124(cl_step_lean_kpi_chain_kernel) : p.form == CLF_OBS ? CL_V124(cl_step_lean_obs_chain_kernel) : CL_V124(cl_step_lean_chain_kernel);
+        if (p.form == CLF_KPI) return CL_V124(cl_step_lean_kpi_kernel);
+        if (p.form == CLF_OBS) return CL_V124(cl_step_lean_obs_kernel);
+        return p.vec == 1 ? CL_NT(cl_step_lean_kernel, 1, true) : p.vec == 2 ? CL_NT(cl_step_lean_kernel, 2, true) : CL_NT(cl_step_lean_kernel, 4, true);
+    case CLK_ENVMAJOR:
+        if (p.prec == 2) return p.nb == 17 ? CL_EM(17, 1, 2) : CL_EM(20, 1, 2);
+        return p.nb == 17 ? (p.vec == 2 ? CL_EM(17, 2, 0) : CL_EM(17, 1, 0)) : (p.vec == 2 ? CL_EM(20, 2, 0) : CL_EM(20, 1, 0));
+    case CLK_FULL:
+        if (p.form == CLF_KPI) return p.nt ? CL_K(cl_step_full_kpi_kernel<true>) : CL_K(cl_step_full_kpi_kernel<false>);
+        if (p.form == CLF_OBS) return p.prec == 2 ? CL_NT(cl_step_full_obs_kernel, 2) : CL_NT(cl_step_full_obs_kernel, 0);
+        if (p.prec == 2)
+            return p.det ? CL_NT(cl_step_full_chain_kernel, 1, true, 1024, 4, false) : p.lp ? CL_NT(cl_step_full_chain_kernel, 1, false, 1024, 4, true)
+                 : CL_NT(cl_step_full_chain_kernel, 1, false, 1024, 4, false);
+        if (p.det)
+            return p.vec == 1 ? CL_NT(cl_step_full_kernel, 1, true, 1024, 4, false) : p.maxt == 576 ? CL_NT(cl_step_full_kernel, 2, true, 576, 3, false)
+                 : CL_NT(cl_step_full_kernel, 2, true, 1024, 4, false);
+        if (p.lp) return p.vec == 1 ? CL_NT(cl_step_full_kernel, 1, false, 1024, 5, true) : CL_NT(cl_step_full_kernel, 2, false, 1024, 4, true);
+        if (p.vec == 1) return CL_NT(cl_step_full_kernel, 1, false, 1024, CL_FULL1_WPE, false);
+        return p.maxt == 576 ? CL_NT(cl_step_full_kernel, 2, false, 576, 5, false) : CL_NT(cl_step_full_kernel, 2, false, 1024, 5, false);
+    case CLK_FULL_TP:
+        if (p.form == CLF_OBS)
+            return p.prec == 2 ? CL_NT(cl_step_full_tp_obs_kernel, 1, 2) : p.vec == 2 ? CL_NT(cl_step_full_tp_obs_kernel, 2, 0) : CL_NT(cl_step_full_tp_obs_kernel, 1, 0);
+        if (p.prec == 2) return CL_NT(cl_step_full_tp_chain_kernel, 1, 4);
+        return p.vec == 2 ? CL_NT(cl_step_full_tp_kernel, 2, 4) : CL_NT(cl_step_full_tp_kernel, 1, 4);
+    }
+#undef CL_EM
+#undef CL_LC_V
 #undef CL_LC
-    return CL_OK;
+#undef CL_V124
+#undef CL_NT
+#undef CL_K
+    return nullptr;
 }
 }  // namespace
 
@@ -1816,10 +1787,6 @@ int cl_flex_reset_f32(const cl_dims* dims, const cl_flex* flex, void* stream) {
 static int step_impl(const cl_dims* dims, const uint32_t* params, const float* ts, float* state, const float* actions,
                      int64_t act_stride_col, int64_t act_stride_env, float* out_bldg, float* out_env, float* kpi_bldg,
                      float* kpi_env, const cl_flex* flex, int32_t t, void* stream, const ObsFusedArgs* of, bool* fused) {
-    // (`of`: the compact observation the step launch may write itself -- the battery + PV kernels under their own limits (`lean_ok`), the thermal
-    //  kernels of cl_full.h for any listed battery / tank / net / reward column)
-    const ObsFusedArgs* const of_full = of;
-    if (of && !of->lean_ok) of = nullptr;
     if (int rc = check_dims(dims)) return rc;
     const cl_tuning& tun = tuning_of(dims);
     name_reset(tun);
@@ -1831,7 +1798,7 @@ static int step_impl(const cl_dims* dims, const uint32_t* params, const float* t
     if (int rc = check_ptr(out_env, "out_env")) return rc;
     if (dims->flags & CLD_KPI) {
         // the per-building accumulators read the detail planes -- except for districts of up to 32 buildings without flexible loads, whose
-        // step kernel updates them itself (cl_step_lean_kpi_kernel / cl_step_full_kpi_kernel; the launch selection below refuses the rest)
+        // step kernel updates them itself (cl_step_lean_kpi_kernel / cl_step_full_kpi_kernel; plan_step refuses the rest)
         if (!(dims->flags & CLD_WRITE_DETAIL) && (dims->n_bldg > 32 || flex))
             return fail(CL_EINVAL, "CLD_KPI requires CLD_WRITE_DETAIL (except for districts of up to 32 buildings without flexible loads)");
         if (int rc = check_ptr(kpi_bldg, "kpi_bldg")) return rc;
@@ -1841,6 +1808,18 @@ static int step_impl(const cl_dims* dims, const uint32_t* params, const float* t
     if (act_stride_env == 1 && (act_stride_col % 4) != 0)
         return fail(CL_EALIGN, "act_stride_col=%lld must be a multiple of 4 floats for the coalesced layout",
                     (long long)act_stride_col);
+    const int ld = pitch_of(dims);
+    // a pitch is implemented where 2^20-env batches exist: battery + PV districts stepped by the lean / env-major / general lean kernels
+    if (ld != dims->n_env && (!(dims->flags & CLD_LEAN) || (dims->flags & (CLD_WRITE_DETAIL | CLD_KPI | CLD_F64_MAPS)) || flex || dims->n_bldg > 32))
+        return fail(CL_EINVAL, "env_pitch=%d != n_env=%d is implemented for CLD_LEAN districts of up to 32 buildings without detail planes, streaming KPIs, "
+                               "flexible loads or CLD_F64_MAPS", ld, dims->n_env);
+    const int rkind_host = (dims->flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT;
+    if (rkind_host == CLR_EV && !flex) return fail(CL_EINVAL, "reward kind CLR_EV needs the flexible-load tables (cl_step_flex_f32)");
+    if (flex)
+        if (int rc = check_flex(dims, flex)) return rc;
+    StepPlan p;
+    if (int rc = plan_step(p, *dims, tun, act_stride_env, flex, of, of && of->lean_ok, of ? of->pitch : 0)) return rc;
+    plan_name(p, tun);
 
     StepArgs a;
     a.params = params; a.ts = ts; a.state = state; a.actions = actions; a.out_bldg = out_bldg; a.out_env = out_env;
@@ -1848,531 +1827,47 @@ static int step_impl(const cl_dims* dims, const uint32_t* params, const float* t
     a.act_stride_col = act_stride_col; a.act_stride_env = act_stride_env;
     a.n_env = dims->n_env; a.n_bldg = dims->n_bldg; a.n_steps = dims->n_steps;
     a.flags = dims->flags; a.t = t; a.env_row0 = dims->env_row0; a.env_offset = (unsigned)dims->env_offset;
-    a.ld = pitch_of(dims);
-    // a pitch is implemented where 2^20-env batches exist: battery + PV districts stepped by the lean / env-major / general lean kernels
-    if (a.ld != a.n_env && (!(dims->flags & CLD_LEAN) || (dims->flags & (CLD_WRITE_DETAIL | CLD_KPI | CLD_F64_MAPS)) || flex || dims->n_bldg > 32))
-        return fail(CL_EINVAL, "env_pitch=%d != n_env=%d is implemented for CLD_LEAN districts of up to 32 buildings without detail planes, streaming KPIs, "
-                               "flexible loads or CLD_F64_MAPS", a.ld, a.n_env);
+    a.ld = ld;
     a.flex_out = nullptr; a.n_flex_bldg = 0; a.ev_penalty_coef = 0.0f;
-    a.fused_finish = 0;                       // set where the kernel that is launched can fold the chunk sums itself (district_reduce<.., FOLD>)
-    // non-temporal plane stores while the launch's footprint (~40 - 60 B per (env, building) unit) stays inside the Infinity Cache
-    // ... and again once it is several times that cache (17 x 1 048 576: 125 -> 115 us, 17 x 1 572 864: 196 -> 170 us): nothing of a step
-    // survives in the cache until the next one anyway, and the hint keeps the stores from displacing what the step still reads.  In
-    // between (footprint of the order of the cache: 17 x 262 144 +10 %, 17 x 524 288 +-4 %) plain stores win.
-    const long long nt_units = (long long)dims->n_env * dims->n_bldg;
-    a.nt = tun.nt_stores == 1 || (tun.nt_stores == 0 && (nt_units <= CL_NT_MAX_UNITS || nt_units >= CL_NT_STREAM_UNITS));
-    const int rkind_host = (dims->flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT;
-    if (rkind_host == CLR_EV && !flex) return fail(CL_EINVAL, "reward kind CLR_EV needs the flexible-load tables (cl_step_flex_f32)");
+    a.nw = p.nw; a.b_chunk = p.b_chunk; a.n_chunks = p.n_chunks; a.nt = p.nt; a.fused_finish = p.fused_finish;
+    hipStream_t s = (hipStream_t)stream;
     if (flex) {
-        if (int rc = check_flex(dims, flex)) return rc;
         FlexArgs fa;
         fa.f = *flex; fa.actions = actions; fa.act_stride_col = act_stride_col; fa.act_stride_env = act_stride_env;
         fa.env_row0 = dims->env_row0; fa.n_env = dims->n_env; fa.n_steps = dims->n_steps; fa.t = t; fa.env_offset = (unsigned)dims->env_offset;
         fa.want_reward = rkind_host == CLR_EV;
         fa.want_chargers = (dims->flags & CLD_WRITE_DETAIL) != 0;
-        const int units = flex->n_flex_bldg + flex->n_ev;
-        const unsigned gy = (unsigned)((units + 3) / 4);
-        // four envs per lane once there are enough envs to fill the chip that way (and plane rows stay 16-byte aligned)
-        int fvec = dims->n_env >= 16384 ? 4 : 1;
-        if (tun.flex_vec) fvec = tun.flex_vec;
-        const dim3 fgrid((unsigned)((dims->n_env + 64 * fvec - 1) / (64 * fvec)), gy);
+        const dim3 fgrid(p.flex_grid_x, (unsigned)((flex->n_flex_bldg + flex->n_ev + 3) / 4));
 #define CL_FLEX_LAUNCH(V) do { \
-            name_add(tun, "cl_flex_kernel<" #V ", %s>", a.nt ? "true" : "false"); \
-            if (a.nt) hipLaunchKernelGGL((cl_flex_kernel<V, true>), fgrid, dim3(256), 0, (hipStream_t)stream, fa); \
-            else hipLaunchKernelGGL((cl_flex_kernel<V, false>), fgrid, dim3(256), 0, (hipStream_t)stream, fa); } while (0)
-        switch (fvec) {
-        case 4: CL_FLEX_LAUNCH(4); break;
-        case 2: CL_FLEX_LAUNCH(2); break;
-        default: CL_FLEX_LAUNCH(1); break;
-        }
+            if (p.flex_nt) hipLaunchKernelGGL((cl_flex_kernel<V, true>), fgrid, dim3(256), 0, s, fa); \
+            else hipLaunchKernelGGL((cl_flex_kernel<V, false>), fgrid, dim3(256), 0, s, fa); } while (0)
+        if (p.flex_vec == 4) CL_FLEX_LAUNCH(4); else if (p.flex_vec == 2) CL_FLEX_LAUNCH(2); else CL_FLEX_LAUNCH(1);
 #undef CL_FLEX_LAUNCH
         a.flex_out = flex->flex_out; a.n_flex_bldg = flex->n_flex_bldg;
         a.ev_penalty_coef = flex->cons_params ? flex->weights[CLEW_PENALTY_COEFFICIENT] : 0.0f;
     }
-    const bool full = !(dims->flags & CLD_LEAN) || (dims->flags & CLD_WRITE_DETAIL) || (tun.lean_variant & 4);   // 4: lean districts through cl_step_full_kernel (experiments)
-    a.nw = tun.nw ? tun.nw : pick_nw(dims->n_bldg, 1);
-    // general kernel: two buildings per wave measured fastest for the 6..16-building thermal schemas (fewer, longer waves)
-    if (!tun.nw && full && dims->n_bldg >= 6 && dims->n_bldg <= 16) a.nw = (dims->n_bldg + 1) / 2;
-    const bool will_chunk = dims->n_bldg > 32 && !tun.no_chunks;
-    int vec = full ? 1 : pick_vec(dims->n_env, dims->n_bldg, act_stride_env == 1);
-    if (will_chunk && act_stride_env == 1) {               // few envs, many buildings: width from the unit count
-        const long long units = (long long)dims->n_env * dims->n_bldg;
-        // (under the float64 chain the four-env pack pays off one octave later -- scripts/r06_cliffs.py, profiles/r06c_cliffs_chain.jsonl: 33 x 16 384 and
-        //  128 x 4 096, both 2^19 units, 13.8 / 12.6 us at four envs per lane against 12.2 / 9.8 us at one)
-        const long long lean4 = (dims->flags & CLD_F64_CHAIN) ? (1ll << 20) : (1ll << 19);
-        vec = full ? (units >= (1ll << 19) && dims->n_env >= 256 ? 2 : 1) : (units >= lean4 && dims->n_env >= 512 ? 4 : 1);
-        // (chain, districts just beyond the 32-building limit of the one-row kernels on batches of >= 2048 one-env tiles: two rows of ~17 buildings at four
-        //  envs per lane leave every wave one or two buildings behind a long load chain -- 33 x 262 144: 117.5 us against 74 us for the UNCHUNKED general
-        //  kernel at one env per lane, which the grid rule below selects by itself once the tile count reaches 2048; profiles/r06d_cliffs_chain.jsonl)
-        if (!full && (dims->flags & CLD_F64_CHAIN) && dims->n_bldg <= 40 && dims->n_env >= 131072) vec = 1;
-    }
-    if (tun.vec) vec = tun.vec;
-    // CLD_F64_MAPS: the battery map in float64 -- general and lean step kernels at one or two envs per lane (a double is two VGPRs)
-    const bool f64 = dims->flags & CLD_F64_MAPS;
-    // CLD_F64_CHAIN: the soc chain in float64 on the default three state planes (cl_unit.h battery_charge_chain) -- lean, env-major, general and
-    // thermal-specialised step kernels
-    const bool chain = dims->flags & CLD_F64_CHAIN;
-    if (chain) {
-        if (f64) return fail(CL_EINVAL, "CLD_F64_CHAIN and CLD_F64_MAPS are two precision models of the same map: pick one");
-        if (flex) return fail(CL_EINVAL, "CLD_F64_CHAIN is not implemented for districts with flexible loads (the EV batteries of cl_flex_kernel are fp32)");
-        // (streaming KPIs without the detail planes: the lean step launch updates them itself under the chain too; a thermal district needs the planes)
-        if ((dims->flags & CLD_KPI) && !(dims->flags & CLD_WRITE_DETAIL) && (full || dims->n_bldg > 32))
-            return fail(CL_EINVAL, "CLD_F64_CHAIN with CLD_KPI needs CLD_WRITE_DETAIL (except for battery + PV districts of up to 32 buildings)");
-        if (full) vec = 1;                     // (the thermal unit around the float64 chain spills at two envs per lane)
-    }
-    if (f64) {
-        if (flex) return fail(CL_EINVAL, "CLD_F64_MAPS is not implemented for districts with flexible loads (the EV batteries of cl_flex_kernel are fp32)");
-        if ((dims->flags & CLD_KPI) && !(dims->flags & CLD_WRITE_DETAIL)) return fail(CL_EINVAL, "CLD_F64_MAPS with CLD_KPI needs CLD_WRITE_DETAIL");
-        vec = full ? 1 : (vec > 2 ? 2 : vec);          // (the thermal unit with a float64 battery spills at two envs per lane)
-    }
-    if (flex && vec > 2 && !(!full && dims->n_bldg <= 2 * a.nw && !will_chunk && (dims->n_env + 64 * vec - 1) / (64 * vec) <= 256 && !(tun.lean_variant & 1)))
-        vec = 2;                             // general-kernel FLEX instantiations exist for 1 and 2 envs per lane
-    const int tile = 64 * vec;
-    const unsigned grid_x = (unsigned)((dims->n_env + tile - 1) / tile);
-    // Large districts (e.g. 1024 buildings x 1024 envs per GPU): a 1-D grid over env tiles would leave most CUs idle, so
-    // the buildings are cut into chunks along gridDim.y and the district sums are finished by a second tiny kernel.
-    a.b_chunk = dims->n_bldg; a.n_chunks = 1;
-    if (dims->n_bldg > 32 && grid_x < 2048 && !tun.no_chunks) {
-        long long r = ((long long)dims->n_bldg * grid_x) / (16ll * 2048);
-        if (r < 1) r = 1;
-        // about one 16-wave workgroup per CU when the launch is small: the 1024 x 1024 thermal shard at two envs per lane then gives
-        // every wave two buildings (32 chunks x 8 env tiles = 256 workgroups, all resident at once): 16.0 vs 18.0 us with one
-        // building per wave in two generations (scripts/c4_sweep.py, profiles/r02_c4_chunk_sweep.log)
-        const long long per_cu = ((long long)dims->n_bldg * grid_x + 2048) / 4096;
-        if (per_cu >= 2 && r < 2) r = 2;
-        // (round 5) the thermal kernel with staged parameter blocks (cl_full.h LP) on batches of several workgroup generations: FEWER, LARGER
-        // chunks -- one or two workgroups per CU, each wave walking 8 - 16 buildings -- instead of eight generations of two buildings per
-        // wave.  1024 buildings (scripts/gpurun/r05_call12.sh, profiles/r05m_*): x 8192 envs 103.0 / 95.3 / 91.4 / 91.6 us with chunks of
-        // 32 / 64 / 128 / 256; x 4096: 55.0 / 50.9 / 48.7 / 78.4 (128 workgroups leave half the CUs idle); x 2048: 26.6 / 30.1 / 36.4 / 61.0
-        // and x 1024: 13.2 / 21.5 / 34.5 / 60.2 -- those stay at 32.  (Battery + PV districts, cl_step_kernel: 32 stays best, 8192 envs:
-        // 63.8 / 60.3 / 64.9 / 67.4 us with 24 / 32 / 48 / 64.)
-        const bool lp_shape = !(dims->flags & CLD_LEAN) && !(tun.lean_variant & 4) && !flex && !(dims->flags & (CLD_WRITE_DETAIL | CLD_F64_MAPS)) && vec == 2 &&
-                              tun.full_variant != 1 && tun.full_variant != 3;
-        if (lp_shape && dims->n_bldg >= 256 && (long long)dims->n_bldg * grid_x >= 32ll * 1024) {     // (measured on 1024 buildings; smaller districts keep the rule above)
-            long long want = ((long long)dims->n_bldg * grid_x + 255) / 256;          // buildings per chunk for 256 workgroups ...
-            r = 2; while (16 * r < want && r < 8) r *= 2;                            // ... as a power of two, 128 at most (40 KB of staged blocks)
-        }
-        // (round 6) the thermal kernel around the float64 chain (one env per lane, parameter blocks through the constant cache): ONE workgroup per CU --
-        // 256 workgroups, chunks of up to 256 buildings.  1024 buildings x 1024 / 2048 / 4096 / 8192 envs with chunks of 32 / 64 / 128 / 256:
-        // 20.2 / 17.7 / 27.4 / 47.6, 37.4 / 33.5 / 31.3 / 48.8, 71.3 / 68.7 / 67.5 / 65.8, 149.7 / 137.3 / 129.5 / 125.4 us
-        // (scripts/gpurun/r06_call15.sh, profiles/r06o_*).
-        const bool chain_full_shape = chain && !(dims->flags & CLD_LEAN) && !flex && !(dims->flags & (CLD_WRITE_DETAIL | CLD_F64_MAPS)) && tun.full_variant != 1;
-        // 128 .. 1024 buildings x 1024 .. 65 536 envs (scripts/r06_chunk_sweep.py, profiles/r06p_chunks_*.jsonl): the rule is within 3 % of the best chunk size
-        // of every cell -- 128 x 16 384 36.4 -> 25.6 us, 256 x 16 384 66.9 -> 49.2, 512 x 16 384 153 -> 126, 1024 x 16 384 317 -> 249 (chunks as large as
-        // the district = one workgroup row, no second launch)
-        if (chain_full_shape && dims->n_bldg >= 128 && (long long)dims->n_bldg * grid_x >= 16ll * 1024) {
-            const long long want = ((long long)dims->n_bldg * grid_x + 255) / 256;
-            r = 2; while (16 * r < want && r < 16) r *= 2;
-        }
-        // (fp32 map, same sweep: up to 256 buildings x 65 536 envs in ONE workgroup row -- 128 buildings 113 -> 98 us, 256 buildings 204 -> 182 us; at
-        //  16 384 envs the chunked launch stays ahead, 29.0 vs 32.4 and 49.0 vs 59.1 us)
-        if (lp_shape && dims->n_bldg <= 256 && grid_x >= 512) r = 16;
-        // ... whose plane stores take the non-temporal hint at every batch size (the footprint rule above is the battery + PV kernels': 1024 x
-        // 8192 envs 101.2 -> 100.0 us, x 4096 54.3 -> 53.3 us, chunks of 128: 91.4 -> 89.1 us; profiles/r05l_*, r05m_*)
-        if (lp_shape && tun.nt_stores == 0) a.nt = 1;
-        a.b_chunk = tun.b_chunk > 0 ? tun.b_chunk : (int)(16 * r);
-        a.n_chunks = (dims->n_bldg + a.b_chunk - 1) / a.b_chunk;
-        if (tun.b_chunk <= 0 && a.n_chunks > 1) {
-            // balanced chunks (round 6): 33 buildings were cut 16 + 16 + 1 -- a third workgroup row per env tile for one building; now round(33 / 16) = 2
-            // rows of 17 (one wave of the sixteen walks two buildings).  Districts that divide evenly (1024 / 32) keep their geometry.
-            const int nc = (int)((2ll * dims->n_bldg + a.b_chunk) / (2ll * a.b_chunk));       // round(n_bldg / b_chunk)
-            if (nc >= 2) { a.n_chunks = nc; a.b_chunk = (dims->n_bldg + nc - 1) / nc; a.n_chunks = (dims->n_bldg + a.b_chunk - 1) / a.b_chunk; }
-        }
-        if (a.n_chunks == 1) a.b_chunk = dims->n_bldg;
-        else a.nw = (tun.b_chunk > 0 && tun.nw > 0) ? tun.nw : 16;
-        // the reserved plane holds the chunk partial sums (twice under the deferred finish), the tickets of the in-launch fold and, in its
-        // last 16 bytes, the marker words EVERY chunked launch touches (a non-deferring one clears its step's marker)
-        // (the second buffer only where the launch can defer at all: finish = 3 on a launch that keeps the second cl_finish launch needs one)
-        const long long scratch_words = (long long)a.n_chunks * NQ * dims->n_env + (dims->n_env + 63) / 64 + 4;
-        if (scratch_words > (long long)dims->n_bldg * dims->n_env)
-            return fail(CL_EINVAL, "b_chunk=%d leaves no room for the %d chunk partial sums, their tickets and the marker words", a.b_chunk, a.n_chunks);
-    }
-    if (a.n_chunks > 1 && rkind_host == CLR_EV)
-        return fail(CL_EINVAL, "reward kind CLR_EV is not implemented for building-chunked launches (n_bldg=%d)", dims->n_bldg);
-    // Deferred finish (cl_tuning.finish = 3): the launch folds the PREVIOUS step's chunk sums and leaves its own for the next launch or for
-    // cl_finish_f32 (district_reduce).  Only where nothing of the path reads out_env inside the step: no coupled reward (MARL's per-building
-    // rewards need the district net of the same step, reward_function.py:132-143; the EV reward likewise), no streaming KPIs, no flexible
-    // loads, and the kernels that carry the fold (the FOLD instantiations below); a 16-wave workgroup folds at most 64 district sums of at most 64 chunks, 1024 partial sums in all,
-    // and the reserved plane has to hold both buffers and the marker words.  Anything else keeps the second launch.
-    const int fold_per_row = a.n_chunks > 1 ? (NQ * tile + a.n_chunks - 1) / a.n_chunks : 0;
-    // (battery + PV districts keep the 16-sum limit: where more sums per row would be needed -- 1024 x 4096 / 8192 envs at four envs per lane --
-    //  the folding instantiation's 107 registers cost more than the second launch: 32.8 vs 32.0 us, 65.2 vs 61.3 us, profiles/r05n_*)
-    const int fold_w = fold_per_row <= 16 ? 16 : fold_per_row <= 32 ? 32 : 64;          // row width of the exchange tile (fold_shift)
-    const bool can_defer = a.n_chunks > 1 && tun.finish == 3 && rkind_host != CLR_MARL && rkind_host != CLR_EV && !flex &&
-                           !(dims->flags & (CLD_KPI | CLD_F64_MAPS | CLD_WRITE_DETAIL)) && (!chain || !full) &&      // (the float64 chain: the battery + PV chunk kernel carries the fold; the thermal chain kernel does not)
-                           fold_per_row <= (full ? 64 : 16) && a.n_chunks * fold_w <= 1024 &&
-                           a.nw == 16 && a.n_chunks <= 64 &&
-                           2ll * a.n_chunks * NQ * dims->n_env + (dims->n_env + 63) / 64 + 4 <= (long long)dims->n_bldg * dims->n_env;
-    const dim3 grid(grid_x, a.n_chunks);
-    const bool det = dims->flags & CLD_WRITE_DETAIL;
-    // streaming KPIs of thermal / outage districts (and of any district stepped with detail planes) inside the step launch:
-    // cl_step_full_kpi_kernel (cl_full.h); cl_tuning.kpi_passes = 1 keeps the separate cl_kpi_kernel pass (A/B), 2 the two round-1 passes
-    // (up to 128 buildings: their baselines of one env tile sit in LDS, 256 B per building)
-    const bool kpi_full = (dims->flags & CLD_KPI) && full && !flex && !f64 && !chain && a.n_chunks == 1 && vec == 1 && tun.full_variant != 1 && tun.kpi_passes == 0 &&
-                          dims->n_bldg <= 128;
-    // ... whose waves should all be resident at once (16 per CU at its 119 registers): as many waves per workgroup as that allows, at least
-    // two (9 x 65 536: four waves 18.8 us, the step-only default of five -- two generations -- 23.6 us; profiles/r03_kpi_in_step_probe.log)
-    if (kpi_full && !tun.nw) {
-        const long long fit = (16ll * 256) / grid_x;
-        a.nw = (int)(fit < 2 ? 2 : fit > 16 ? 16 : fit);
-        if (a.nw > dims->n_bldg) a.nw = dims->n_bldg;
-    }
-    // thermal kernel with the parameter blocks of the workgroup's buildings staged in LDS
-    // (for the building-chunked launches only -- a workgroup of the 9 x 65 536 launch would wait for the staging round trip before it
-    //  can issue its plane loads, while its scalar reads hit the constant cache: 10.7 vs 8.7 us; full_variant = 2 forces it, 3 forbids it)
-    // (not under the float64 chain unless forced: its one-env-per-lane thermal kernel reads the blocks through the constant cache faster -- chunked 1024-,
-    //  512-, 256-building districts 1.06 - 1.21 x, profiles/r06c_cliffs_chain.jsonl -- and a 512-building chunk's 160 KB of staged blocks do not exist)
-    const bool lp = full && !flex && !det && !f64 && tun.full_variant != 1 && tun.full_variant != 3 && vec <= 2 &&
-                    ((a.n_chunks > 1 && !chain) || tun.full_variant == 2) && (size_t)a.b_chunk * CL_LP_WORDS * sizeof(uint32_t) <= 96 * 1024;
-    const size_t lds = (size_t)a.nw * NQ * tile * sizeof(float) + (lp ? (size_t)a.b_chunk * CL_LP_WORDS * sizeof(uint32_t) : 0) +
-                       (can_defer ? 1024 * sizeof(float) : 0);          // (+ the [chunks][16 / 32 / 64 sums] exchange tile of the deferred fold)
-    const dim3 block(64 * a.nw);
-    hipStream_t s = (hipStream_t)stream;
-    // Thermal districts whose batch can be cut into ONE 16-wave workgroup per CU: a workgroup takes `tiles` 128-env tiles (two envs per
-    // lane) and deals its tiles x B (tile, building) items to the 16 waves in order (cl_step_full_tp_kernel) -- the items divide over
-    // the four SIMDs where the B buildings of one tile do not, and the whole launch is resident at once.  scripts/tp_sweep.py,
-    // scripts/tp_sweep2.py (profiles/r02_tp_sweep*.log), one-tile kernel -> this one: 9 x 65 536 8.5 -> 7.7 us, 9 x 131 072 17.3 -> 14.3,
-    // 9 x 262 144 29.4 -> 28.0, 12 x 65 536 11.8 -> 9.2, 16 x 65 536 13.4 -> 11.7, 6 x 65 536 7.0 -> 6.6, 3 x 262 144 11.9 -> 10.7; with
-    // fewer than ~12 items per workgroup (3 x 65 536) or with more / fewer workgroups than CUs the one-tile kernel wins and stays.
-    // full_variant: 5 forces it (tun.vec = envs per lane, tun.nw = waves, tun.b_chunk = tiles), 3 forbids it.
-    const bool tp_forced = tun.full_variant == 5;
-    // small batches (193 .. 256 one-env-per-lane tiles, i.e. up to 16 384 envs): one tile per workgroup, one WAVE per building --
-    // 9 x 16 384 5.62 -> 5.01 us, 6 x 16 384 5.50 -> 4.41, 12 x 16 384 6.15 -> 5.25, 16 x 16 384 6.26 -> 5.84 (scripts/tp_small_probe.py)
-    const unsigned tiles1 = (unsigned)((dims->n_env + 63) / 64);
-    const bool tp_small = !tp_forced && tiles1 > 192 && tiles1 <= 256 && dims->n_bldg >= 6 && dims->n_bldg <= 16;
-    const int tp_vec = (tp_forced && tun.vec == 1) || tp_small || chain ? 1 : 2;       // (the float64 chain spills at two envs per lane)
-    const int tp_auto_tiles = tp_small ? 1 : (int)((dims->n_env + 256 * 64 * tp_vec - 1) / (256 * 64 * tp_vec));      // one workgroup per CU
-    // (chain, round 6: where one workgroup per CU would need more tiles than LDS holds -- 17 / 20 thermal buildings x 262 144 envs -- four tiles per
-    //  workgroup in several generations still beat the one-tile kernel 1.36 x / 1.16 x: profiles/r06c_cliffs_chain.jsonl)
-    const size_t tp_tile_bytes = ((size_t)dims->n_bldg * NQ + 1) * 64 * tp_vec * sizeof(float);
-    const bool tp_capped = chain && !tp_forced && !tp_small && (size_t)tp_auto_tiles * tp_tile_bytes > 150 * 1024 && 4 * tp_tile_bytes <= 150 * 1024 && dims->n_bldg >= 6;
-    const int tp_tiles = tp_forced ? (tun.b_chunk > 0 ? tun.b_chunk : CL_ROW0_BLOCK / (64 * tp_vec)) : tp_capped ? 4 : tp_auto_tiles;
-    const int tp_nw = tp_forced && tun.nw ? tun.nw : (tp_small ? dims->n_bldg : 16);
-    const unsigned tp_grid = (unsigned)((dims->n_env + tp_tiles * 64 * tp_vec - 1) / (tp_tiles * 64 * tp_vec));
-    const size_t tp_lds = ((size_t)tp_tiles * dims->n_bldg * NQ + tp_tiles) * 64 * tp_vec * sizeof(float);
-    bool tp_kernel = full && !flex && !(dims->flags & CLD_WRITE_DETAIL) && !kpi_full && a.n_chunks == 1 && dims->n_bldg <= 32 && tp_lds <= 150 * 1024 &&
-                     (!dims->env_row0 || CL_ROW0_BLOCK % (tp_tiles * 64 * tp_vec) == 0);    // one episode offset per workgroup: no workgroup straddles two blocks
-    if (tp_forced) {
-        if (!tp_kernel || tp_nw > 16)
-            return fail(CL_EINVAL, "full_variant = 5: %d tiles x %d envs per lane x %d waves is not a launch of cl_step_full_tp_kernel for this district", tp_tiles, tp_vec, tp_nw);
-    } else tp_kernel = tp_kernel && tun.full_variant == 0 && !tun.vec && !tun.nw && (tp_small || tp_tiles * dims->n_bldg >= 12) && ((tp_grid > 192 && tp_grid <= 256) || tp_capped);
-    // (up to 480 workgroups -- two 9-wave workgroups per CU are resident at once, so up to 512 the launch is still ONE generation: re-measured
-    //  at the end of round 5, after the latency-ordered kernel lost the non-temporal hint on its loads (scripts/gpurun/r05_call24.sh,
-    //  profiles/r05_nt_loads/r05y.log), 17 buildings x 98 304 / 106 496 / 114 688 / 131 072 / 163 840 / 196 608 / 262 144 envs: 10.6 / 11.0 /
-    //  11.8 / 15.5 / 19.2 / 22.6 / 31.7 us against 13.2 / 13.2 / 13.5 / 15.6 / 19.2 / 21.3 / 26.2 us for the env-major kernel -- the old rule
-    //  (352 workgroups, env-major from 106 496 envs) had the general kernel at 98 304 envs, 13.0 us)
-    // streaming KPIs without the detail planes: the lean kernel updates the per-building accumulators itself, at any grid size
-    const bool kpi_lean = (dims->flags & CLD_KPI) && !(dims->flags & CLD_WRITE_DETAIL) && !kpi_full;
-    // cl_step_observe_f32 on a thermal / outage district: the step launch fills the compact observation itself (cl_full.h OBS) where it is one
-    // workgroup row of the one-env-per-lane kernel or the multi-tile kernel, without detail planes / KPIs / a coupled reward
-    const bool obs_full = of_full && full && !flex && !det && !f64 && !(dims->flags & CLD_KPI) && a.n_chunks == 1 && rkind_host != CLR_MARL && tuning_of(dims).obs_variant == 0;
-    // Env-major or building-major above one wave generation?  Re-measured in round 6, both kernels alternating in ONE process (scripts/r06_lean_vs_envmajor.py,
-    // profiles/r06_lean_vs_envmajor*.log; a process lands in a +- 4 % band, which is what hid this in round 5):
-    //  * the env-major kernel wins where the step's footprint is of the order of the Infinity Cache -- 17 x 262 144: 25.8 / 30.7 us (fp32 / chain) against 27.9 /
-    //    32.2 for the latency-ordered building-major kernel at four envs per lane; 9 x 262 144: 16.1 / 18.8 against 19.2 / 21.4;
-    //  * far beyond the cache the building-major kernel's 16-byte accesses win again: 17 x 1 048 576 -- the HBM-true shape of the bench line -- 104.6 - 111.8 us
-    //    against 113.5 - 127.6 us (fp32) and 113.5 - 120.4 against 125.6 - 134.4 (chain) in three processes, 17 x 2 097 152 222 - 224 / 236 against 225 - 247 /
-    //    245 - 261, 20 x 1 048 576 (fp32) 126 - 129 against 133 - 140;
-    //  * under the float64 chain the building-major kernel holds on longer below: 17 x 147 456 / 163 840 / 180 224 20.5 / 21.8 / 22.8 us against 23.4 / 24.2 /
-    //    25.2 (196 608: 24.4 - 25.6 against 25.8 - 26.5; 229 376: even); 9 and 6 buildings: 131 072 envs 10.1 / 7.6 against 11.1 / 8.6, even or behind from 147 456.
-    //  * (scripts/r06_stream_map.py, 6 .. 20 buildings x 393 216 .. 2 097 152 envs, five variants side by side, medians of three rounds; profiles/r06_stream_map*.jsonl)
-    //    from 12 buildings and 8 Mi units the building-major kernel WITH non-temporal stores is the best or within 3 % of it in 25 of 30 cells -- 12 x 786 432 /
-    //    1 048 576: 57.0 / 75.0 us against 62.8 / 84.3 (fp32), 57.0 / 75.0 against 68.9 / 94.0 (chain); 20 x 524 288 / 786 432 (fp32): 61.2 / 93.2 against 72.8 / 106.9;
-    //    6 and 9 buildings are mixed and keep the env-major kernel.
-    const bool stream_lean = dims->n_bldg >= 12 && (long long)dims->n_bldg * dims->n_env >= (8ll << 20);
-    const int em_min = !chain ? 122880 : dims->n_bldg >= 16 ? 196608 : 131072;
-    const bool em_auto = dims->n_env > em_min && !(chain && dims->n_bldg > 17) && !stream_lean;
-    const bool lean_beyond = tun.envmajor == 0 && !full && dims->n_bldg <= 20 && dims->n_env > 122880 && !em_auto;      // (what the env-major rule no longer takes)
-    const bool lean_shape = a.n_chunks == 1 && dims->n_bldg <= 2 * a.nw && (grid_x <= 480 || (tun.lean_variant & 2) || kpi_lean || lean_beyond) &&
-                            !((tun.lean_variant & 1) && !kpi_lean);
-    if (lean_beyond && stream_lean && lean_shape && tun.nt_stores == 0) a.nt = 1;      // (8 .. 16 Mi units: the footprint rule above says plain stores -- measured on the env-major kernel)
-    // without the detail planes only cl_step_lean_kpi_kernel updates the per-building accumulators (and writes the baseline plane
-    // cl_kpi_env_kernel sums): a launch shape that cannot take it must not silently leave them stale
-    if (kpi_lean && (full || flex || !lean_shape))
-        return fail(CL_EINVAL, "CLD_KPI without CLD_WRITE_DETAIL needs a step launch that updates the accumulators itself (battery + PV: n_bldg=%d <= 2 x nw=%d "
-                               "waves, no chunks; thermal: one env per lane, no chunks, no flexible loads, no CLD_F64_MAPS): drop the cl_tuning override or set CLD_WRITE_DETAIL",
-                    dims->n_bldg, a.nw);
-    // (chain: the 20-building instantiation holds 140 registers -- three waves per SIMD -- and loses to the building-major kernel, 41.6 vs 33.6 us at
-    //  20 x 262 144: only districts of up to 17 buildings go env-major by themselves; profiles/r06c_cliffs_chain.jsonl)
-    const bool envmajor_shape = !full && a.n_chunks == 1 && dims->n_bldg <= 20 && !kpi_lean &&
-                                (tun.envmajor == 1 || (tun.envmajor == 0 && em_auto));
-    if (dims->flags & CLD_CHECK) {
-        // debug mode: the general kernel with the reference's assertions compiled in, one env per lane (include/citylearn_amd.h CLD_CHECK)
-        if (!det || (dims->flags & CLD_DETAIL_MIN) || a.n_chunks > 1 || kpi_full)
-            return fail(CL_EINVAL, "CLD_CHECK needs CLD_WRITE_DETAIL (all planes), a district of up to 32 buildings (the violation words use the reserved plane) "
-                                   "and, with CLD_KPI, the separate KPI launch (cl_tuning.kpi_passes = 1)");
-        const dim3 grid1((unsigned)((dims->n_env + 63) / 64));
-        const size_t lds1 = (size_t)a.nw * NQ * 64 * sizeof(float);
-        name_add(tun, "cl_step_kernel<1, true, true, %s, %d, false, true>", flex ? "true" : "false", chain ? 2 : f64 ? 1 : 0);
-        if (flex) hipLaunchKernelGGL((cl_step_kernel<1, true, true, true, 0, false, true>), grid1, block, lds1, s, a);
-        else if (chain) hipLaunchKernelGGL((cl_step_kernel<1, true, true, false, 2, false, true>), grid1, block, lds1, s, a);
-        else if (f64) hipLaunchKernelGGL((cl_step_kernel<1, true, true, false, 1, false, true>), grid1, block, lds1, s, a);
-        else hipLaunchKernelGGL((cl_step_kernel<1, true, true, false, 0, false, true>), grid1, block, lds1, s, a);
-    } else if (chain) {
-        if (envmajor_shape) {
-            const dim3 egrid((unsigned)((dims->n_env + 255) / 256));
-            const int enb = dims->n_bldg <= 17 ? 17 : 20;
-            name_add(tun, "cl_step_envmajor_kernel<%d, %s, 1, 2>", enb, a.nt ? "true" : "false");
-            if (enb == 17) { if (a.nt) hipLaunchKernelGGL((cl_step_envmajor_kernel<17, true, 1, 2>), egrid, dim3(256), 0, s, a);
-                             else hipLaunchKernelGGL((cl_step_envmajor_kernel<17, false, 1, 2>), egrid, dim3(256), 0, s, a); }
-            else { if (a.nt) hipLaunchKernelGGL((cl_step_envmajor_kernel<20, true, 1, 2>), egrid, dim3(256), 0, s, a);
-                   else hipLaunchKernelGGL((cl_step_envmajor_kernel<20, false, 1, 2>), egrid, dim3(256), 0, s, a); }
-        } else if (!full && lean_shape) {
-            const bool obs_fused = of && rkind_host != CLR_MARL && !kpi_lean;      // (MARL's reward plane is finished after the sweep the tile is filled in)
-            const size_t lds_x = lds + (kpi_lean ? CL_OBS_FUSED_BLDG * sizeof(float) : obs_fused ? (size_t)tile * of->pitch * sizeof(float) : 0);
-#define CL_CHAIN_CASE(V) case V: \
-            name_add(tun, "%s<" #V ", %s>", kpi_lean ? "cl_step_lean_kpi_chain_kernel" : obs_fused ? "cl_step_lean_obs_chain_kernel" : "cl_step_lean_chain_kernel", a.nt ? "true" : "false"); \
-            if (kpi_lean) { \
-                if (a.nt) hipLaunchKernelGGL((cl_step_lean_kpi_chain_kernel<V, true>), grid, block, lds_x, s, a); \
-                else hipLaunchKernelGGL((cl_step_lean_kpi_chain_kernel<V, false>), grid, block, lds_x, s, a); \
-            } else if (obs_fused) { \
-                if (a.nt) hipLaunchKernelGGL((cl_step_lean_obs_chain_kernel<V, true>), grid, block, lds_x, s, a, *of); \
-                else hipLaunchKernelGGL((cl_step_lean_obs_chain_kernel<V, false>), grid, block, lds_x, s, a, *of); \
-                *fused = true; \
-            } else if (a.nt) hipLaunchKernelGGL((cl_step_lean_chain_kernel<V, true>), grid, block, lds, s, a); \
-            else hipLaunchKernelGGL((cl_step_lean_chain_kernel<V, false>), grid, block, lds, s, a); \
-            break;
-            switch (vec) {
-            CL_CHAIN_CASE(1) CL_CHAIN_CASE(2) CL_CHAIN_CASE(4)
-            default: return fail(CL_EINVAL, "bad vec %d", vec);
-            }
-#undef CL_CHAIN_CASE
-        } else if (!full && a.n_chunks > 1 && tun.finish != 2 && (vec == 1 || vec == 2 || vec == 4) && !(tun.lean_variant & 16)) {
-            // building-chunked battery + PV districts: the latency-ordered chunk kernel around the float64 chain (deferred fold where it applies)
-            a.fused_finish = can_defer ? 2 : 0;
-            name_add(tun, "cl_step_lean_chunk_kernel<%d, %s, %s, 2>", vec, a.nt ? "true" : "false", can_defer ? "true" : "false");
-            if (int rc = launch_lean_chunk<2>(vec, a.nt, can_defer, grid, block, lds, s, a)) return rc;
-        } else if (tp_kernel) {
-            // thermal districts, several env tiles per workgroup (cl_step_full_tp_kernel's launch shape)
-            a.nw = tp_nw;
-            const dim3 g2(tp_grid), b2(64 * a.nw);
-            if (obs_full && tp_lds + (size_t)tp_tiles * 64 * of_full->pitch * sizeof(float) <= 150 * 1024) {      // (a tile that does not fit: the two launches)
-                const size_t l2 = tp_lds + (size_t)tp_tiles * 64 * of_full->pitch * sizeof(float);
-                if (int rc = launch_tp_obs<1, 2>(a.nt, g2, b2, l2, s, a, tp_tiles, *of_full, tun)) return rc;
-                *fused = true;
-            } else {
-            name_add(tun, "cl_step_full_tp_chain_kernel<1, 4, %s>", a.nt ? "true" : "false");
-            if (a.nt) hipLaunchKernelGGL((cl_step_full_tp_chain_kernel<1, 4, true>), g2, b2, tp_lds, s, a, tp_tiles);
-            else hipLaunchKernelGGL((cl_step_full_tp_chain_kernel<1, 4, false>), g2, b2, tp_lds, s, a, tp_tiles);
-            }
-        } else if (full && tun.full_variant != 1) {
-            // thermal / outage districts: the pack-generic kernel of cl_full.h at one env per lane (parameter blocks staged in LDS where chunked)
-            if (det) CL_LAUNCH_NT(cl_step_full_chain_kernel, 1, true, 1024, 4, false);
-            else if (obs_full && !lp) {
-                if (int rc = launch_full_obs<2>(a.nt, grid, block, lds + (size_t)64 * of_full->pitch * sizeof(float), s, a, *of_full, tun)) return rc;
-                *fused = true;
-            } else if (lp) { const dim3 grid_xy = grid; { const dim3 grid = CL_SWAP_GRID ? dim3(grid_xy.y, grid_xy.x) : grid_xy; CL_LAUNCH_NT(cl_step_full_chain_kernel, 1, false, 1024, 4, true); } }
-            else CL_LAUNCH_NT(cl_step_full_chain_kernel, 1, false, 1024, 4, false);
-        } else {
-            name_add(tun, "cl_step_kernel<%d, %s, %s, false, 2, false>", vec, full ? "true" : "false", full && det ? "true" : "false");
-            if (full && det) hipLaunchKernelGGL((cl_step_kernel<1, true, true, false, 2>), grid, block, lds, s, a);
-            else if (full) hipLaunchKernelGGL((cl_step_kernel<1, true, false, false, 2>), grid, block, lds, s, a);
-            else if (vec == 1) hipLaunchKernelGGL((cl_step_kernel<1, false, false, false, 2>), grid, block, lds, s, a);
-            else if (vec == 2) hipLaunchKernelGGL((cl_step_kernel<2, false, false, false, 2>), grid, block, lds, s, a);
-            else hipLaunchKernelGGL((cl_step_kernel<4, false, false, false, 2>), grid, block, lds, s, a);
-        }
-    } else if (f64) {
-        if (!full && lean_shape) {
-            if (vec == 1) CL_LAUNCH_NT(cl_step_lean_f64_kernel, 1); else CL_LAUNCH_NT(cl_step_lean_f64_kernel, 2);
-        } else {
-            name_add(tun, "cl_step_kernel<%d, %s, %s, false, 1, false>", vec, full ? "true" : "false", full && det ? "true" : "false");
-            if (full && det) hipLaunchKernelGGL((cl_step_kernel<1, true, true, false, 1>), grid, block, lds, s, a);
-            else if (full) hipLaunchKernelGGL((cl_step_kernel<1, true, false, false, 1>), grid, block, lds, s, a);
-            else if (vec == 1) hipLaunchKernelGGL((cl_step_kernel<1, false, false, false, 1>), grid, block, lds, s, a);
-            else hipLaunchKernelGGL((cl_step_kernel<2, false, false, false, 1>), grid, block, lds, s, a);
-        }
-    } else if (flex && !full && lean_shape) {
-        switch (vec) {
-        case 1: CL_LAUNCH_NT(cl_step_lean_kernel, 1, true); break;
-        case 2: CL_LAUNCH_NT(cl_step_lean_kernel, 2, true); break;
-        case 4: CL_LAUNCH_NT(cl_step_lean_kernel, 4, true); break;
-        default: return fail(CL_EINVAL, "bad vec %d", vec);
-        }
-    } else if (flex) {
-        // districts with chargers / washing machines: the FLEX instantiations of the general kernel
-        if (vec > 2) return fail(CL_EINVAL, "bad vec %d for the flexible-load step", vec);
-        const dim3& grid_f = grid;
-        const size_t lds_f = lds;
-        name_add(tun, "cl_step_kernel<%d, %s, %s, true, 0, false>", vec, full ? "true" : "false", full && det ? "true" : "false");
-        if (full && det) {
-            if (vec == 1) hipLaunchKernelGGL((cl_step_kernel<1, true, true, true>), grid_f, block, lds_f, s, a);
-            else hipLaunchKernelGGL((cl_step_kernel<2, true, true, true>), grid_f, block, lds_f, s, a);
-        } else if (full) {
-            if (vec == 1) hipLaunchKernelGGL((cl_step_kernel<1, true, false, true>), grid_f, block, lds_f, s, a);
-            else hipLaunchKernelGGL((cl_step_kernel<2, true, false, true>), grid_f, block, lds_f, s, a);
-        } else {
-            if (vec == 1) hipLaunchKernelGGL((cl_step_kernel<1, false, false, true>), grid_f, block, lds_f, s, a);
-            else hipLaunchKernelGGL((cl_step_kernel<2, false, false, true>), grid_f, block, lds_f, s, a);
-        }
-    } else if (tp_kernel) {
-        // several env tiles per workgroup (cl_step_full_tp_kernel, cl_full.h); forced: tun.vec = envs per lane, tun.nw = waves, tun.b_chunk = tiles
-        a.nw = tp_nw;
-        const dim3 g2(tp_grid), b2(64 * a.nw);
-        const size_t l2 = tp_lds;
-        if (obs_full && l2 + (size_t)tp_tiles * 64 * tp_vec * of_full->pitch * sizeof(float) <= 150 * 1024) {
-            const size_t lo = l2 + (size_t)tp_tiles * 64 * tp_vec * of_full->pitch * sizeof(float);
-            if (int rc = tp_vec == 2 ? launch_tp_obs<2, 0>(a.nt, g2, b2, lo, s, a, tp_tiles, *of_full, tun) : launch_tp_obs<1, 0>(a.nt, g2, b2, lo, s, a, tp_tiles, *of_full, tun)) return rc;
-            *fused = true;
-        } else {
-        name_add(tun, "cl_step_full_tp_kernel<%d, 4, %s>", tp_vec, a.nt ? "true" : "false");
-        if (tp_vec == 2) {
-            if (a.nt) hipLaunchKernelGGL((cl_step_full_tp_kernel<2, 4, true>), g2, b2, l2, s, a, tp_tiles);
-            else hipLaunchKernelGGL((cl_step_full_tp_kernel<2, 4, false>), g2, b2, l2, s, a, tp_tiles);
-        } else {
-            if (a.nt) hipLaunchKernelGGL((cl_step_full_tp_kernel<1, 4, true>), g2, b2, l2, s, a, tp_tiles);
-            else hipLaunchKernelGGL((cl_step_full_tp_kernel<1, 4, false>), g2, b2, l2, s, a, tp_tiles);
-        }
-        }
-    } else if (full && tun.full_variant != 1 && vec <= 2) {
-        // thermal / outage districts: the pack-generic kernel of cl_full.h
-        const bool small = block.x <= 576;
-        if (kpi_full) {
-            const size_t lds_k = lds + (size_t)dims->n_bldg * tile * sizeof(float);      // + the per-building baselines of the tile
-            name_add(tun, "cl_step_full_kpi_kernel<%s>", a.nt ? "true" : "false");
-            if (a.nt) hipLaunchKernelGGL((cl_step_full_kpi_kernel<true>), grid, block, lds_k, s, a);
-            else hipLaunchKernelGGL((cl_step_full_kpi_kernel<false>), grid, block, lds_k, s, a);
-        } else if (det) {
-            if (vec == 1) CL_LAUNCH_NT(cl_step_full_kernel, 1, true, 1024, 4, false);
-            else if (small) CL_LAUNCH_NT(cl_step_full_kernel, 2, true, 576, 3, false);
-            else CL_LAUNCH_NT(cl_step_full_kernel, 2, true, 1024, 4, false);
-        } else if (lp) {
-            // parameter blocks staged in LDS (cl_full.h); full_variant = 3 keeps them in SGPRs (tests, A/B)
-            a.fused_finish = (a.n_chunks > 1 && vec == 2 && !small) ? (tun.finish == 2 ? 1 : can_defer ? 2 : 0) : 0;
-            const dim3 grid_xy = grid;
-            {
-                const dim3 grid = CL_SWAP_GRID ? dim3(grid_xy.y, grid_xy.x) : grid_xy;       // the LP instantiations read (building chunk, env tile) from blockIdx: district_reduce's SWAP note
-                if (vec != 1 && !small && lds > 64 * 1024) {
-                    // (chunks of 128 buildings: 40 KB of staged blocks + 32 KB of reduction rows + the exchange tile -- more dynamic LDS than a
-                    //  kernel gets without opting in where the runtime enforces the 64 KB default)
-                    const void* fn = a.nt ? reinterpret_cast<const void*>(cl_step_full_kernel<2, false, 1024, 4, true, true>)
-                                          : reinterpret_cast<const void*>(cl_step_full_kernel<2, false, 1024, 4, true, false>);
-                    if (hipError_t e = ensure_dynamic_lds(fn, lds); e != hipSuccess)
-                        return hip_fail(e, "hipFuncSetAttribute(cl_step_full_kernel<2, .., LP>)");
-                }
-                if (vec == 1) CL_LAUNCH_NT(cl_step_full_kernel, 1, false, 1024, 5, true);
-                else if (!small) CL_LAUNCH_NT(cl_step_full_kernel, 2, false, 1024, 4, true);
-            }
-            if (vec != 1 && small) CL_LAUNCH_NT(cl_step_full_kernel, 2, false, 576, 5, false);      // (96 VGPRs do not hold the staged operands: 61 scratch accesses)
-        } else {
-            if (vec == 1 && obs_full) {
-                if (int rc = launch_full_obs<0>(a.nt, grid, block, lds + (size_t)64 * of_full->pitch * sizeof(float), s, a, *of_full, tun)) return rc;
-                *fused = true;
-            } else
-#ifdef CL_TRACE                  // the stamps need a few registers: five waves per SIMD (what the 9-building launch holds) instead of six
-            if (vec == 1) CL_LAUNCH_NT(cl_step_full_kernel, 1, false, 1024, 5, false);
-#else
-            if (vec == 1) CL_LAUNCH_NT(cl_step_full_kernel, 1, false, 1024, 6, false);
-#endif
-            else if (small) CL_LAUNCH_NT(cl_step_full_kernel, 2, false, 576, 5, false);
-            else CL_LAUNCH_NT(cl_step_full_kernel, 2, false, 1024, 5, false);
-        }
-    } else if (full && det) {
-        name_add(tun, "cl_step_kernel<%d, true, true, false, 0, false>", vec);
-        switch (vec) {
-        case 1: hipLaunchKernelGGL((cl_step_kernel<1, true, true>), grid, block, lds, s, a); break;
-        case 2: hipLaunchKernelGGL((cl_step_kernel<2, true, true>), grid, block, lds, s, a); break;
-        default: return fail(CL_EINVAL, "bad vec %d", vec);
-        }
-    } else if (full) {
-        name_add(tun, "cl_step_kernel<%d, true, false, false, 0, false>", vec);
-        switch (vec) {
-        case 1: hipLaunchKernelGGL((cl_step_kernel<1, true, false>), grid, block, lds, s, a); break;
-        case 2: hipLaunchKernelGGL((cl_step_kernel<2, true, false>), grid, block, lds, s, a); break;
-        // (four envs per lane is not instantiated for the thermal unit: 92 bytes of scratch per lane, never selected by the library)
-        default: return fail(CL_EINVAL, "bad vec %d", vec);
-        }
-    } else if (envmajor_shape) {
-        // two or more waves per SIMD: the env-major kernel (bench.py --envs-per-gpu: 17 x 131 072 17.0 vs 18.5 us,
-        // 17 x 262 144 28.2 vs 32.5 us, 17 x 1 048 576 136 vs 157 us; at 17 x 65 536 -- one wave per SIMD, nothing to hide the
-        // per-building dependency chain behind -- 13.1 vs 8.0 us)
-        const dim3 egrid((unsigned)((dims->n_env + 255) / 256));
-        // envs per lane (cl_tuning.vec: 1 or 2) and the compile-time bound on the buildings held in flight (17 = the 2022 challenge's
-        // district: three fewer register quadruples than the general 20)
-        const int evec = tun.vec == 2 && act_stride_env == 1 ? 2 : 1;
-        const int enb = dims->n_bldg <= 17 && tun.lean_variant != 8 ? 17 : 20;
-        name_add(tun, "cl_step_envmajor_kernel<%d, %s, %d, 0>", enb, a.nt ? "true" : "false", evec);
-#define CL_EM(NB_, V_) do { if (a.nt) hipLaunchKernelGGL((cl_step_envmajor_kernel<NB_, true, V_>), egrid, dim3(256 / V_), 0, s, a); \
-                            else hipLaunchKernelGGL((cl_step_envmajor_kernel<NB_, false, V_>), egrid, dim3(256 / V_), 0, s, a); } while (0)
-        if (enb == 17) { if (evec == 2) CL_EM(17, 2); else CL_EM(17, 1); }
-        else { if (evec == 2) CL_EM(20, 2); else CL_EM(20, 1); }
-#undef CL_EM
-    } else if (lean_shape) {
-        // one workgroup per CU at most: with more rounds the generic kernel's smaller register file (52 vs 88 VGPRs, two
-        // workgroups per CU) wins again -- 17 x 262 144: 30.8 us vs 33.0 us
-        switch (vec) {                                   // latency-ordered lean kernel (two buildings per wave at most)
-#define CL_LEAN_CASE(V) case V: \
-            name_add(tun, "%s<" #V ", %s%s>", kpi_lean ? "cl_step_lean_kpi_kernel" : (of && rkind_host != CLR_MARL) ? "cl_step_lean_obs_kernel" : "cl_step_lean_kernel", \
-                     kpi_lean || (of && rkind_host != CLR_MARL) ? "" : "false, ", a.nt ? "true" : "false"); \
-            if (kpi_lean) { \
-                const size_t lds_k = lds + CL_OBS_FUSED_BLDG * sizeof(float);      /* + one baseline value per building */ \
-                if (a.nt) hipLaunchKernelGGL((cl_step_lean_kpi_kernel<V, true>), grid, block, lds_k, s, a); \
-                else hipLaunchKernelGGL((cl_step_lean_kpi_kernel<V, false>), grid, block, lds_k, s, a); \
-            } else if (of && rkind_host != CLR_MARL) {       /* (MARL's reward plane is finished after the sweep the tile is filled in) */ \
-                const size_t lds_o = lds + (size_t)tile * of->pitch * sizeof(float); \
-                if (a.nt) hipLaunchKernelGGL((cl_step_lean_obs_kernel<V, true>), grid, block, lds_o, s, a, *of); \
-                else hipLaunchKernelGGL((cl_step_lean_obs_kernel<V, false>), grid, block, lds_o, s, a, *of); \
-                *fused = true; \
-            } else if (const int rc = cl_tu_launch_lean(V, a.nt, grid.x, grid.y, block.x, lds, stream, &a)) \
-                return hip_fail((hipError_t)rc, "cl_step_lean_kernel launch"); \
-            break;
-        CL_LEAN_CASE(1) CL_LEAN_CASE(2) CL_LEAN_CASE(4)
-#undef CL_LEAN_CASE
-        default: return fail(CL_EINVAL, "bad vec %d", vec);
-        }
-    } else if (a.n_chunks > 1 && tun.finish != 2 && (vec == 1 || vec == 2 || vec == 4) && !(tun.lean_variant & 16)) {
-        // building-chunked battery + PV districts: the latency-ordered chunk kernel (lean_variant & 16 keeps cl_step_kernel: tests, A/B)
-        a.fused_finish = can_defer ? 2 : 0;
-        name_add(tun, "cl_step_lean_chunk_kernel<%d, %s, %s, 0>", vec, a.nt ? "true" : "false", can_defer ? "true" : "false");
-        if (int rc = launch_lean_chunk<0>(vec, a.nt, can_defer, grid, block, lds, s, a)) return rc;
-    } else if (a.n_chunks > 1 && (tun.finish == 2 || can_defer) && (vec == 1 || vec == 4)) {
-        // building-chunked battery + PV districts (C4 with the 2022 device set): the instantiations that fold the chunk sums themselves
-        // (finish = 2: their own, inside the launch; finish = 3: the previous step's, deferred)
-        a.fused_finish = tun.finish == 2 ? 1 : 2;
-        name_add(tun, "cl_step_kernel<%d, false, false, false, 0, true>", vec);
-        // (four envs per lane x 16 waves: 64 KB of reduction rows + the 4 KB exchange tile of the deferred fold -- more dynamic LDS than a
-        //  kernel gets without opting in where the runtime enforces the 64 KB default; gfx950's 160 KB hold it)
-        if (lds > 64 * 1024) {
-            const void* fn = vec == 1 ? reinterpret_cast<const void*>(cl_step_kernel<1, false, false, false, 0, true>)
-                                      : reinterpret_cast<const void*>(cl_step_kernel<4, false, false, false, 0, true>);
-            if (hipError_t e = ensure_dynamic_lds(fn, lds); e != hipSuccess)
-                return hip_fail(e, "hipFuncSetAttribute(cl_step_kernel<.., FOLD>)");
-        }
-        const dim3 grid_sw = CL_SWAP_GRID ? dim3(grid.y, grid.x) : grid;      // (chunks along x: district_reduce's SWAP note)
-        if (vec == 1) hipLaunchKernelGGL((cl_step_kernel<1, false, false, false, 0, true>), grid_sw, block, lds, s, a);
-        else hipLaunchKernelGGL((cl_step_kernel<4, false, false, false, 0, true>), grid_sw, block, lds, s, a);
+    if (p.kernel == CLK_LEAN && p.form == CLF_PLAIN && p.prec == 0 && !p.flex) {
+        if (const int rc = cl_tu_launch_lean(p.vec, p.nt, p.grid_x, p.grid_y, p.block, p.lds, stream, &a))
+            return hip_fail((hipError_t)rc, "cl_step_lean_kernel launch");
     } else {
-        name_add(tun, "cl_step_kernel<%d, false, false, false, 0, false>", vec);
-        switch (vec) {
-        case 1: hipLaunchKernelGGL((cl_step_kernel<1, false, false>), grid, block, lds, s, a); break;
-        case 2: hipLaunchKernelGGL((cl_step_kernel<2, false, false>), grid, block, lds, s, a); break;
-        case 4: hipLaunchKernelGGL((cl_step_kernel<4, false, false>), grid, block, lds, s, a); break;
-        default: return fail(CL_EINVAL, "bad vec %d", vec);
-        }
+        const void* fn = step_kernel_fn(p);
+        if (p.lds > 64 * 1024)
+            if (hipError_t e = ensure_dynamic_lds(fn, p.lds); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(step kernel)");
+        // kernel arguments: (a), (a, of), (a, tp) or (a, tp, of)
+        int tp = p.tp_tiles;
+        ObsFusedArgs* obs = const_cast<ObsFusedArgs*>(of);
+        void* args[3] = {&a, p.kernel == CLK_FULL_TP ? (void*)&tp : (void*)obs, obs};
+        (void)hipLaunchKernel(fn, dim3(p.grid_x, p.grid_y), dim3(p.block), args, p.lds, s);
+        if (p.form == CLF_OBS) *fused = true;
     }
-    if (a.n_chunks > 1) {
-        if (!a.fused_finish) {
-            name_add(tun, "cl_finish_kernel");
-            hipLaunchKernelGGL(cl_finish_kernel, dim3((dims->n_env + 63) / 64, NQ), dim3(1024), 0, s, a, 0, (float*)nullptr);
-        }
-        if (((dims->flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT) == CLR_MARL) {
-            const long long n = (long long)dims->n_env * dims->n_bldg;
-            name_add(tun, "cl_marl_reward_kernel");
-            hipLaunchKernelGGL(cl_marl_reward_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
-        }
-    }
-    if (dims->flags & CLD_KPI) {
-        const long long n = (long long)dims->n_env * dims->n_bldg;
-        // (without the detail planes -- lean districts -- the step launch above has updated every accumulator itself)
-        if (kpi_full) {
-            // (cl_step_full_kpi_kernel has updated every accumulator)
-        } else if ((dims->flags & CLD_WRITE_DETAIL) && tun.kpi_passes == 2) {            // the round-1 / round-2 form: two passes (tests, A/B)
-            name_add(tun, "cl_kpi_bldg_kernel+cl_kpi_env_kernel");
-            hipLaunchKernelGGL(cl_kpi_bldg_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
-            hipLaunchKernelGGL(cl_kpi_env_kernel, dim3((dims->n_env + 63) / 64), dim3(1024), 0, s, a);
-        } else if (dims->flags & CLD_WRITE_DETAIL) {
-            name_add(tun, "cl_kpi_kernel");
-            hipLaunchKernelGGL(cl_kpi_kernel, dim3((dims->n_env + 63) / 64), dim3(1024), 0, s, a);
-        }
+    if (p.finish) hipLaunchKernelGGL(cl_finish_kernel, dim3((dims->n_env + 63) / 64, NQ), dim3(1024), 0, s, a, 0, (float*)nullptr);
+    const long long n = (long long)dims->n_env * dims->n_bldg;
+    if (p.marl) hipLaunchKernelGGL(cl_marl_reward_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+    if (p.kpi_passes == 2) {            // the round-1 / round-2 form: two passes (tests, A/B)
+        hipLaunchKernelGGL(cl_kpi_bldg_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(cl_kpi_env_kernel, dim3((dims->n_env + 63) / 64), dim3(1024), 0, s, a);
+    } else if (p.kpi_passes == 1) {
+        hipLaunchKernelGGL(cl_kpi_kernel, dim3((dims->n_env + 63) / 64), dim3(1024), 0, s, a);
     }
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "cl_step_kernel launch");
     return CL_OK;

@@ -46,6 +46,8 @@ def _parse(text: str) -> dict:
 _C = _parse(HEADER.read_text())
 globals().update(_C)
 CONSTANTS = dict(_C)
+# (CL_ABI_VERSION comes from the header like everything else: 9 since CLD_ROLLOUT_FUSED -- `cl_rollout_seq_f32` as one fused launch that keeps
+#  the streaming KPI accumulators; `_lib.load()` refuses a library built from another version)
 
 # every function the header declares (used by the "library exports every symbol" test)
 EXPORTED_SYMBOLS = sorted(set(re.findall(r'\b(cl_\w+)\s*\(', _strip_comments(HEADER.read_text()))))

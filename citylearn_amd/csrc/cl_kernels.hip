@@ -1546,6 +1546,15 @@ extern "C" __attribute__((visibility("hidden"))) int cl_tu_launch_rollout(int ke
     case 1012: hipLaunchKernelGGL((cl_rollout_kernel<1, false, 2, true, true>), grid, block, lds, s, r); break;
     case 1022: hipLaunchKernelGGL((cl_rollout_kernel<2, false, 2, true, true>), grid, block, lds, s, r); break;
     case 1111: hipLaunchKernelGGL((cl_rollout_kernel<1, true, 1, true, true>), grid, block, lds, s, r); break;
+    // with the streaming KPI accumulators (cl_rollout_kpi_kernel; 4000 + 10 * envs per lane + 2, + 2000 under CLD_F64_CHAIN)
+#define CL_TU_RKPI(V, P) do { \
+        if (lds > 64 * 1024) if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(cl_rollout_kpi_kernel<V, P>), lds); e != hipSuccess) return (int)e; \
+        hipLaunchKernelGGL((cl_rollout_kpi_kernel<V, P>), grid, block, lds, s, r); } while (0)
+    case 4012: CL_TU_RKPI(1, 0); break;
+    case 4022: CL_TU_RKPI(2, 0); break;
+    case 6012: CL_TU_RKPI(1, 2); break;
+    case 6022: CL_TU_RKPI(2, 2); break;
+#undef CL_TU_RKPI
     default: return -1;
     }
     return (int)hipGetLastError();
@@ -1942,11 +1951,80 @@ int cl_step_observe_f32(const cl_dims* dims, const uint32_t* params, const float
                           n_rows, obs_row, 0u, stream);
 }
 
+// cl_rollout_seq_f32 under CLD_ROLLOUT_FUSED: the K steps in ONE fused launch or CL_EINVAL -- never the launch sequence.  (`dims` checked by the caller.)
+static int rollout_fused(const cl_dims* dims, const uint32_t* params, const float* ts, float* state, const float* actions,
+                         int64_t act_stride_step, int64_t act_stride_col, int64_t act_stride_env, const float* act_low,
+                         const float* act_high, uint64_t seed, float* out_bldg, float* out_env,
+                         float* ret_env, float* kpi_bldg, float* kpi_env, const cl_flex* flex, int32_t t0, int32_t k_steps, void* stream) {
+    if (flex) return fail(CL_EINVAL, "CLD_ROLLOUT_FUSED: flex != NULL -- the fused rollout kernels carry no flexible-load state (drop the flag for the launch sequence)");
+    if (dims->flags & CLD_F64_MAPS)
+        return fail(CL_EINVAL, "CLD_ROLLOUT_FUSED: the fused rollout kernels evaluate the battery map in fp32 or as the float64 chain (CLD_F64_CHAIN), not CLD_F64_MAPS");
+    if (!(dims->flags & CLD_KPI))
+        return cl_rollout_f32(dims, params, ts, state, actions, act_stride_step, act_stride_col, act_stride_env, act_low, act_high, seed, out_bldg,
+                              out_env, ret_env, t0, k_steps, stream);
+    if (!(dims->flags & CLD_LEAN))
+        return fail(CL_EINVAL, "CLD_ROLLOUT_FUSED with CLD_KPI: only battery + PV districts (CLD_LEAN); a thermal / outage district keeps the launch sequence");
+    if (dims->flags & CLD_WRITE_DETAIL) return fail(CL_EINVAL, "CLD_ROLLOUT_FUSED with CLD_KPI: not with the detail planes (CLD_WRITE_DETAIL)");
+    if (dims->n_bldg > CL_RKPI_NB)
+        return fail(CL_EINVAL, "CLD_ROLLOUT_FUSED with CLD_KPI: n_bldg=%d > %d would be a building-chunked launch, which the fused KPI kernel is not", dims->n_bldg, CL_RKPI_NB);
+    if (pitch_of(dims) != dims->n_env)
+        return fail(CL_EINVAL, "CLD_ROLLOUT_FUSED with CLD_KPI: env_pitch=%d != n_env=%d -- the streaming KPI planes are not pitched", dims->env_pitch, dims->n_env);
+    if (((dims->flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT) == CLR_EV)
+        return fail(CL_EINVAL, "CLD_ROLLOUT_FUSED: reward kind CLR_EV needs the flexible-load tables");
+    const cl_tuning& tun = tuning_of(dims);
+    if (int rc = check_ptr(params, "params")) return rc;
+    if (int rc = check_ptr(ts, "ts")) return rc;
+    if (int rc = check_ptr(state, "state")) return rc;
+    if (int rc = check_ptr(out_bldg, "out_bldg")) return rc;
+    if (int rc = check_ptr(out_env, "out_env")) return rc;
+    if (int rc = check_ptr(kpi_bldg, "kpi_bldg")) return rc;
+    if (int rc = check_ptr(kpi_env, "kpi_env")) return rc;
+    if (!actions && dims->n_act_cols > 0 && (!act_low || !act_high)) return fail(CL_ENULL, "act_low / act_high are required for the on-device policy");
+    if (actions && act_stride_env == 1 && ((act_stride_col % 4) != 0 || (act_stride_step % 4) != 0))
+        return fail(CL_EALIGN, "action strides must be multiples of 4 floats for the coalesced layout");
+
+    RolloutArgs r;
+    StepArgs& a = r.s;
+    a.params = params; a.ts = ts; a.state = state; a.actions = actions; a.out_bldg = out_bldg; a.out_env = out_env;
+    a.kpi_bldg = kpi_bldg; a.kpi_env = kpi_env;
+    a.act_stride_col = act_stride_col; a.act_stride_env = act_stride_env;
+    a.flex_out = nullptr; a.n_flex_bldg = 0; a.ev_penalty_coef = 0.0f;
+    a.n_env = dims->n_env; a.n_bldg = dims->n_bldg; a.n_steps = dims->n_steps; a.ld = dims->n_env;
+    a.flags = dims->flags; a.t = t0; a.b_chunk = dims->n_bldg; a.n_chunks = 1; a.env_row0 = dims->env_row0; a.env_offset = (unsigned)dims->env_offset;
+    a.nt = 0; a.fused_finish = 0;
+    r.act_stride_step = act_stride_step; r.act_low = act_low; r.act_high = act_high; r.ret_env = ret_env; r.seed = seed;
+    r.t0 = t0; r.k_steps = k_steps;
+    // two buildings per wave; envs per lane as cl_rollout_f32 picks them (128-env workgroups in nearly full rounds of one per CU)
+    a.nw = tun.nw ? tun.nw : (dims->n_bldg + 1) / 2;
+    if (a.nw * 2 < dims->n_bldg || a.nw < 1 || a.nw > 16) return fail(CL_EINVAL, "bad nw %d", a.nw);
+    const long long wg2 = (dims->n_env + 127) / 128, rounds2 = (wg2 + 255) / 256;
+    const bool full_rounds = dims->n_env >= 32768 && wg2 * 100 >= rounds2 * 256 * 85;
+    const int vec = tun.vec ? tun.vec : (((actions == nullptr || act_stride_env == 1) && full_rounds) ? 2 : 1);
+    if (vec != 1 && vec != 2) return fail(CL_EINVAL, "no fused KPI rollout kernel at %d envs per lane", vec);
+    const int tile = 64 * vec;
+    const size_t lds = rollout_kpi_lds_floats(a.nw, tile) * sizeof(float);
+    if (lds > CL_LDS_PER_CU) return fail(CL_EINVAL, "the fused KPI rollout would need %zu bytes of LDS per workgroup (nw=%d, %d envs per lane): a CU has %d", lds, a.nw, vec, CL_LDS_PER_CU);
+    const bool chain = dims->flags & CLD_F64_CHAIN;
+    name_reset(tun);
+    name_add(tun, "cl_rollout_kpi_kernel<%d, %d>", vec, chain ? 2 : 0);
+    const int rc = cl_tu_launch_rollout(4000 + (chain ? 2000 : 0) + vec * 10 + 2, 1, (unsigned)((dims->n_env + tile - 1) / tile), 1u, 64u * a.nw, lds, stream, &r);
+    if (rc) return hip_fail((hipError_t)rc, "cl_rollout_kpi_kernel launch");
+    return CL_OK;
+}
+
 int cl_rollout_seq_f32(const cl_dims* dims, const uint32_t* params, const float* ts, float* state, const float* actions,
                        int64_t act_stride_step, int64_t act_stride_col, int64_t act_stride_env, const float* act_low,
                        const float* act_high, uint64_t seed, float* policy_actions, float* out_bldg, float* out_env,
                        float* ret_env, float* kpi_bldg, float* kpi_env, const cl_flex* flex, int32_t t0, int32_t k_steps, void* stream) {
     if (int rc = check_dims(dims)) return rc;
+    if (dims->flags & CLD_ROLLOUT_FUSED) {
+        if (int rc = check_ptr(actions, "actions", false)) return rc;
+        if (int rc = check_ptr(ret_env, "ret_env", false)) return rc;
+        if (k_steps < 0 || t0 < 0 || t0 + k_steps > dims->n_steps)
+            return fail(CL_ERANGE, "steps [%d, %d) outside [0, %d)", t0, t0 + k_steps, dims->n_steps);
+        return rollout_fused(dims, params, ts, state, actions, act_stride_step, act_stride_col, act_stride_env, act_low, act_high, seed, out_bldg,
+                             out_env, ret_env, kpi_bldg, kpi_env, flex, t0, k_steps, stream);
+    }
     if (int rc = check_ptr(actions, "actions", false)) return rc;
     if (int rc = check_ptr(ret_env, "ret_env", false)) return rc;
     if (!actions && dims->n_act_cols > 0) {
@@ -2000,7 +2078,8 @@ int cl_rollout_f32(const cl_dims* dims, const uint32_t* params, const float* ts,
     }
     if (((dims->flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT) == CLR_EV)
         return fail(CL_EINVAL, "reward kind CLR_EV needs the flexible-load tables (cl_rollout_seq_f32)");
-    if (dims->flags & CLD_KPI) return fail(CL_EINVAL, "the fused rollout keeps no streaming KPIs: use cl_rollout_seq_f32 with CLD_KPI");
+    if (dims->flags & CLD_KPI)
+        return fail(CL_EINVAL, "cl_rollout_f32 takes no KPI planes: call cl_rollout_seq_f32 with CLD_KPI (launch sequence), or with CLD_KPI | CLD_ROLLOUT_FUSED (one fused launch, battery + PV districts)");
     if (dims->flags & CLD_F64_MAPS) return fail(CL_EINVAL, "the fused rollout evaluates the battery map in fp32 or as the float64 chain (CLD_F64_CHAIN): use cl_rollout_seq_f32 with CLD_F64_MAPS");
     if (k_steps < 0 || t0 < 0 || t0 + k_steps > dims->n_steps)
         return fail(CL_ERANGE, "steps [%d, %d) outside [0, %d)", t0, t0 + k_steps, dims->n_steps);
@@ -2068,6 +2147,7 @@ int cl_rollout_f32(const cl_dims* dims, const uint32_t* params, const float* ts,
         const size_t tile_b = (size_t)64 * fvec * sizeof(float);
         const size_t rows = (size_t)a.nw * NQ * tile_b, rnd = (size_t)a.nw * tile_b + (size_t)a.nw * (fvec == 1 ? CL_ROLLOUT_RND_ROWS<1> : CL_ROLLOUT_RND_ROWS<2>) * tile_b;
         const size_t plds = rows > rnd ? rows : rnd;
+        if (plds > CL_LDS_PER_CU) return fail(CL_EINVAL, "the packed fused rollout would need %zu bytes of LDS per workgroup (nw=%d): a CU has %d", plds, a.nw, CL_LDS_PER_CU);
         name_add(tun, "cl_rollout_full_kernel<%d, %s, %d, %s>", fvec, chunked ? "true" : "false", chain ? 2 : 0, marl ? "true" : "false");
 #define CL_RFM(V, C, P, M) do { \
             if (plds > 64 * 1024) if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(cl_rollout_full_kernel<V, C, P, M>), plds); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(cl_rollout_full_kernel)"); \

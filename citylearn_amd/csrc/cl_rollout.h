@@ -312,6 +312,376 @@ __global__ void __launch_bounds__(1024) cl_rollout_kernel(const RolloutArgs r) {
     }
 }
 
+// ---- mode B with the streaming KPI accumulators (CLD_ROLLOUT_FUSED | CLD_KPI through cl_rollout_seq_f32) ---------------------------------------
+// The K-step loop of cl_rollout_kernel's battery + PV path (same unit, same action streams, same district reduction and return rows) that also
+// keeps what cl_step_lean_kpi_kernel + kpi_series_apply keep, in their layout and arithmetic, with ONE read and ONE write of every accumulator
+// per launch instead of per step:
+//  * per (env, building) CLK_C_POS / _NET / _EMISSION / _COST: four registers per unit, loaded before the loop, stored behind it;
+//  * per env block (CL_ROW0_BLOCK envs share a table row), at the block's first env: CLK_B_POS .. CLK_B_COST and CLK_EXPECTED_ALL, five registers
+//    per building of the block's FIRST workgroup (lane 0 loads and stores them);
+//  * per env the control district series (rows CLKE_PREV .. CLKE_ALL_MAX of kpi_env) and per env block the baseline series (the rows behind
+//    CLKE_PER_COND): twelve accumulators each, parked in LDS for the whole launch ([12][tile] + [12]) -- in registers they would cost every wave of
+//    the workgroup twelve VGPRs for the sake of the one or two waves that own a series.
+// The district series needs the DISTRICT net of every step.  Chosen: every wave's partial net of step k goes to slot k % S of an LDS ring
+// [S][nw][tile] (S = CL_RKPI_S = 8), and every S steps (and behind the last step) the threads that own an env's series add the waves' partials in
+// wave order 0 .. nw-1 -- district_reduce's order -- and feed the S samples to the series, day (24) and month (730) groups closing on the ABSOLUTE
+// step index t0 + k.  Two barriers per S steps instead of MARL's two per step: a barrier stalls all nw waves for the slowest one, and the loop
+// is VALU-bound.  MARL needs the district net inside the step anyway: it reads the ring slot it just wrote behind ONE barrier per step (the next
+// step writes another slot; the fold's trailing barrier protects the wrap).  The baseline series' samples -- sum over the buildings, in building
+// order, of the net without the battery -- take the same route: lane 0 of every wave parks its buildings' values in [S][32], the workgroup's
+// last thread folds them (cl_step_lean_kpi_kernel's `base_writer`).
+// LDS per workgroup: 4 x (S nw tile + 12 tile + 16 + 32 S) bytes -- 44 080 at 17 buildings (nw = 9) and two envs per lane, 72 752 at the
+// largest geometry (nw = 16, two envs per lane); the host refuses anything beyond the CU's 160 KiB before it launches.  The last step's
+// district reduction ([nw][NQ][tile]) and the return rows alias the ring (S >= NQ).
+// Instantiations: two buildings per wave (what every lean district of up to 32 buildings fits into, and the only form of the plain kernel that
+// exists for the float64 chain), one and two envs per lane (the host picks as cl_rollout_f32 does), PREC 0 and 2; curve parameters pinned.
+// Lives in the no-SLP unit like cl_rollout_kernel: same arithmetic, same loss to packed fp32.
+constexpr int CL_LDS_PER_CU = 160 * 1024;      // gfx950: what one workgroup can be given at most (the host refuses a fused-rollout geometry beyond it)
+constexpr int CL_RKPI_S = 8;          // steps per fold of the district series
+constexpr int CL_RKPI_NB = 32;        // buildings of a district this kernel holds in one workgroup row
+constexpr size_t rollout_kpi_lds_floats(int nw, int tile) {
+    return (size_t)CL_RKPI_S * nw * tile + (size_t)CLKE_PER_COND * tile + 16 + (size_t)CL_RKPI_S * 4 * CL_RKPI_NB + 5 * CL_RKPI_NB;
+}
+
+// Wave-uniform reads of the READ-ONLY tables (params, ts, action bounds) through the constant address space: inside a loop that holds a barrier the
+// compiler no longer proves a global read unclobbered and fetches it with a vector load per lane + v_readfirstlane (cl_rollout_full_kernel's note);
+// a constant-address-space read is a scalar load whatever surrounds it.  Nothing writes these tables while a kernel runs.
+typedef const uint32_t __attribute__((address_space(4)))* cl_cptr;
+CL_DEV cl_cptr as_const(const void* p) { return (cl_cptr)(const uint32_t*)p; }
+CL_DEV float cw(cl_cptr p, int slot) { return __uint_as_float(p[slot]); }
+CL_DEV double cd(cl_cptr p, int k) {                               // k-th double of the CLP_C_* block (cl::pc)
+    const uint64_t bits = (uint64_t)p[CLP_C_FIRST + 2 * k] | ((uint64_t)p[CLP_C_FIRST + 2 * k + 1] << 32);
+    double d;
+    __builtin_memcpy(&d, &bits, 8);
+    return d;
+}
+CL_DEV void load_battc_const(cl::BattC& C, cl_cptr p) {            // cl::load_battc
+    C.cap = cd(p, CLPC_CAP); C.oml = cd(p, CLPC_OML); C.rcap = cd(p, CLPC_RCAP); C.pdt = cd(p, CLPC_PDT); C.pow = cd(p, CLPC_POW);
+    C.rpow = cd(p, CLPC_RPOW); C.r = cd(p, CLPC_TSR);
+    C.ca0 = cd(p, CLPC_CPC_A0); C.cb0 = cd(p, CLPC_CPC_B0); C.cx1 = cd(p, CLPC_CPC_X1); C.cdb1 = cd(p, CLPC_CPC_DB1);
+    C.ea0 = cd(p, CLPC_PEC_A0); C.eb0 = cd(p, CLPC_PEC_B0); C.ex1 = cd(p, CLPC_PEC_X1); C.edb1 = cd(p, CLPC_PEC_DB1);
+    C.ex2 = cd(p, CLPC_PEC_X2); C.edb2 = cd(p, CLPC_PEC_DB2); C.ex3 = cd(p, CLPC_PEC_X3); C.edb3 = cd(p, CLPC_PEC_DB3);
+    C.cap32 = cw(p, CLP_L_CAP); C.omd32 = cw(p, CLP_L_OMD); C.degk = cw(p, CLP_L_DEGK);
+}
+// rollout_action_cached with the column's bounds read through the constant address space
+template <int VEC>
+CL_DEV void rollout_action_kpi(float (&dst)[VEC], PhiloxCache (&cache)[VEC], const RolloutArgs& r, int col, int env0, int t, int k, bool live) {
+    if (col < 0 || r.s.actions) { rollout_action<VEC>(dst, r, col, env0, t, k, live); return; }
+    if (k == 0 || (t & 3) == 0) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            const cl::U4 blk = cl::philox_block(r.seed, (uint32_t)(env0 + i) + r.s.env_offset, (uint32_t)col, (uint32_t)t >> 2);
+            cache[i].w0 = blk.w[0]; cache[i].w1 = blk.w[1]; cache[i].w2 = blk.w[2]; cache[i].w3 = blk.w[3];
+        }
+    }
+    const float lo = cw(as_const(r.act_low), col), span = cw(as_const(r.act_high), col) - lo;
+    const int sel = t & 3;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+        const uint32_t w0 = cache[i].w0, w1 = cache[i].w1, w2 = cache[i].w2, w3 = cache[i].w3;
+        const uint32_t lo_w = (sel & 1) ? w1 : w0, hi_w = (sel & 1) ? w3 : w2;
+        const uint32_t word = (sel & 2) ? hi_w : lo_w;
+        dst[i] = fmaf(cl::u01(word), span, lo);
+    }
+}
+
+struct KpiSeriesAll { float prev, ramp, dsum, dmax, dlf, dpk, dn, msum, mmax, mlf, mn, amax; };
+CL_DEV void kpi_series_get(KpiSeriesAll& s, const float* k, long long stride) {
+    s.prev = k[CLKE_PREV * stride]; s.ramp = k[CLKE_RAMP * stride]; s.dsum = k[CLKE_DAY_SUM * stride]; s.dmax = k[CLKE_DAY_MAX * stride];
+    s.dlf = k[CLKE_DAY_LF_SUM * stride]; s.dpk = k[CLKE_DAY_PEAK_SUM * stride]; s.dn = k[CLKE_DAY_N * stride];
+    s.msum = k[CLKE_MON_SUM * stride]; s.mmax = k[CLKE_MON_MAX * stride]; s.mlf = k[CLKE_MON_LF_SUM * stride]; s.mn = k[CLKE_MON_N * stride];
+    s.amax = k[CLKE_ALL_MAX * stride];
+}
+CL_DEV void kpi_series_put(float* k, long long stride, const KpiSeriesAll& s) {
+    k[CLKE_PREV * stride] = s.prev; k[CLKE_RAMP * stride] = s.ramp; k[CLKE_DAY_SUM * stride] = s.dsum; k[CLKE_DAY_MAX * stride] = s.dmax;
+    k[CLKE_DAY_LF_SUM * stride] = s.dlf; k[CLKE_DAY_PEAK_SUM * stride] = s.dpk; k[CLKE_DAY_N * stride] = s.dn;
+    k[CLKE_MON_SUM * stride] = s.msum; k[CLKE_MON_MAX * stride] = s.mmax; k[CLKE_MON_LF_SUM * stride] = s.mlf; k[CLKE_MON_N * stride] = s.mn;
+    k[CLKE_ALL_MAX * stride] = s.amax;
+}
+// one more sample `v` (index t) of a district series whose twelve accumulators sit in LDS at k[row * stride]: kpi_series_apply's statements.
+// (On the LDS copy, not on a register copy of the twelve: the fold's registers are every wave's registers, and the two-envs-per-lane fp32
+//  instantiation went to scratch memory with them.)
+CL_DEV void kpi_series_advance(float* k, int stride, int t, float v) {
+    if (t > 0) k[CLKE_RAMP * stride] = k[CLKE_RAMP * stride] + fmaxf(v - k[CLKE_PREV * stride], 0.0f);
+    k[CLKE_PREV * stride] = v;
+    float dsum = k[CLKE_DAY_SUM * stride], dmax = k[CLKE_DAY_MAX * stride];
+    if (t > 0 && t % 24 == 0) {
+        k[CLKE_DAY_LF_SUM * stride] += 1.0f - (dsum * (1.0f / 24.0f)) / dmax;
+        k[CLKE_DAY_PEAK_SUM * stride] += dmax;
+        k[CLKE_DAY_N * stride] += 1.0f;
+        dsum = 0.0f; dmax = -INFINITY;
+    }
+    k[CLKE_DAY_SUM * stride] = dsum + v; k[CLKE_DAY_MAX * stride] = fmaxf(dmax, v);
+    float msum = k[CLKE_MON_SUM * stride], mmax = k[CLKE_MON_MAX * stride];
+    if (t > 0 && t % 730 == 0) {
+        k[CLKE_MON_LF_SUM * stride] += 1.0f - (msum * (1.0f / 730.0f)) / mmax;
+        k[CLKE_MON_N * stride] += 1.0f;
+        msum = 0.0f; mmax = -INFINITY;
+    }
+    k[CLKE_MON_SUM * stride] = msum + v; k[CLKE_MON_MAX * stride] = fmaxf(mmax, v);
+    k[CLKE_ALL_MAX * stride] = fmaxf(k[CLKE_ALL_MAX * stride], v);
+}
+
+template <int VEC, int PREC>
+__global__ void __launch_bounds__(1024) cl_rollout_kpi_kernel(const RolloutArgs r) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];     // ring [S][nw][64*VEC] | control series [12][64*VEC] | baseline series [16] | rows [S][4][32] | baseline sums [5][32]
+    constexpr int MB = 2, TILE = 64 * VEC, S = CL_RKPI_S;
+    const StepArgs& a = r.s;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int tile_env0 = blockIdx.x * TILE;
+    const int env0 = tile_env0 + lane * VEC;
+    const bool live = env0 < a.n_env;
+    const long long plane = (long long)a.n_bldg * a.n_env;         // (no row pitch with KPI planes: host)
+    const int rkind = (a.flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT;
+    const bool quirk = a.flags & CLD_REF_T0_QUIRK;
+    const bool head = tile_env0 % CL_ROW0_BLOCK == 0;               // workgroup-uniform: this workgroup keeps its env block's env-independent sums
+    const bool base_owner = head && threadIdx.x == blockDim.x - 1;
+    float* const ser = lds + (size_t)S * a.nw * TILE;
+    float* const bser = ser + (size_t)CLKE_PER_COND * TILE;
+    float* const brow = bser + 16;                                  // per ring slot and building: baseline net, carbon intensity, price, load
+    float* const bsum = brow + S * 4 * CL_RKPI_NB;                  // CLK_B_POS, _NET, _EMISSION, _COST, CLK_EXPECTED_ALL of the env block
+    // the env block's per-building sums: lane b of the head workgroup's LAST wave keeps building b's five
+    const bool bsum_owner = head && w == a.nw - 1 && lane < a.n_bldg;
+
+    // the district series' accumulators: HBM -> LDS, by the thread that folds them (no barrier: nobody else touches the column)
+    for (int e = threadIdx.x; e < TILE; e += blockDim.x) {
+        if (tile_env0 + e >= a.n_env) continue;
+        KpiSeriesAll c;
+        kpi_series_get(c, a.kpi_env + tile_env0 + e, a.n_env);
+        kpi_series_put(ser + e, TILE, c);
+    }
+    if (base_owner) {
+        KpiSeriesAll c;
+        kpi_series_get(c, a.kpi_env + (long long)CLKE_PER_COND * a.n_env + tile_env0, a.n_env);
+        kpi_series_put(bser, 1, c);
+    }
+    if (bsum_owner) {
+        const float* kp = a.kpi_bldg + (long long)lane * a.n_env + tile_env0;      // building `lane` at the block's first env
+        bsum[0 * CL_RKPI_NB + lane] = kp[(long long)CLK_B_POS * plane]; bsum[1 * CL_RKPI_NB + lane] = kp[(long long)CLK_B_NET * plane];
+        bsum[2 * CL_RKPI_NB + lane] = kp[(long long)CLK_B_EMISSION * plane]; bsum[3 * CL_RKPI_NB + lane] = kp[(long long)CLK_B_COST * plane];
+        bsum[4 * CL_RKPI_NB + lane] = kp[(long long)CLK_EXPECTED_ALL * plane];
+    }
+
+    const float* __restrict__ ts_w = a.ts + (long long)w * CL_NF;
+    cl::Bp B[MB];
+    cl::State St[MB][VEC];
+    bool own[MB];
+    long long off[MB];
+    float k_pos[MB][VEC], k_net[MB][VEC], k_em[MB][VEC], k_cost[MB][VEC];
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+        const int b = w + m * a.nw;
+        own[m] = b < a.n_bldg;
+        const int bc = own[m] ? b : w;
+        off[m] = (long long)bc * a.n_env + env0;
+        cl::load_bp<false>(B[m], a.params + (long long)bc * CL_NP);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            St[m][i] = {0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            k_pos[m][i] = k_net[m][i] = k_em[m][i] = k_cost[m][i] = 0.0f;
+        }
+        if (live && own[m]) {
+            float v[VEC];
+#define CL_GET(dst, base, plane_id)                                    \
+    vload<VEC>(v, base + (long long)(plane_id) * plane + off[m]);      \
+    _Pragma("unroll") for (int i = 0; i < VEC; ++i) dst = v[i];
+            CL_GET(St[m][i].soc, a.state, CLS_B_SOC) CL_GET(St[m][i].eff, a.state, CLS_B_EFF) CL_GET(St[m][i].degcap, a.state, CLS_B_DEGCAP)
+            CL_GET(k_pos[m][i], a.kpi_bldg, CLK_C_POS) CL_GET(k_net[m][i], a.kpi_bldg, CLK_C_NET)
+            CL_GET(k_em[m][i], a.kpi_bldg, CLK_C_EMISSION) CL_GET(k_cost[m][i], a.kpi_bldg, CLK_C_COST)
+#undef CL_GET
+        }
+    }
+    cl::BattP Bv[MB];
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+        Bv[m] = B[m].batt;
+        // the curve parameters pinned in VGPRs for all K steps (cl_rollout_kernel's PIN) -- not at two envs per lane on the fp32 map: the sixteen
+        // control sums on top of cl_rollout_kernel<2, false, 2>'s 112 registers leave nothing of the 128 a 1024-thread workgroup may have, and with
+        // the pins (all twelve, or the efficiency curve's eight) the instantiation parks 44 / 12 bytes in scratch memory
+        if constexpr (VEC == 2 && PREC == 0) continue;
+        CL_PIN_V(Bv[m].cpc_a0); CL_PIN_V(Bv[m].cpc_b0); CL_PIN_V(Bv[m].cpc_a1); CL_PIN_V(Bv[m].cpc_b1);
+        CL_PIN_V(Bv[m].pec_a0); CL_PIN_V(Bv[m].pec_b0); CL_PIN_V(Bv[m].pec_a1); CL_PIN_V(Bv[m].pec_b1);
+        CL_PIN_V(Bv[m].pec_a2); CL_PIN_V(Bv[m].pec_b2); CL_PIN_V(Bv[m].pec_a3); CL_PIN_V(Bv[m].pec_b3);
+    }
+    float ret[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) ret[i] = 0.0f;
+    float q_net[VEC], q_cost[VEC], q_em[VEC], q_rw[VEC];
+    float last_net[MB][VEC], last_rw[MB][VEC];
+    PhiloxCache rnd[MB][VEC];
+
+    const int row0 = a.env_row0 ? a.env_row0[tile_env0 / CL_ROW0_BLOCK] : 0;   // workgroup-uniform
+    for (int k = 0; k < r.k_steps; ++k) {
+        const int t = r.t0 + k;
+        const int slot = k & (S - 1);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) q_net[i] = q_cost[i] = q_em[i] = q_rw[i] = 0.0f;
+#pragma unroll
+        for (int m = 0; m < MB; ++m) {
+            if (!own[m]) continue;                                       // wave-uniform
+            cl::Row R;
+            const cl_cptr q = as_const(ts_w + ((long long)(t + row0) * a.n_bldg + m * a.nw) * CL_NF);
+            R.nsl = cw(q, CLT_NSL); R.sol = cw(q, CLT_SOLAR); R.price = cw(q, CLT_PRICE); R.carbon = cw(q, CLT_CARBON);
+            float a_es[VEC];
+            rollout_action_kpi<VEC>(a_es, rnd[m], r, B[m].a_es, env0, t, k, live);
+            // the lean unit exactly as in cl_rollout_kernel
+            const bool first = quirk && t == 0;
+            float c_ns = first ? 3.0f * R.nsl : R.nsl, sol = R.sol;
+            const float cbk = first ? 2.0f : 1.0f;
+            if (head && lane == 0) {
+                // the step's net with the battery term left out (and what prices it): for the env block's baseline sums and baseline district series
+                float* row = brow + (size_t)slot * 4 * CL_RKPI_NB + w + m * a.nw;
+                row[0 * CL_RKPI_NB] = fmaf(c_ns, B[m].r, sol); row[1 * CL_RKPI_NB] = R.carbon; row[2 * CL_RKPI_NB] = R.price; row[3 * CL_RKPI_NB] = R.nsl;
+            }
+            if constexpr (VEC > 1) { CL_PIN_V(c_ns); CL_PIN_V(sol); }
+            const bool batt = B[m].flags & CLF_BATTERY;
+            float nets[VEC], socs[VEC], rws[VEC];
+            [[maybe_unused]] cl::BattC bc;
+            if constexpr (PREC == 2) {
+                if (batt) load_battc_const(bc, as_const(B[m].p));   // (scalar loads every step, as in cl_rollout_kernel)
+            }
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                float eb = 0.0f;
+                if constexpr (PREC == 2) {
+                    if (batt) eb = cl::battery_charge_chain(bc, a_es[i], INFINITY, St[m][i]);
+                } else if (batt) eb = cl::battery_energy(Bv[m], a_es[i] * Bv[m].pdt, St[m][i]);
+                nets[i] = fmaf(c_ns + cbk * eb, B[m].r, sol);
+                socs[i] = St[m][i].soc;
+            }
+            cl::lean_rewards<VEC>(rkind, B[m], socs, nets, rws);
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                last_net[m][i] = nets[i]; last_rw[m][i] = rws[i];
+                q_net[i] += nets[i]; q_cost[i] += cl::mul_rn(nets[i], R.price); q_em[i] += fmaxf(0.0f, nets[i] * R.carbon); q_rw[i] += rws[i];
+                // cl_step_lean_kpi_kernel's four control sums
+                k_pos[m][i] += fmaxf(nets[i], 0.0f); k_net[m][i] += nets[i];
+                k_em[m][i] += fmaxf(nets[i] * R.carbon, 0.0f); k_cost[m][i] += fmaxf(nets[i] * R.price, 0.0f);
+            }
+        }
+        vstore<VEC>(lds + ((size_t)slot * a.nw + w) * TILE + lane * VEC, q_net);
+        if (rkind == CLR_MARL) {
+            __syncthreads();
+            float dnet[VEC];
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) dnet[i] = 0.0f;
+            for (int kk = 0; kk < a.nw; ++kk) {
+                float part[VEC];
+                vload<VEC>(part, lds + ((size_t)slot * a.nw + kk) * TILE + lane * VEC);
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) dnet[i] += part[i];
+            }
+#pragma unroll
+            for (int m = 0; m < MB; ++m) {
+                if (!own[m]) continue;
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) { last_rw[m][i] = cl::marl_reward(last_net[m][i], dnet[i]); ret[i] += last_rw[m][i]; }
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) ret[i] += q_rw[i];
+        }
+        if (slot == S - 1 || k == r.k_steps - 1) {
+            // fold the ring's slot + 1 samples (steps t - slot .. t) into the district series
+            if (rkind != CLR_MARL) __syncthreads();                      // (MARL: everybody's slot is behind this step's barrier already)
+            const int tb = t - slot;
+            for (int e = threadIdx.x; e < TILE; e += blockDim.x) {
+                if (tile_env0 + e >= a.n_env) continue;
+                for (int j = 0; j <= slot; ++j) {
+                    float v = 0.0f;
+                    for (int kk = 0; kk < a.nw; ++kk) v += lds[((size_t)j * a.nw + kk) * TILE + e];
+                    kpi_series_advance(ser + e, TILE, tb + j, v);
+                }
+            }
+            if (bsum_owner) {
+                // cl_step_lean_kpi_kernel's `block_sums`, step by step
+                float p_pos = bsum[0 * CL_RKPI_NB + lane], p_net = bsum[1 * CL_RKPI_NB + lane], p_em = bsum[2 * CL_RKPI_NB + lane],
+                      p_cost = bsum[3 * CL_RKPI_NB + lane], p_exp = bsum[4 * CL_RKPI_NB + lane];
+                for (int j = 0; j <= slot; ++j) {
+                    const float* row = brow + (size_t)j * 4 * CL_RKPI_NB + lane;
+                    const float base = row[0 * CL_RKPI_NB], carbon = row[1 * CL_RKPI_NB], price = row[2 * CL_RKPI_NB];
+                    p_pos += fmaxf(base, 0.0f); p_net += base;
+                    p_em += fmaxf(base * carbon, 0.0f); p_cost += fmaxf(base * price, 0.0f);
+                    p_exp += row[3 * CL_RKPI_NB];
+                }
+                bsum[0 * CL_RKPI_NB + lane] = p_pos; bsum[1 * CL_RKPI_NB + lane] = p_net; bsum[2 * CL_RKPI_NB + lane] = p_em;
+                bsum[3 * CL_RKPI_NB + lane] = p_cost; bsum[4 * CL_RKPI_NB + lane] = p_exp;
+            }
+            if (base_owner) {
+                // the baseline district series: the buildings' baselines in building order (cl_step_lean_kpi_kernel's `base_writer`)
+                for (int j = 0; j <= slot; ++j) {
+                    float v = 0.0f;
+                    for (int b = 0; b < a.n_bldg; ++b) v += brow[(size_t)j * 4 * CL_RKPI_NB + b];
+                    kpi_series_advance(bser, 1, tb + j, v);
+                }
+            }
+            __syncthreads();                                             // the ring is free again (and, behind the last step, for the reduction rows)
+        }
+    }
+
+    // ---- write back: carried state, the last step's per-building outputs, the KPI accumulators, district sums, episode-return partials ----
+#pragma unroll
+    for (int m = 0; m < MB; ++m) {
+        if (!own[m]) continue;
+        if (live) {
+            float v[VEC];
+#define CL_PUT(base, plane_id, expr)                                   \
+    _Pragma("unroll") for (int i = 0; i < VEC; ++i) v[i] = (expr);      \
+    vstore<VEC>(base + (long long)(plane_id) * plane + off[m], v);
+            if (B[m].flags & CLF_BATTERY) {
+                CL_PUT(a.state, CLS_B_SOC, St[m][i].soc) CL_PUT(a.state, CLS_B_EFF, St[m][i].eff) CL_PUT(a.state, CLS_B_DEGCAP, St[m][i].degcap)
+            }
+            if (r.k_steps > 0) {
+                CL_PUT(a.out_bldg, CLO_NET, last_net[m][i])
+                CL_PUT(a.out_bldg, CLO_REWARD, last_rw[m][i])
+                CL_PUT(a.kpi_bldg, CLK_C_POS, k_pos[m][i]) CL_PUT(a.kpi_bldg, CLK_C_NET, k_net[m][i])
+                CL_PUT(a.kpi_bldg, CLK_C_EMISSION, k_em[m][i]) CL_PUT(a.kpi_bldg, CLK_C_COST, k_cost[m][i])
+            }
+#undef CL_PUT
+        }
+    }
+    if (r.k_steps > 0) {
+        if (bsum_owner) {
+            float* kp = a.kpi_bldg + (long long)lane * a.n_env + tile_env0;
+            kp[(long long)CLK_B_POS * plane] = bsum[0 * CL_RKPI_NB + lane]; kp[(long long)CLK_B_NET * plane] = bsum[1 * CL_RKPI_NB + lane];
+            kp[(long long)CLK_B_EMISSION * plane] = bsum[2 * CL_RKPI_NB + lane]; kp[(long long)CLK_B_COST * plane] = bsum[3 * CL_RKPI_NB + lane];
+            kp[(long long)CLK_EXPECTED_ALL * plane] = bsum[4 * CL_RKPI_NB + lane];
+        }
+        for (int e = threadIdx.x; e < TILE; e += blockDim.x) {
+            if (tile_env0 + e >= a.n_env) continue;
+            KpiSeriesAll c;
+            kpi_series_get(c, ser + e, TILE);
+            kpi_series_put(a.kpi_env + tile_env0 + e, a.n_env, c);
+        }
+        if (base_owner) {
+            KpiSeriesAll c;
+            kpi_series_get(c, bser, 1);
+            kpi_series_put(a.kpi_env + (long long)CLKE_PER_COND * a.n_env + tile_env0, a.n_env, c);
+        }
+        if (rkind == CLR_MARL) {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                q_rw[i] = 0.0f;
+#pragma unroll
+                for (int m = 0; m < MB; ++m) q_rw[i] += own[m] ? last_rw[m][i] : 0.0f;
+            }
+        }
+        // district sums of the last step (for MARL the reward plane / sum were finished above: pass kind DEFAULT)
+        district_reduce<VEC>(a, lds, w, lane, env0, live, plane, rkind == CLR_MARL ? (int)CLR_DEFAULT : rkind, q_net, q_cost, q_em, q_rw, a.nw);
+    }
+    if (r.ret_env) {
+        __syncthreads();
+        vstore<VEC>(lds + (size_t)w * TILE + lane * VEC, ret);
+        __syncthreads();
+        for (int e = threadIdx.x; e < TILE; e += blockDim.x) {
+            float s = 0.0f;
+            for (int kk = 0; kk < a.nw; ++kk) s += lds[(size_t)kk * TILE + e];
+            if (tile_env0 + e < a.n_env) r.ret_env[tile_env0 + e] += s;
+        }
+    }
+}
+
 #ifndef CL_TU_NOSLP
 // ---- mode B for thermal / outage districts around the PACK-GENERIC unit of cl_full.h (round 6) ------------------------------------------------
 // cl_rollout_kernel<1, true, 1> above steps a thermal building with the scalar unit of cl_unit.h at one env per lane: 384 vector instructions per

@@ -215,6 +215,7 @@ class StepEngine:
         self._flex_ref = None if self.flex is None else ctypes.byref(self.flex)
         self.act_low = self.act_high = None         # bounds of the on-device rollout policy (set_action_limits)
         self._policy_actions = None                 # scratch planes of cl_rollout_seq_f32 (four steps of policy draws)
+        self._dims_fused = None                     # `dims` with CLD_ROLLOUT_FUSED (rollout(fused=True) on a kpi=True engine)
         self.t = 0
         self.reset()
 
@@ -438,6 +439,13 @@ class StepEngine:
         couples the buildings of a chunked district inside a step (MARL) run the same K steps as K x (policy, [flex], step, [kpi])
         launches (`cl_rollout_seq_f32`), same action streams; ``fused=False`` asks for that sequence explicitly.
 
+        ``fused=True`` on a ``kpi=True`` engine runs the K steps as ONE fused launch that keeps the streaming KPI accumulators itself
+        (`cl_rollout_seq_f32` under `CLD_ROLLOUT_FUSED`: `cl_rollout_kpi_kernel`, battery + PV districts of up to 32 buildings on the fp32 map
+        or the float64 chain) -- the planes `evaluate()` / `state_dict()` read are the same, equal to the single-step path's to ~1e-6 relative,
+        not bit for bit, which is why ``fused=None`` keeps the launch sequence for ``kpi=True``.  On a district that kernel does not cover
+        (thermal / outage, more than 32 buildings, flexible loads, ``f64_maps=True``) ``fused=True`` raises the library's `EngineError`
+        (`CL_EINVAL`): it never degrades to the sequence.
+
         ``actions``: open-loop float32 tensor ``[k_steps, n_act_cols, n_env]`` (any strides), or ``None`` for the
         on-device policy ``a = low + u (high - low)``, ``u = Philox4x32-10(seed; env, column, t)``.
         ``ret_env`` (``[n_env]``, optional) accumulates the district reward summed over the K steps."""
@@ -455,14 +463,21 @@ class StepEngine:
         chunked = self.n_bldg > (16 if full else 32)
         if fused is None:
             fused = not (self.flex is not None or self.kpi or self.f64_maps or (chunked and self.reward == 'MARL'))
-        if not fused:
-            if actions is None and self._policy_actions is None:
+        fused_kpi = bool(fused) and self.kpi          # one fused launch that keeps the KPI accumulators, or the library's refusal
+        if not fused or fused_kpi:
+            dims = self.dims
+            if fused_kpi:
+                if self._dims_fused is None:        # the same dims with CLD_ROLLOUT_FUSED (same tuning block: trace_kernels() sees this call too)
+                    self._dims_fused = _lib.Dims.from_buffer_copy(self.dims)
+                    self._dims_fused.flags |= abi.CLD_ROLLOUT_FUSED
+                dims = self._dims_fused
+            elif actions is None and self._policy_actions is None:
                 self._policy_actions = torch.empty((4, self.n_act_cols, self.n_env), dtype=torch.float32, device=self.device)
             with torch.cuda.device(self.device):
                 _lib.check(self.lib.cl_rollout_seq_f32(
-                    ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), _ptr(actions), st[0], st[1], st[2],
+                    ctypes.byref(dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), _ptr(actions), st[0], st[1], st[2],
                     _ptr(self.act_low), _ptr(self.act_high), int(seed) & (2 ** 64 - 1),
-                    _ptr(None if actions is not None else self._policy_actions), _ptr(self.out_bldg), _ptr(self._out_env), _ptr(ret_env),
+                    _ptr(None if actions is not None or fused_kpi else self._policy_actions), _ptr(self.out_bldg), _ptr(self._out_env), _ptr(ret_env),
                     _ptr(self.kpi_bldg), _ptr(self.kpi_env), self._flex_ref, int(t0), int(k_steps), self._stream()))
             self.t = t0 + k_steps
             self._pending_t = None          # (cl_rollout_seq_f32 finishes its last step itself)

@@ -392,11 +392,14 @@ class VectorCityLearnEnv:
         the user-level API (scripts/env_step_bench.py).  See `CapturedRollout`."""
         return CapturedRollout(self, policy, int(k_steps), keep_rewards)
 
-    def rollout(self, k_steps: int, actions: Optional[torch.Tensor] = None, seed: int = 0) -> torch.Tensor:
+    def rollout(self, k_steps: int, actions: Optional[torch.Tensor] = None, seed: int = 0, fused: Optional[bool] = None) -> torch.Tensor:
         """Advance ``k_steps`` steps without returning to Python in between (`StepEngine.rollout`: one fused launch, or a launch
         sequence for districts with flexible loads) with open-loop ``actions`` ``[k_steps, n_act_cols, n_envs]`` or the uniform
         random policy keyed by ``seed`` (the device analogue of `Agent.predict`, agents/base.py:188-209).  Returns the district
-        reward summed over those steps, ``[n_envs]``.  Streaming KPIs (``kpi=True``) are updated after every step.  Not available with
+        reward summed over those steps, ``[n_envs]``.  Streaming KPIs (``kpi=True``) are updated after every step -- by the launch
+        sequence, or with ``fused=True`` inside one fused launch (battery + PV districts of up to 32 buildings; `StepEngine.rollout`:
+        `evaluate()` reads the same accumulators afterwards, and a district the fused kernel does not cover raises instead of
+        degrading).  ``fused=None`` is the engine's own choice, ``fused=False`` the launch sequence.  Not available with
         the LSTM temperature stage or a batched reward plugin, which run their own code between steps -- use :meth:`step` there."""
         if self.stage is not None or self._plugin is not None:
             raise NotImplementedError('rollout() needs a district without the LSTM temperature stage and a fused reward; use step()')
@@ -406,7 +409,7 @@ class VectorCityLearnEnv:
         if actions is None and e.act_low is None:
             e.set_action_limits(self.action_low.cpu().numpy(), self.action_high.cpu().numpy())
         ret = torch.zeros(self.n_envs, dtype=torch.float32, device=self.device)
-        e.rollout(k_steps, actions=actions, seed=seed, ret_env=ret, t0=self._t)
+        e.rollout(k_steps, actions=actions, seed=seed, ret_env=ret, t0=self._t, fused=fused)
         self._t += k_steps
         return ret
 

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define CL_ABI_VERSION 8   /* 8: CLD_CHECK (the reference's runtime assertions as a violation word per unit), tickets of the in-launch fold at the reserved plane's tail; 7: CLD_F64_CHAIN (params rows of 320 words: CLP_C_* block); 6: cl_finish_f32, cl_tuning.finish = 3 (deferred finish); 5: cl_tuning.kernel_name, CLD_F64_MAPS; 4: LSTM tables with pre-scaled gate rows, CLD_LSTM_F16 (two-term f16 `lstm_wb`) */
+#define CL_ABI_VERSION 9   /* 9: CLD_ROLLOUT_FUSED (cl_rollout_seq_f32 as ONE fused launch, with the streaming KPI accumulators kept inside it: cl_rollout_kpi_kernel); 8: CLD_CHECK (the reference's runtime assertions as a violation word per unit), tickets of the in-launch fold at the reserved plane's tail; 7: CLD_F64_CHAIN (params rows of 320 words: CLP_C_* block); 6: cl_finish_f32, cl_tuning.finish = 3 (deferred finish); 5: cl_tuning.kernel_name, CLD_F64_MAPS; 4: LSTM tables with pre-scaled gate rows, CLD_LSTM_F16 (two-term f16 `lstm_wb`) */
 
 /* ---- error codes ---- */
 #define CL_OK            0
@@ -318,6 +318,14 @@ enum cl_kpi_env {             /* kpi_env[cond*12 + k][env], cond 0 = control dis
                                          cut into building chunks (n_bldg <= 32), whose scratch the plane otherwise is; selects the general step kernel
                                          (cl_step_kernel<1, true, true, .., CHECK = true>), one env per lane.  The demand-limit assertion
                                          (building.py:1825-1829) only involves env-independent operands and stays a host table (CityLearnEnv). */
+#define CLD_ROLLOUT_FUSED  (1u << 16) /* cl_rollout_seq_f32 only (ABI 9; every other entry point ignores it): run the K steps in ONE fused launch or return CL_EINVAL
+                                         with the reason -- never the launch sequence.  Without CLD_KPI the call is forwarded to cl_rollout_f32.  With
+                                         CLD_KPI the fused kernel keeps the streaming accumulators itself (cl_rollout_kpi_kernel: one read and one write
+                                         of `kpi_bldg` / `kpi_env` per K steps, same layout as K calls of cl_step_f32 leave, values equal to ~1e-6 relative
+                                         like the rest of the fused rollout -- not bit for bit): CLD_LEAN districts of up to 32 buildings, fp32 map or
+                                         CLD_F64_CHAIN, every reward kind but CLR_EV, both action sources, env_row0 / env_offset.  Refused with the flag:
+                                         flex != NULL, CLD_F64_MAPS; and with CLD_KPI also a district without CLD_LEAN, n_bldg > 32 (a building-chunked
+                                         launch), CLD_WRITE_DETAIL, env_pitch != n_env.  `policy_actions` is not read on this path and may be NULL. */
 enum cl_violation {
     CLV_FLEXIBILITY = 1,   /* downward_electrical_flexibility < 0 beyond TOLERANCE during a power outage (building.py:665) */
     CLV_COOLING     = 2,   /* ___electricity_consumption_polarity_check('cooling', ..): negative device consumption (building.py:1660, 1831-1835) */
@@ -435,9 +443,12 @@ int cl_step_f32(const cl_dims* dims, const uint32_t* params, const float* ts, fl
  * Districts of more than 32 battery + PV / 16 thermal buildings run building-chunked (round 5): workgroup rows of `cl_tuning.b_chunk` (default 32 /
  * 8) buildings, the last step's chunk partial sums and each chunk's share of the return in the scratch rows of out_bldg's reserved plane
  * (n_chunks x (CL_NQ + 1) rows of n_env floats), folded by ONE cl_finish_kernel launch per call -- out_env / ret_env are final on return.
- * Limits of the fused kernel: no streaming KPIs (CLD_KPI), no flexible loads, no CLD_F64_MAPS (CLD_F64_CHAIN is available), and on a chunked
- * district no reward that couples the buildings inside a step (CLR_MARL: CL_EINVAL) -- cl_rollout_seq_f32 below runs the same K steps as a
- * launch sequence for everything else. */
+ * Limits of the fused kernels: no flexible loads, no CLD_F64_MAPS (CLD_F64_CHAIN is available), and on a chunked district no reward that
+ * couples the buildings inside a step (CLR_MARL: CL_EINVAL) -- cl_rollout_seq_f32 below runs the same K steps as a launch sequence for
+ * everything else.  This entry point takes no KPI planes and refuses CLD_KPI; the streaming KPI accumulators of a battery + PV district of up to
+ * 32 buildings are kept inside ONE fused launch by cl_rollout_seq_f32 under CLD_KPI | CLD_ROLLOUT_FUSED (cl_rollout_kpi_kernel, csrc/cl_rollout.h);
+ * thermal / outage and building-chunked districts keep their KPIs through the launch sequence only.  A geometry whose workgroup would need more
+ * than the CU's 160 KiB of LDS is refused with CL_EINVAL before anything is launched. */
 int cl_rollout_f32(const cl_dims* dims, const uint32_t* params, const float* ts, float* state,
                    const float* actions, int64_t act_stride_step, int64_t act_stride_col, int64_t act_stride_env,
                    const float* act_low, const float* act_high, uint64_t seed,
@@ -680,7 +691,10 @@ int cl_step_flex_f32(const cl_dims* dims, const uint32_t* params, const float* t
  * on-device policy a = low + u (high - low), u = cl_philox_uniform(seed, env, column, t), generated four steps at a time into the
  * scratch planes `policy_actions` [4][n_act_cols][n_env] (required then; n_env a multiple of 4).
  * `flex`, `kpi_bldg`, `kpi_env` are nullable; `ret_env` [n_env] (optional) accumulates the district reward; out_bldg / out_env
- * hold the LAST step's values. */
+ * hold the LAST step's values.
+ * With CLD_ROLLOUT_FUSED in dims->flags (ABI 9) the same arguments run as ONE fused launch instead -- cl_rollout_kpi_kernel when CLD_KPI is set
+ * (kpi_bldg / kpi_env required), cl_rollout_f32 otherwise -- or the call returns CL_EINVAL naming what the fused kernels do not cover (see the
+ * flag); it never degrades to the launch sequence.  `policy_actions` may then be NULL. */
 int cl_rollout_seq_f32(const cl_dims* dims, const uint32_t* params, const float* ts, float* state,
                        const float* actions, int64_t act_stride_step, int64_t act_stride_col, int64_t act_stride_env,
                        const float* act_low, const float* act_high, uint64_t seed, float* policy_actions,

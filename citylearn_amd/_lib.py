@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import subprocess
 from pathlib import Path
 
@@ -16,6 +17,7 @@ from . import abi
 PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / 'libcitylearn_amd.so'
 TUNE_LIB_PATH = PKG / 'libcitylearn_amd_tune.so'
+POLICY_LIB_PATH = PKG / 'libcitylearn_amd_policy.so'
 CSRC = PKG / 'csrc'
 # -amdgpu-mfma-vgpr-form: MFMA accumulators stay in VGPRs (gfx950's register file is unified), which removes the
 # v_accvgpr_read copies in front of the LSTM activations (64 per window step)
@@ -58,6 +60,14 @@ class Flex(ctypes.Structure):
                 ('ev_state', ctypes.c_void_p), ('wm_state', ctypes.c_void_p),
                 ('flex_out', ctypes.c_void_p), ('charger_out', ctypes.c_void_p), ('drift', ctypes.c_void_p),
                 ('seed', ctypes.c_uint64), ('weights', ctypes.c_float * 8)]
+
+
+class PolicyMLP(ctypes.Structure):
+    """``clpol_mlp`` (include/citylearn_amd_policy.h): the packed tables of a per-building MLP policy (`policy.MLPPolicy.pack`)."""
+    _fields_ = [('n_hidden', ctypes.c_int32), ('n_sets', ctypes.c_int32), ('flags', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('pre', ctypes.c_void_p), ('dep', ctypes.c_void_p), ('out', ctypes.c_void_p), ('set_of_block', ctypes.c_void_p),
+                ('net_reset', ctypes.c_void_p), ('act_low', ctypes.c_void_p), ('act_high', ctypes.c_void_p), ('sigma', ctypes.c_void_p),
+                ('seed', ctypes.c_uint64)]
 
 
 def _compile(sources, out: Path, deps, force: bool, verbose: bool) -> Path:
@@ -122,6 +132,50 @@ def load_tune() -> ctypes.CDLL:
     lib.cl_tune_mfma_bench.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     lib.cl_tune_mfma_bf16_probe.argtypes = [ctypes.c_void_p] * 4
     return lib
+
+
+# The closed-loop rollout (csrc/cl_policy.hip + cl_policy.h; include/citylearn_amd_policy.h): a product library of its own, so that the main
+# library's symbol list, structs and translation units stay what they are.  No SLP vectorisation, like the other rollout kernels.
+POLICY_HEADER = abi.HEADER.parent / 'citylearn_amd_policy.h'
+POLICY_SOURCES = [(CSRC / 'cl_policy.hip', ['-fno-slp-vectorize'])]
+POLICY_ABI_VERSION = int(re.search(r'#define\s+CLPOL_ABI_VERSION\s+(\d+)', POLICY_HEADER.read_text()).group(1))
+POLICY_SYMBOLS = sorted(set(re.findall(r'\b(clpol_\w+)\s*\(', abi._strip_comments(POLICY_HEADER.read_text()))))
+
+
+def build_policy(force: bool = False, verbose: bool = False) -> Path:
+    """Compile csrc/cl_policy.hip for gfx950 into the in-tree ``libcitylearn_amd_policy.so``."""
+    return _compile(POLICY_SOURCES, POLICY_LIB_PATH, sorted(CSRC.glob('*.hip')) + sorted(CSRC.glob('*.h')) + [abi.HEADER, POLICY_HEADER], force, verbose)
+
+
+_policy_lib = None
+
+
+def load_policy() -> ctypes.CDLL:
+    """``libcitylearn_amd_policy.so`` (after torch, like `load`); refuses a build from another version of either header."""
+    global _policy_lib
+    if _policy_lib is not None:
+        return _policy_lib
+    import torch  # noqa: F401
+    if not POLICY_LIB_PATH.exists():
+        raise EngineUnavailable(f'{POLICY_LIB_PATH} not found: the policy extension is not built (run __graft_entry__.build())')
+    lib = ctypes.CDLL(str(POLICY_LIB_PATH))
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    lib.clpol_abi_version.restype = ctypes.c_int
+    lib.clpol_core_abi_version.restype = ctypes.c_int
+    lib.clpol_last_error.restype = ctypes.c_char_p
+    lib.clpol_rollout_mlp_f32.restype = ctypes.c_int
+    lib.clpol_rollout_mlp_f32.argtypes = [ctypes.POINTER(Dims), vp, vp, vp, ctypes.POINTER(PolicyMLP), vp, vp, vp, vp, i32, i32, vp]
+    got, core = lib.clpol_abi_version(), lib.clpol_core_abi_version()
+    if got != POLICY_ABI_VERSION or core != abi.CL_ABI_VERSION:
+        raise EngineUnavailable(f'ABI mismatch: policy library {got} (core {core}), headers {POLICY_ABI_VERSION} (core {abi.CL_ABI_VERSION}); '
+                                'rebuild the extension')
+    _policy_lib = lib
+    return lib
+
+
+def check_policy(rc: int):
+    if rc != 0:
+        raise EngineError(rc, load_policy().clpol_last_error().decode(errors='replace'))
 
 
 _lib = None

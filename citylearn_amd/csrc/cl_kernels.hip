@@ -1520,7 +1520,9 @@ extern "C" __attribute__((visibility("hidden"))) int cl_tu_launch_rollout(int ke
 extern "C" __attribute__((visibility("hidden"))) int cl_tu_launch_lean(int vec, int nt, unsigned grid_x, unsigned grid_y, unsigned block, size_t lds,
                                                                        void* stream, const void* step_args);
 
-#ifdef CL_TU_NOSLP
+#if defined(CL_TU_POLICY)
+// (cl_policy.hip: the helpers and cl_rollout.h above are all it takes from this file -- its kernel, launcher and entry points are its own)
+#elif defined(CL_TU_NOSLP)
 extern "C" __attribute__((visibility("hidden"))) int cl_tu_launch_rollout(int key, int pin, unsigned grid_x, unsigned grid_y, unsigned block_threads, size_t lds,
                                                                           void* stream, const void* rollout_args) {
     const RolloutArgs& r = *static_cast<const RolloutArgs*>(rollout_args);       // the struct of the including translation unit: same source

@@ -490,6 +490,42 @@ class StepEngine:
         self._pending_t = None              # (a chunked fused rollout folds its last step's district sums itself)
         self.t = t0 + k_steps
 
+    def rollout_policy(self, k_steps: int, policy_tables, seed: int = 0, ret_env: Optional[torch.Tensor] = None,
+                       traj: Optional[torch.Tensor] = None, t0: Optional[int] = None):
+        """Fused K-step rollout driven by a CLOSED-LOOP policy in one launch (`clpol_rollout_mlp_f32`, ``libcitylearn_amd_policy.so``): every
+        building's storage action of every step is a one-hidden-layer tanh MLP of its observation, evaluated inside the kernel from the soc and
+        the previous net in its registers (`policy.MLPPolicy`; ``policy_tables`` = its `pack(...)` on this engine's device and tables).
+        Battery + PV districts of up to 32 buildings on the fp32 map or the float64 chain, no streaming KPIs (``kpi=True`` engines are refused by
+        the library: record ``traj`` and replay its action plane through ``rollout(actions=..., fused=True)``, see `policy`'s docstring).
+        ``seed`` keys the exploration noise (only drawn where the policy's sigma is not 0).  ``ret_env`` (``[n_env]``, optional) accumulates the
+        district reward over the K steps; ``traj`` (float32 ``[k_steps, CLPOL_NT, n_bldg, n_env]``, optional) records every step's action,
+        reward, net and soc planes.  A launch continues where the previous one (or `reset`) stopped: the previous net travels in ``out_bldg``."""
+        from . import policy as _policy
+        if self.flex is not None:
+            # (the library cannot see this: a battery + PV district with EV chargers / washing machines and a non-EV reward has CLD_LEAN set)
+            raise NotImplementedError('rollout_policy: districts with flexible loads (EV chargers / washing machines) are not covered by the policy '
+                                      'kernel -- it would leave their consumption out of net; use step() / capture_rollout')
+        lib = _lib.load_policy()
+        t0 = self.t if t0 is None else t0
+        pt = policy_tables
+        if (pt.n_rows, pt.n_bldg) != (self.n_ts_rows, self.n_bldg) or pt.pre.device != self.device:
+            raise ValueError(f'policy tables are packed for {pt.n_rows} table rows x {pt.n_bldg} buildings on {pt.pre.device}; this engine has '
+                             f'{self.n_ts_rows} x {self.n_bldg} on {self.device}')
+        if pt.act_low.numel() != self.n_act_cols:
+            raise ValueError(f'policy tables hold {pt.act_low.numel()} action columns, the engine {self.n_act_cols}')
+        if pt.set_of_block is not None and pt.set_of_block.numel() != -(-self.n_env // abi.CL_ROW0_BLOCK):
+            raise ValueError(f'set_of_block needs one entry per {abi.CL_ROW0_BLOCK} envs')
+        for name, x, shape in (('ret_env', ret_env, (self.n_env,)), ('traj', traj, (k_steps, _policy.CLPOL_NT, self.n_bldg, self.n_env))):
+            if x is not None and (x.dtype != torch.float32 or x.device != self.device or tuple(x.shape) != shape or not x.is_contiguous()):
+                raise ValueError(f'{name} must be a contiguous float32 tensor {shape} on {self.device}')
+        mlp = pt.struct(seed)
+        with torch.cuda.device(self.device):
+            _lib.check_policy(lib.clpol_rollout_mlp_f32(ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), ctypes.byref(mlp),
+                                                        _ptr(self.out_bldg), _ptr(self._out_env), _ptr(ret_env), _ptr(traj), int(t0), int(k_steps),
+                                                        self._stream()))
+        self._pending_t = None
+        self.t = t0 + k_steps
+
     def step_many(self, actions: torch.Tensor, t0: Optional[int] = None):
         """``actions.shape[0]`` consecutive env steps enqueued by ONE C call (`cl_rollout_seq_f32` with an open-loop action tensor
         ``[k, n_act_cols, n_env]``, any strides): the same launches as k calls of :meth:`step`, without k trips through Python and ctypes

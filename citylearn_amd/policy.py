@@ -1,0 +1,265 @@
+"""A closed-loop policy INSIDE the fused K-step rollout: a one-hidden-layer tanh MLP per building over that building's own observation
+vector, evaluated by `cl_rollout_policy_kernel` (csrc/cl_policy.h, ``libcitylearn_amd_policy.so``, include/citylearn_amd_policy.h).
+
+Inference of a GIVEN policy only -- no training, no agent: the weights come from the caller (a learner in torch, an evolution strategy that
+scores a population of controllers by return: one parameter set per block of ``abi.CL_ROW0_BLOCK`` envs).
+
+    policy = MLPPolicy(w1, b1, w2, b2, sigma=0.1)                  # w1 [n_sets, n_bldg, H, n_obs] over ObservationLayout.building_names[i]
+    env = VectorCityLearnEnv(schema, n_envs, observations='tensor', normalize_observations=True)
+    ret, traj = env.rollout_policy(policy, 24, seed=3, record=True)    # ONE launch; traj [24, CLPOL_NT, n_bldg, n_envs]
+
+Streaming KPIs are not kept by this kernel.  To score a recorded rollout with them, replay its actions open-loop on a ``kpi=True`` env
+(battery + PV districts whose storage action column of building b is column b, as in the 2022 schemas):
+
+    kenv = VectorCityLearnEnv(schema, n_envs, kpi=True)
+    kenv.rollout(24, actions=traj[:, policy.CLPOL_T_ACTION].contiguous(), fused=True)      # policy = this module
+    building_kpis, district_kpis = kenv.evaluate()
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+import re
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from . import _lib, abi
+from .observations import SRC_OUT, SRC_STATE, ObservationLayout
+
+# tanh x = (1 - e) / (1 + e), e = 2^(ACT_SCALE x): what the kernel evaluates with one v_exp_f32 + one v_rcp_f32 per hidden unit; folded into
+# the packed first layer (`pre`, `dep`)
+ACT_SCALE = -2.0 * math.log2(math.e)
+
+_H = re.sub(r'/\*.*?\*/', ' ', _lib.POLICY_HEADER.read_text(), flags=re.S)
+CONSTANTS = {m.group(1): int(m.group(2).rstrip('ulUL'), 0) for m in re.finditer(r'#define\s+(CLPOL_\w+)\s+(0x[0-9a-fA-F]+\w*|\d+)\b', _H)}
+CLPOL_NT, CLPOL_T_ACTION, CLPOL_T_REWARD, CLPOL_T_NET, CLPOL_T_SOC = (CONSTANTS[k] for k in ('CLPOL_NT', 'CLPOL_T_ACTION', 'CLPOL_T_REWARD',
+                                                                                             'CLPOL_T_NET', 'CLPOL_T_SOC'))
+CLPOL_NOISE_KEY, CLPOL_MAX_HIDDEN = CONSTANTS['CLPOL_NOISE_KEY'], CONSTANTS['CLPOL_MAX_HIDDEN']
+
+
+def building_columns(layout: ObservationLayout) -> List[List[int]]:
+    """For every building, the columns of the env's observation tensor that make up ITS observation vector, in the order of
+    ``layout.building_names[i]`` (a central agent's tensor keeps a shared observation once, at the first building that has it)."""
+    index = {}
+    for c, (i, k) in enumerate(layout.columns):
+        index.setdefault((i, k), c)
+    first = {}
+    for c, (i, k) in enumerate(layout.columns):
+        first.setdefault(k, c)
+    return [[index[(i, k)] if (i, k) in index else first[k] for k in names] for i, names in enumerate(layout.building_names)]
+
+
+def philox_uniform_host(seed: int, env, col: int, t: int) -> np.ndarray:
+    """`cl_philox_uniform(seed, env, col, t)` (csrc/cl_philox.h: Philox4x32-10, word t & 3 of block t >> 2, 24 bits -> [0, 1)) for an array of
+    env indices, in numpy -- tests/test_policy_host.py pins it to the library's function."""
+    M = np.uint64(0xFFFFFFFF)
+    c0 = np.asarray(env, dtype=np.uint64) & M
+    c1, c2, c3 = np.full_like(c0, int(col)), np.full_like(c0, int(t) >> 2), np.zeros_like(c0)
+    k0, k1 = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & M, (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & M
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    word = (c0, c1, c2, c3)[int(t) & 3]
+    return (word >> np.uint64(8)).astype(np.float64) / 16777216.0
+
+
+def noise_host(seed: int, env, col: int, t: int) -> np.ndarray:
+    """The kernel's standard normal of (global env index = env_offset + env, action column, step), replayed on the host in float64:
+    z = sqrt(-2 ln(u1 + 2^-25)) cos(2 pi u2) on draws 2 t and 2 t + 1 of the stream keyed seed ^ CLPOL_NOISE_KEY, with u1 + 2^-25 rounded to
+    float32 as the header defines it."""
+    key = (int(seed) ^ CLPOL_NOISE_KEY) & (2 ** 64 - 1)
+    u1 = philox_uniform_host(key, env, col, 2 * int(t)).astype(np.float32)
+    u2 = philox_uniform_host(key, env, col, 2 * int(t) + 1)
+    x = (u1 + np.float32(2.0 ** -25)).astype(np.float64)
+    return np.sqrt(-2.0 * np.log(x)) * np.cos(2.0 * np.pi * u2)
+
+
+class PolicyTables:
+    """`MLPPolicy.pack`'s result: the tables of `clpol_mlp` as float32 tensors on one device (the layouts of the header)."""
+
+    def __init__(self, pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, es_cols, low_bldg, high_bldg, sigma_bldg, version):
+        self.pre, self.dep, self.out, self.net_reset = pre, dep, out, net_reset
+        self.act_low, self.act_high, self.sigma, self.set_of_block = act_low, act_high, sigma, set_of_block
+        # host side, float64 / int64 [n_bldg]: every building's storage action column (-1: none), that column's bounds and sigma -- what
+        # `MLPPolicy.actions_host(..., tables=this)` evaluates the reference with
+        self.es_cols, self.low_bldg, self.high_bldg, self.sigma_bldg = es_cols, low_bldg, high_bldg, sigma_bldg
+        self.version = version                                           # `MLPPolicy.version` the tables were packed from
+        self.n_sets, self.n_rows, self.n_bldg, self.n_hidden = (int(x) for x in pre.shape)
+
+    def struct(self, seed: int) -> _lib.PolicyMLP:
+        p = lambda t: None if t is None else t.data_ptr()
+        return _lib.PolicyMLP(self.n_hidden, self.n_sets, 0, 0, p(self.pre), p(self.dep), p(self.out), p(self.set_of_block), p(self.net_reset),
+                              p(self.act_low), p(self.act_high), p(self.sigma), int(seed) & (2 ** 64 - 1))
+
+
+class MLPPolicy:
+    """``a = clamp(mid + half tanh(w2 . tanh(W1 obs + b1) + b2) + sigma z, low, high)`` per building, `obs` = the building's own observation
+    vector as the env defines it (``ObservationLayout.building_names[i]``: normalised or not, whatever the env was built with), (low, high) =
+    the bounds of the building's electrical-storage action, z ~ N(0, 1).
+
+    ``w1 [n_sets, n_bldg, H, n_obs]``, ``b1 [n_sets, n_bldg, H]``, ``w2 [n_sets, n_bldg, H]``, ``b2 [n_sets, n_bldg]`` (anything array-like;
+    kept in float64); a leading dimension of 1 broadcasts -- shared weights over the buildings and / or one parameter set.  ``H``: 4, 8, .. 32.
+    ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
+
+    **The packed tables are a snapshot.**  `pack` reads the weights once; `VectorCityLearnEnv.rollout_policy` caches the packed tables per
+    (policy object, `version`, episode window).  Change the weights through :meth:`update` (or assign the arrays and call :meth:`invalidate`):
+    both bump `version`, so the next `rollout_policy` packs again.  Arrays edited in place without that keep driving the OLD policy."""
+
+    def __init__(self, w1, b1, w2, b2, sigma=None):
+        self.w1, self.b1, self.w2, self.b2 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2))
+        if self.w1.ndim != 4 or self.b1.ndim != 3 or self.w2.ndim != 3 or self.b2.ndim != 2:
+            raise ValueError('w1 [n_sets, n_bldg, H, n_obs], b1 [n_sets, n_bldg, H], w2 [n_sets, n_bldg, H], b2 [n_sets, n_bldg]')
+        self.n_hidden, self.n_obs = int(self.w1.shape[2]), int(self.w1.shape[3])
+        if self.n_hidden % 4 or not 4 <= self.n_hidden <= CLPOL_MAX_HIDDEN:
+            raise ValueError(f'H={self.n_hidden}: the policy kernel takes 4, 8, .. {CLPOL_MAX_HIDDEN} hidden units')
+        if self.b1.shape[2] != self.n_hidden or self.w2.shape[2] != self.n_hidden:
+            raise ValueError('b1 / w2 disagree with w1 about H')
+        self.n_sets = max(x.shape[0] for x in (self.w1, self.b1, self.w2, self.b2))
+        self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
+        self.version = 0
+
+    def invalidate(self) -> None:
+        """Tell the caches that the weights changed (see the class docstring)."""
+        self.version += 1
+
+    def update(self, w1=None, b1=None, w2=None, b2=None, sigma=None) -> None:
+        """Replace some of the weight arrays (same shapes) and / or sigma, and bump `version`: the learner's step between two rollouts."""
+        for name, v in (('w1', w1), ('b1', b1), ('w2', w2), ('b2', b2)):
+            if v is not None:
+                v = np.asarray(v, dtype=np.float64)
+                if v.shape != getattr(self, name).shape:
+                    raise ValueError(f'{name}: shape {v.shape} != {getattr(self, name).shape}')
+                setattr(self, name, v)
+        if sigma is not None:
+            self.sigma = np.asarray(sigma, dtype=np.float64)
+        self.invalidate()
+
+    def _full(self, n_bldg: int):
+        S, H = self.n_sets, self.n_hidden
+        try:
+            return (np.broadcast_to(self.w1, (S, n_bldg, H, self.n_obs)), np.broadcast_to(self.b1, (S, n_bldg, H)),
+                    np.broadcast_to(self.w2, (S, n_bldg, H)), np.broadcast_to(self.b2, (S, n_bldg)))
+        except ValueError as e:
+            raise ValueError(f'the weights do not broadcast to {S} sets x {n_bldg} buildings: {e}') from None
+
+    # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
+    def actions_host(self, obs_vectors, noise=None, tables: Optional[PolicyTables] = None, low=None, high=None, sigma_bldg=None,
+                     set_index: int = 0) -> np.ndarray:
+        """float64 numpy evaluation of the plain MLP: ``obs_vectors [..., n_bldg, n_obs]`` -> actions ``[..., n_bldg]``.  ``noise``: the
+        standard normals z (same shape as the result; `noise_host` replays the kernel's), scaled by each building's sigma.  The bounds of the
+        buildings' storage actions and their sigmas (``[n_bldg]`` each) come from ``tables`` (a `pack` result: `low_bldg`, `high_bldg`,
+        `sigma_bldg`) or from the arguments; without either: -1 / 1 and the policy's scalar sigma.  Nothing is remembered between calls."""
+        x = np.asarray(obs_vectors, dtype=np.float64)
+        n_bldg = x.shape[-2]
+        w1, b1, w2, b2 = (v[set_index] for v in self._full(n_bldg))
+        pick = lambda arg, attr, default: np.asarray(arg if arg is not None else getattr(tables, attr) if tables is not None else default, dtype=np.float64)
+        lo, hi = pick(low, 'low_bldg', -1.0), pick(high, 'high_bldg', 1.0)
+        h = np.tanh(np.einsum('bjc,...bc->...bj', w1, x) + b1)
+        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('bj,...bj->...b', w2, h) + b2)
+        if noise is not None:
+            if sigma_bldg is None and tables is None and self.sigma is not None and self.sigma.ndim:
+                raise ValueError('a per-column sigma needs `tables` (or `sigma_bldg`): which column drives which building')
+            sg = pick(sigma_bldg, 'sigma_bldg', 0.0 if self.sigma is None or self.sigma.ndim else float(self.sigma))
+            a = a + sg * np.asarray(noise, dtype=np.float64)
+        return np.clip(a, lo, hi)
+
+    def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
+        """The same MLP (no noise) written in torch over the env's observation TENSOR (``observations='tensor'``): returns
+        ``f(obs [n_envs, n_obs_total], i=None) -> actions [n_act_cols, n_envs]`` -- a `VectorCityLearnEnv.capture_rollout` policy; what
+        `rollout_policy` replaces with one launch, and what the tests compare it with."""
+        cols = building_columns(layout)
+        n_bldg = len(cols)
+        w1, b1, w2, b2 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(n_bldg))
+        idx = torch.as_tensor(np.array([c + [c[0]] * (self.n_obs - len(c)) for c in cols]), device=device)
+        mask = torch.as_tensor(np.array([[1.0] * len(c) + [0.0] * (self.n_obs - len(c)) for c in cols]), dtype=dtype, device=device)
+        params = np.ascontiguousarray(tab.params).view(np.int32)
+        es = params[:, abi.CLP_ACT_ELEC_STO].astype(np.int64)
+        n_act = int(params[:, abi.CLP_ACT_COOL_STO:abi.CLP_ACT_COH_DEV + 1].max()) + 1
+        low, high = layout.spec.action_limits()
+        driven = np.nonzero(es >= 0)[0]
+        lo = torch.as_tensor(np.asarray(low)[es[driven]], dtype=dtype, device=device)
+        hi = torch.as_tensor(np.asarray(high)[es[driven]], dtype=dtype, device=device)
+        rows, drv = torch.as_tensor(es[driven], device=device), torch.as_tensor(driven, device=device)
+
+        def f(obs, i=None):
+            x = obs.to(dtype)[:, idx] * mask                                     # [E, B, n_obs]
+            h = torch.tanh(torch.einsum('bjc,ebc->ebj', w1, x) + b1)
+            o = torch.tanh((w2 * h).sum(dim=2) + b2)[:, drv]                     # [E, driven]
+            a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
+            out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
+            out[rows] = a.t().to(torch.float32)
+            return out
+        return f
+
+    # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
+    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None) -> PolicyTables:
+        """Split the first layer along the observation tables of `layout` over the episode tables `tab` (``layout.episode(tab,
+        reset_table=True)``): the env-independent columns of every table row go into ``pre`` (one matmul in float64 on `device`, rounded
+        once), the ``col_scale`` of the two env-dependent columns -- the building's own ``electrical_storage_soc`` and
+        ``net_electricity_consumption`` -- into ``dep``, their table offsets into ``pre``.  A building observation fed by anything else on the
+        device raises ``ValueError`` naming the column.  ``set_of_block``: the parameter set of every block of ``abi.CL_ROW0_BLOCK`` envs."""
+        obs = layout.episode(tab, reset_table=True)
+        cols = building_columns(layout)
+        n_bldg, T = len(cols), int(obs.table.shape[0])
+        if any(len(c) > self.n_obs for c in cols) or not any(len(c) == self.n_obs for c in cols):
+            raise ValueError(f'w1 takes {self.n_obs} observations, the buildings have {sorted(set(len(c) for c in cols))}')
+        w1, b1, w2, b2 = self._full(n_bldg)
+        S, H = self.n_sets, self.n_hidden
+        table = obs.table.copy()
+        x = np.zeros((T, n_bldg, self.n_obs))
+        scale = np.zeros((n_bldg, 2, self.n_obs))                        # [b][soc | net][position in the building's vector]
+        net_reset = np.zeros((T, n_bldg))
+        for i, bcols in enumerate(cols):
+            for j, c in enumerate(bcols):
+                name = f'{layout.columns[c][1]!r} of building {i} (column {c})'
+                src = int(obs.col_src[c])
+                if src < 0:
+                    # env-independent: the reset observation of an episode that starts at row r must show the table's value
+                    if T > 1 and not np.array_equal(obs.reset_table[1:, c], table[1:, c]):
+                        raise ValueError(f'observation {name} is reset to a value its table row does not hold (observation_mode="reference"?): '
+                                         'the policy kernel reads the tables of observation_mode="current"')
+                    x[:, i, j] = table[:, c]
+                    continue
+                kind, plane, b = src >> 28, (src >> 20) & 0xFF, src & 0xFFFFF
+                which = 0 if (kind, plane) == (SRC_STATE, abi.CLS_B_SOC) else 1 if (kind, plane) == (SRC_OUT, abi.CLO_NET) else None
+                if which is None or b != i or layout.columns[c][0] != i:
+                    raise ValueError(f'observation {name} is fed by device plane (kind {kind}, plane {plane}, building {b}): the policy kernel '
+                                     "only has the building's own electrical_storage_soc (CLS_B_SOC) and net_electricity_consumption (CLO_NET)")
+                offset = table[1:, c] if T > 1 else np.zeros(1)
+                if np.ptp(offset) != 0.0:
+                    raise ValueError(f'observation {name}: a table offset that changes with the row')
+                x[:, i, j] = offset[0]
+                scale[i, which, j] = float(obs.col_scale[c])
+                if which == 1 and scale[i, 1, j] != 0.0:
+                    net_reset[:, i] = (obs.reset_table[:, c] - offset[0]) / scale[i, 1, j]
+        dev = torch.device(device)
+        f64 = lambda v: torch.from_numpy(np.array(v, dtype=np.float64)).to(dev)
+        pre = (torch.einsum('sbjc,tbc->stbj', f64(w1), f64(x)) + f64(b1)[:, None]) * ACT_SCALE
+        dep = torch.einsum('sbjc,bkc->sbkj', f64(w1), f64(scale)) * ACT_SCALE
+        out = torch.cat([f64(w2), f64(b2)[:, :, None]], dim=2)
+        es = np.ascontiguousarray(tab.params).view(np.int32)[:, abi.CLP_ACT_ELEC_STO].astype(np.int64)
+        n_act = int(np.ascontiguousarray(tab.params).view(np.int32)[:, abi.CLP_ACT_COOL_STO:abi.CLP_ACT_COH_DEV + 1].max()) + 1
+        low, high = layout.spec.action_limits()
+        if len(low) != n_act:
+            raise ValueError(f'{len(low)} action limits for {n_act} action columns')
+        low_bldg = np.where(es >= 0, np.asarray(low, dtype=np.float64)[np.maximum(es, 0)], -1.0)
+        high_bldg = np.where(es >= 0, np.asarray(high, dtype=np.float64)[np.maximum(es, 0)], 1.0)
+        sigma = None
+        if self.sigma is not None:
+            sigma = np.full(n_act, float(self.sigma)) if self.sigma.ndim == 0 else self.sigma
+            if sigma.shape != (n_act,) or np.any(sigma < 0):
+                raise ValueError(f'sigma: a non-negative scalar or [{n_act}] (one per action column)')
+        f32 = lambda v: None if v is None else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev)
+        sob = None
+        if set_of_block is not None:
+            sob = np.asarray(set_of_block, dtype=np.int64).reshape(-1)
+            if sob.min() < 0 or sob.max() >= S:
+                raise ValueError(f'set_of_block outside [0, {S})')
+            sob = torch.from_numpy(sob.astype(np.int32)).to(dev)
+        return PolicyTables(pre.to(torch.float32).contiguous(), dep.to(torch.float32).contiguous(), out.to(torch.float32).contiguous(),
+                            f32(net_reset), f32(low), f32(high), f32(sigma), sob, es, low_bldg, high_bldg,
+                            np.zeros(n_bldg) if sigma is None else np.where(es >= 0, np.asarray(sigma, dtype=np.float64)[np.maximum(es, 0)], 0.0),
+                            self.version)

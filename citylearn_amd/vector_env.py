@@ -413,6 +413,41 @@ class VectorCityLearnEnv:
         self._t += k_steps
         return ret
 
+    def rollout_policy(self, policy, k_steps: int, seed: int = 0, record: bool = False, set_of_block=None):
+        """Advance ``k_steps`` steps in ONE launch with a closed-loop `policy.MLPPolicy` in the loop (`StepEngine.rollout_policy`): each
+        building's storage action is the MLP of the observation vector this env would hand out for it (``observation_names`` of the building --
+        normalised or not as the env was built; an env built with ``observations='planes'`` uses the plain ``'current'`` layout).  Returns the
+        district reward summed over the steps ``[n_envs]``, with ``record=True`` also the trajectory ``[k_steps, CLPOL_NT, n_bldg, n_envs]``
+        (`policy.CLPOL_T_ACTION / _REWARD / _NET / _SOC`).  ``set_of_block``: which of the policy's parameter sets drives each block of
+        ``abi.CL_ROW0_BLOCK`` envs (a population of controllers in one launch).  The tables are packed once per (policy object, its
+        `version`, episode window) and cached: **change a policy's weights through `MLPPolicy.update()` / `invalidate()`**, arrays edited in
+        place keep driving the old tables.  Same episode-end and stage / plugin checks as :meth:`rollout`; battery + PV districts without streaming KPIs."""
+        if self.stage is not None or self._plugin is not None:
+            raise NotImplementedError('rollout_policy() needs a district without the LSTM temperature stage and a fused reward; use step()')
+        if self.engine.flex is not None:
+            raise NotImplementedError('rollout_policy() does not cover districts with flexible loads (EV chargers / washing machines); use step()')
+        if self._t + k_steps > self.time_steps - 1:
+            raise RuntimeError(f'{k_steps} steps from t={self._t} run past the episode end ({self.time_steps - 1} steps)')
+        from . import policy as _policy
+        e = self.engine
+        sob = None if set_of_block is None else tuple(int(x) for x in np.asarray(set_of_block).reshape(-1))
+        key = (id(policy), int(policy.version), id(e), int(self.tables.start), int(self.tables.end), sob)
+        cache = getattr(self, '_policy_tables', None)
+        if cache is None:
+            cache = self._policy_tables = {}
+        if key not in cache:
+            layout = self.layout
+            if layout is None:
+                from .observations import ObservationLayout
+                layout = ObservationLayout(self.spec, 'current', False, self.reference_quirks)
+            cache.clear()                                     # (one live entry: tables of another window or engine are stale)
+            cache[key] = (policy, policy.pack(layout, self.tables, device=self.device, set_of_block=sob))
+        ret = torch.zeros(self.n_envs, dtype=torch.float32, device=self.device)
+        traj = torch.empty((k_steps, _policy.CLPOL_NT, e.n_bldg, self.n_envs), dtype=torch.float32, device=self.device) if record else None
+        e.rollout_policy(k_steps, cache[key][1], seed=seed, ret_env=ret, traj=traj, t0=self._t)
+        self._t += k_steps
+        return (ret, traj) if record else ret
+
     def evaluate(self):
         """Per-env KPI ratios of `CityLearnEnv.evaluate` (citylearn.py:1136-1323) from the on-device streaming
         accumulators (construct with ``kpi=True``).  Returns ``(building, district)`` dicts of tensors."""

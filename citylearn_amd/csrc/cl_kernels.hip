@@ -1998,7 +1998,8 @@ static int rollout_fused(const cl_dims* dims, const uint32_t* params, const floa
     r.t0 = t0; r.k_steps = k_steps;
     // two buildings per wave; envs per lane as cl_rollout_f32 picks them (128-env workgroups in nearly full rounds of one per CU)
     a.nw = tun.nw ? tun.nw : (dims->n_bldg + 1) / 2;
-    if (a.nw * 2 < dims->n_bldg || a.nw < 1 || a.nw > 16) return fail(CL_EINVAL, "bad nw %d", a.nw);
+    // (nw > n_bldg: a wave without any building would read its parameter row -- row `w` -- past the end of the table)
+    if (a.nw * 2 < dims->n_bldg || a.nw < 1 || a.nw > 16 || a.nw > dims->n_bldg) return fail(CL_EINVAL, "bad nw %d", a.nw);
     const long long wg2 = (dims->n_env + 127) / 128, rounds2 = (wg2 + 255) / 256;
     const bool full_rounds = dims->n_env >= 32768 && wg2 * 100 >= rounds2 * 256 * 85;
     const int vec = tun.vec ? tun.vec : (((actions == nullptr || act_stride_env == 1) && full_rounds) ? 2 : 1);

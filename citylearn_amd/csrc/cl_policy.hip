@@ -106,7 +106,8 @@ int clpol_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const flo
     p.traj = traj; p.n_rows = dims->n_ts_rows ? dims->n_ts_rows : dims->n_steps; p.n_hidden = mlp->n_hidden;
     // the lean rollout's geometry: two buildings per wave, two envs per lane where the 128-env workgroups come in (nearly) full rounds of one per CU
     a.nw = tun.nw ? tun.nw : (dims->n_bldg + 1) / 2;
-    if (a.nw * 2 < dims->n_bldg || a.nw < 1 || a.nw > 16) return fail(CL_EINVAL, "bad nw %d", a.nw);
+    // (nw > n_bldg: a wave without any building would read its parameter row -- row `w` -- past the end of the table)
+    if (a.nw * 2 < dims->n_bldg || a.nw < 1 || a.nw > 16 || a.nw > dims->n_bldg) return fail(CL_EINVAL, "bad nw %d", a.nw);
     const long long wg2 = (dims->n_env + 127) / 128, rounds2 = (wg2 + 255) / 256;
     const bool full_rounds = dims->n_env >= 32768 && wg2 * 100 >= rounds2 * 256 * 85;
     const int vec = tun.vec ? tun.vec : (full_rounds ? 2 : 1);

@@ -330,8 +330,9 @@ __global__ void __launch_bounds__(1024) cl_rollout_kernel(const RolloutArgs r) {
 // step writes another slot; the fold's trailing barrier protects the wrap).  The baseline series' samples -- sum over the buildings, in building
 // order, of the net without the battery -- take the same route: lane 0 of every wave parks its buildings' values in [S][32], the workgroup's
 // last thread folds them (cl_step_lean_kpi_kernel's `base_writer`).
-// LDS per workgroup: 4 x (S nw tile + 12 tile + 16 + 32 S) bytes -- 44 080 at 17 buildings (nw = 9) and two envs per lane, 72 752 at the
-// largest geometry (nw = 16, two envs per lane); the host refuses anything beyond the CU's 160 KiB before it launches.  The last step's
+// LDS per workgroup: 4 x (S nw tile + 12 tile + 16 + 4 x 32 S + 5 x 32) bytes (rollout_kpi_lds_floats) -- 47 808 at 17 buildings (nw = 9) and two
+// envs per lane, 76 480 at the largest geometry (nw = 16, two envs per lane; from nw = 14 at two envs per lane the launch has to opt into more
+// than 64 KiB: tests/test_gpu_rollout_geometry.py); the host refuses anything beyond the CU's 160 KiB before it launches.  The last step's
 // district reduction ([nw][NQ][tile]) and the return rows alias the ring (S >= NQ).
 // Instantiations: two buildings per wave (what every lean district of up to 32 buildings fits into, and the only form of the plain kernel that
 // exists for the float64 chain), one and two envs per lane (the host picks as cl_rollout_f32 does), PREC 0 and 2; curve parameters pinned.

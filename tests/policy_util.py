@@ -28,26 +28,31 @@ def make_policy(layout: ObservationLayout, H: int, n_sets: int = 1, seed: int = 
 
 class HostObservations:
     """Observation vectors [E, n_bldg, n_obs] of a batch at table row r from soc / previous-net planes [n_bldg, E], float64: the arithmetic of
-    `ObservationTables.host_row` (row + plane * col_scale for the env-dependent columns; row 0 / the reset table as they are), vectorised."""
+    `ObservationTables.host_row` (row + plane * col_scale for the env-dependent columns; row 0 / the reset table as they are), vectorised.
+    A building whose own vector is shorter than `n_obs` (the longest one) is padded at the end, and the padding is multiplied by zero -- what
+    `MLPPolicy.pack` feeds the first layer's trailing weights of such a building (its `x` / `scale` rows stay 0 there)."""
 
     def __init__(self, layout: ObservationLayout, tab):
         self.obs = layout.episode(tab, reset_table=True)
         self.cols = building_columns(layout)
         self.n_obs = max(len(c) for c in self.cols)
-        assert all(len(c) == self.n_obs for c in self.cols)
-        self.idx = np.array(self.cols)                                         # [B, n_obs]
+        self.lengths = np.array([len(c) for c in self.cols])
+        self.idx = np.array([c + [c[0]] * (self.n_obs - len(c)) for c in self.cols])          # [B, n_obs] (padding: any valid column, masked)
+        self.mask = np.arange(self.n_obs)[None, :] < self.lengths[:, None]                    # [B, n_obs]
         src = self.obs.col_src[self.idx]
         kind, plane = src >> 28, (src >> 20) & 0xFF
-        self.is_soc = (src >= 0) & (kind == SRC_STATE) & (plane == abi.CLS_B_SOC)
-        self.is_net = (src >= 0) & (kind == SRC_OUT) & (plane == abi.CLO_NET)
-        assert np.array_equal(src >= 0, self.is_soc | self.is_net)
+        self.is_soc = self.mask & (src >= 0) & (kind == SRC_STATE) & (plane == abi.CLS_B_SOC)
+        self.is_net = self.mask & (src >= 0) & (kind == SRC_OUT) & (plane == abi.CLO_NET)
+        assert np.array_equal(self.mask & (src >= 0), self.is_soc | self.is_net)
         self.scale = self.obs.col_scale[self.idx].astype(np.float64)
 
     def at(self, r: int, soc, net, reset: bool = False):
         """`reset`: the observation `reset()` returns for an episode that starts at row r (soc / net not read)."""
+        E = np.shape(soc)[1]
         if reset:
-            return np.broadcast_to((self.obs.reset_table[r] if r else self.obs.table[0])[self.idx][None], (np.shape(soc)[1],) + self.idx.shape).copy()
-        x = np.broadcast_to(self.obs.table[r][self.idx][None], (np.shape(soc)[1],) + self.idx.shape).copy()
+            row = (self.obs.reset_table[r] if r else self.obs.table[0])[self.idx] * self.mask
+            return np.broadcast_to(row[None], (E,) + self.idx.shape).copy()
+        x = np.broadcast_to((self.obs.table[r][self.idx] * self.mask)[None], (E,) + self.idx.shape).copy()
         soc, net = np.asarray(soc, dtype=np.float64).T[:, :, None], np.asarray(net, dtype=np.float64).T[:, :, None]
         x += np.where(self.is_soc, soc * self.scale, 0.0) + np.where(self.is_net, net * self.scale, 0.0)
         return x

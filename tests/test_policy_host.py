@@ -117,8 +117,12 @@ def test_refusals_name_their_cause_before_any_hip_call(lib):
     assert _call(lib, _dims(), t0=-1) == ERANGE and _call(lib, _dims(), k_steps=-1) == ERANGE
     tun = _lib.Tuning(vec=4)
     assert _call(lib, _dims(tuning=ctypes.pointer(tun))) == EINVAL and '4 envs per lane' in err()
-    tun = _lib.Tuning(nw=8)
+    tun = _lib.Tuning(nw=8)                              # 17 buildings: 8 waves x 2 buildings < 17
     assert _call(lib, _dims(tuning=ctypes.pointer(tun))) == EINVAL and 'bad nw 8' in err()
+    # ... and more waves than buildings: a wave without any building would read parameter row `w` and `net_reset[.. + w]` past the tables' end
+    assert _call(lib, _dims(n_bldg=5, tuning=ctypes.pointer(tun))) == EINVAL and 'bad nw 8' in err()
+    tun = _lib.Tuning(nw=2)
+    assert _call(lib, _dims(n_bldg=1, tuning=ctypes.pointer(tun))) == EINVAL and 'bad nw 2' in err()
 
 
 # ---- 3. generated code ----------------------------------------------------------------------------------------------------------------
@@ -230,29 +234,99 @@ def test_packer_refuses_observations_it_cannot_feed():
 
 
 # ---- 5. conditioning ------------------------------------------------------------------------------------------------------------------
+def _conditioning(spec, H, K=48, E=4):
+    """{'soc' | 'net': worst deviation of the perturbed loop in units of the plain bar}, the action tolerance and the reference trajectory."""
+    tab = spec.episode_tables(0)
+    layout = ObservationLayout(spec, 'current', True)
+    pol = make_policy(layout, H, seed=H)
+    pt = pol.pack(layout, tab)
+    ref = host_closed_loop(spec, tab, layout, pol, pt, K, E)
+    hobs = HostObservations(layout, tab)
+    x = np.stack([hobs.at(t, ref['soc'][t - 1], ref['net'][t - 1]) for t in range(1, K)])
+    tol = 4.0 * f32_torch_deviation(pol, x, pt)
+    got = host_closed_loop(spec, tab, layout, pol, pt, K, E, perturb=tol, round_f32=True)
+    return {k: float((np.abs(got[k] - ref[k]) / (1e-4 + 1e-4 * np.abs(ref[k]))).max()) for k in ('soc', 'net')}, tol, ref, pt
+
+
 @pytest.mark.parametrize('H', [4, 16, 32])
 def test_closed_loop_is_well_conditioned(H):
     """The CPU oracle stepped K = 48 from reset on g2022_all with `actions_host` in float64, against the same loop with every action rounded
     through float32 and moved by the teacher-forced tolerance of the GPU test -- 4 x the worst deviation of a float32 torch evaluation of the
     unsplit MLP on this trajectory's own observations: soc and net must stay within 0.1 x (1e-4 + 1e-4 |ref|).  That makes the free-running GPU
     comparison (test_gpu_policy_rollout.py, (c)) a test of the kernel and not of a chaotic loop; it fixes policy_util's weight scale."""
-    spec = golden('g2022_all').spec()
-    tab = spec.episode_tables(0)
-    layout = ObservationLayout(spec, 'current', True)
-    pol = make_policy(layout, H, seed=H)
-    pt = pol.pack(layout, tab)
-    K, E = 48, 4
-    ref = host_closed_loop(spec, tab, layout, pol, pt, K, E)
-    hobs = HostObservations(layout, tab)
-    x = np.stack([hobs.at(t, ref['soc'][t - 1], ref['net'][t - 1]) for t in range(1, K)])
-    tol = 4.0 * f32_torch_deviation(pol, x, pt)
+    err, tol, ref, _ = _conditioning(golden('g2022_all').spec(), H)
     assert 0 < tol < 1e-5, tol
-    got = host_closed_loop(spec, tab, layout, pol, pt, K, E, perturb=tol, round_f32=True)
     assert np.abs(ref['action']).max() > 0.05 and np.ptp(ref['action']) > 0.1             # a policy that does something
     for k in ('soc', 'net'):
-        err = np.abs(got[k] - ref[k]) / (1e-4 + 1e-4 * np.abs(ref[k]))
-        print(f'H={H} {k}: worst {err.max():.4f} x (1e-4 + 1e-4 |ref|), action tolerance {tol:.3e}')
-        assert err.max() < 0.1, (k, err.max())
+        print(f'H={H} {k}: worst {err[k]:.4f} x (1e-4 + 1e-4 |ref|), action tolerance {tol:.3e}')
+        assert err[k] < 0.1, (k, err[k])
+
+
+@pytest.mark.parametrize('H', [4, 16, 32])
+@pytest.mark.parametrize('name', ['b1', 'b32', 'het17'])
+def test_closed_loop_is_well_conditioned_on_the_geometry_districts(name, H):
+    """The same condition, same weight scale and K = 48, on the districts of tests/district_util.py that the free-running GPU comparison of
+    tests/test_gpu_rollout_geometry.py runs beyond g2022_all (the scale was chosen on the 17-building district only): one building, 32 jittered
+    ones, and het17 with its undriven buildings (action 0, not perturbed: no column) and its zero-padded observation vector."""
+    from district_util import HET_UNDRIVEN, district
+    err, tol, ref, pt = _conditioning(district(name), H)
+    assert 0 < tol < 1e-5, tol
+    driven = pt.es_cols >= 0
+    # a policy that does something: as on g2022_all where there are many buildings; b1 has ONE seeded draw of weights per H (|action| 0.016 at
+    # H = 4), where all the closed loop needs is an action that is not 0 and moves with the observations
+    act = ref['action'][:, driven]
+    assert (np.abs(act).max() > 0.05 and np.ptp(act) > 0.1) if name != 'b1' else (np.abs(act).max() > 1e-3 and np.ptp(act) > 1e-4)
+    if name == 'het17':
+        assert sorted(np.nonzero(~driven)[0]) == sorted(HET_UNDRIVEN)
+    for k in ('soc', 'net'):
+        print(f'{name} H={H} {k}: worst {err[k]:.4f} x (1e-4 + 1e-4 |ref|), action tolerance {tol:.3e}')
+        assert err[k] < 0.1, (name, k, err[k])
+
+
+def test_ragged_observation_vectors_host_reference_equals_torch_policy():
+    """het17's building with the shorter observation vector: `MLPPolicy.pack` zero-pads it, `torch_policy` masks it, `HostObservations` pads
+    with zeros -- three statements of one thing.  In float64 on the CPU: (1) `actions_host` over `HostObservations` against `torch_policy` over
+    the env's observation tensor (`ObservationTables.host_row`), every building, at 1e-12; (2) the packed first layer `pre + dep x` of the ragged
+    building against `W1 x_padded + b1`, at the tables' own rounding (test_split_first_layer_equals_the_unsplit_one's bound).  The trailing
+    first-layer weights of that building are NOT zero, so a padding that let any table value through would show."""
+    from district_util import HET_SHORT_OBS, HET_UNDRIVEN, district
+    spec = district('het17')
+    tab = spec.episode_tables(0)
+    layout = ObservationLayout(spec, 'current', True)
+    cols = policy.building_columns(layout)
+    lengths = [len(c) for c in cols]
+    n_obs = max(lengths)
+    assert lengths[HET_SHORT_OBS] == n_obs - 1 and all(n == n_obs for i, n in enumerate(lengths) if i != HET_SHORT_OBS)
+    pol = make_policy(layout, 16, seed=6)
+    assert pol.n_obs == n_obs and np.abs(pol.w1[0, HET_SHORT_OBS, :, -1]).min() > 0
+    pt = pol.pack(layout, tab)
+    hobs = HostObservations(layout, tab)
+    assert hobs.n_obs == n_obs and not hobs.mask[HET_SHORT_OBS, -1] and hobs.mask.sum() == sum(lengths)
+    obs = layout.episode(tab, reset_table=True)
+    f = pol.torch_policy(layout, tab, 'cpu', dtype=torch.float64)
+    rng = np.random.RandomState(3)
+    B, E = len(cols), 6
+    pre, dep = pt.pre.numpy().astype(np.float64) / policy.ACT_SCALE, pt.dep.numpy().astype(np.float64) / policy.ACT_SCALE
+    driven = pt.es_cols >= 0
+    assert sorted(np.nonzero(~driven)[0]) == sorted(HET_UNDRIVEN)
+    for r in (1, 7, 100):
+        soc, net = rng.uniform(0, 1, (B, E)), rng.uniform(-5, 8, (B, E))
+        rows = []
+        for e in range(E):
+            state, out_bldg = np.zeros((abi.CL_NS, B)), np.zeros((abi.CL_NO, B))
+            state[abi.CLS_B_SOC], out_bldg[abi.CLO_NET] = soc[:, e], net[:, e]
+            rows.append(obs.host_row(r, state=state, out_bldg=out_bldg))
+        x = hobs.at(r, soc, net)                                                   # [E, B, n_obs]
+        assert np.all(x[:, HET_SHORT_OBS, -1] == 0.0)
+        want = f(torch.from_numpy(np.stack(rows))).numpy()                         # [n_act_cols, E] (float32 storage of float64 arithmetic)
+        got = pol.actions_host(x, tables=pt)                                       # [E, B]
+        assert want.shape == (int(driven.sum()), E)
+        np.testing.assert_allclose(got[:, driven].T, want[pt.es_cols[driven]], rtol=0, atol=2.0 ** -22)
+        b = HET_SHORT_OBS
+        for e in range(E):
+            unsplit = pol.w1[0, b] @ x[e, b] + pol.b1[0, b]
+            terms = np.stack([pre[0, r, b], dep[0, b, 0] * soc[b, e], dep[0, b, 1] * net[b, e]])
+            assert np.all(np.abs(terms.sum(axis=0) - unsplit) <= 2.0 ** -22 * np.abs(terms).sum(axis=0) + 1e-30), (r, e)
 
 
 def test_pack_is_a_snapshot_and_the_policy_keeps_no_state():

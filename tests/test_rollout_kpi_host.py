@@ -96,6 +96,13 @@ def test_fused_kpi_rollout_refuses_what_the_kernel_does_not_cover(lib):
     assert _call(lib, _dims(flags=base | (abi.CLR_EV << abi.CLD_REWARD_SHIFT))) == abi.CL_EINVAL and 'CLR_EV' in err()
     assert _call(lib, _dims(flags=base), t0=95) == abi.CL_ERANGE
     assert _call(lib, _dims(flags=base), policy=True, act_low=False) == abi.CL_ENULL and 'act_low' in err()
+    # launch-geometry overrides: fewer waves than ceil(n_bldg / 2), and more waves than buildings (a wave without any building would read
+    # parameter row `w` past the end of the table)
+    tun = _lib.Tuning(nw=8)
+    assert _call(lib, _dims(flags=base, tuning=ctypes.pointer(tun))) == abi.CL_EINVAL and 'bad nw 8' in err()
+    assert _call(lib, _dims(n_bldg=5, flags=base, tuning=ctypes.pointer(tun))) == abi.CL_EINVAL and 'bad nw 8' in err()
+    tun = _lib.Tuning(nw=2)
+    assert _call(lib, _dims(n_bldg=1, flags=base, tuning=ctypes.pointer(tun))) == abi.CL_EINVAL and 'bad nw 2' in err()
     # the flag without CLD_KPI forwards to cl_rollout_f32 -- whose own refusals apply -- and still never takes the launch sequence
     assert _call(lib, _dims(flags=abi.CLD_ROLLOUT_FUSED | abi.CLD_LEAN), flex=ctypes.byref(flex)) == abi.CL_EINVAL and 'flex != NULL' in err()
     assert _call(lib, _dims(flags=abi.CLD_ROLLOUT_FUSED | abi.CLD_LEAN | abi.CLD_F64_MAPS)) == abi.CL_EINVAL and 'CLD_F64_MAPS' in err()
@@ -129,3 +136,14 @@ def test_launch_sequence_validation_is_unchanged_without_the_flag(lib):
     assert seq(ctypes.byref(d), p, p, p, p, 0, 0, 1, p, p, 0, None, p, p, p, p, p, None, 95, 8, None) == abi.CL_ERANGE
     assert seq(ctypes.byref(d), p, p, p, p, 0, 0, 1, p, p, 0, None, p, p, p, p, p, None, -1, 8, None) == abi.CL_ERANGE
     assert seq(ctypes.byref(_dims(flags=flags | (9 << abi.CLD_REWARD_SHIFT))), p, p, p, p, 0, 0, 1, p, p, 0, None, p, p, p, p, p, None, 0, 8, None) == abi.CL_EINVAL
+
+
+def test_lds_request_of_the_largest_geometries():
+    """`rollout_kpi_lds_floats` with the header's constants: the figures the kernel's comment quotes, and which geometries have to opt into more
+    than 64 KiB of dynamic LDS (from nw = 14 at two envs per lane: 27 to 32 buildings; tests/test_gpu_rollout_geometry.py launches 31 and 32)."""
+    text = (_lib.CSRC / 'cl_rollout.h').read_text()
+    s, nb = (int(re.search(rf'constexpr int {k} = (\d+);', text).group(1)) for k in ('CL_RKPI_S', 'CL_RKPI_NB'))
+    assert re.search(r'return \(size_t\)CL_RKPI_S \* nw \* tile \+ \(size_t\)CLKE_PER_COND \* tile \+ 16 \+ \(size_t\)CL_RKPI_S \* 4 \* CL_RKPI_NB \+ 5 \* CL_RKPI_NB;', text)
+    lds = lambda nw, tile: 4 * (s * nw * tile + abi.CLKE_PER_COND * tile + 16 + s * 4 * nb + 5 * nb)
+    assert lds(16, 128) == 76480 and lds(9, 128) == 47808 and '76 480' in text and '47 808' in text
+    assert lds(16, 64) <= 65536 and lds(13, 128) <= 65536 < lds(14, 128) and lds(16, 128) <= 160 * 1024

@@ -18,6 +18,7 @@ PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / 'libcitylearn_amd.so'
 TUNE_LIB_PATH = PKG / 'libcitylearn_amd_tune.so'
 POLICY_LIB_PATH = PKG / 'libcitylearn_amd_policy.so'
+POLICY_KPI_LIB_PATH = PKG / 'libcitylearn_amd_policy_kpi.so'
 CSRC = PKG / 'csrc'
 # -amdgpu-mfma-vgpr-form: MFMA accumulators stay in VGPRs (gfx950's register file is unified), which removes the
 # v_accvgpr_read copies in front of the LSTM activations (64 per window step)
@@ -176,6 +177,59 @@ def load_policy() -> ctypes.CDLL:
 def check_policy(rc: int):
     if rc != 0:
         raise EngineError(rc, load_policy().clpol_last_error().decode(errors='replace'))
+
+
+# The closed-loop rollout that keeps the streaming KPIs (csrc/cl_policy_kpi.hip + cl_policy_kpi.h; include/citylearn_amd_policy_kpi.h): once more a
+# library of its own -- the policy library's export list, ABI version and kernel set stay what they are, like the main library's.
+POLICY_KPI_HEADER = abi.HEADER.parent / 'citylearn_amd_policy_kpi.h'
+POLICY_KPI_SOURCES = [(CSRC / 'cl_policy_kpi.hip', ['-fno-slp-vectorize'])]
+POLICY_KPI_ABI_VERSION = int(re.search(r'#define\s+CLPK_ABI_VERSION\s+(\d+)', POLICY_KPI_HEADER.read_text()).group(1))
+POLICY_KPI_SYMBOLS = sorted(set(re.findall(r'\b(clpk_\w+)\s*\(', abi._strip_comments(POLICY_KPI_HEADER.read_text()))))
+
+
+def build_policy_kpi(force: bool = False, verbose: bool = False) -> Path:
+    """Compile csrc/cl_policy_kpi.hip for gfx950 into the in-tree ``libcitylearn_amd_policy_kpi.so``."""
+    deps = sorted(CSRC.glob('*.hip')) + sorted(CSRC.glob('*.h')) + [abi.HEADER, POLICY_HEADER, POLICY_KPI_HEADER]
+    return _compile(POLICY_KPI_SOURCES, POLICY_KPI_LIB_PATH, deps, force, verbose)
+
+
+_policy_kpi_lib = None
+
+
+def load_policy_kpi() -> ctypes.CDLL:
+    """``libcitylearn_amd_policy_kpi.so`` (after torch, like `load`); refuses a build from another version of its own or the core header."""
+    global _policy_kpi_lib
+    if _policy_kpi_lib is not None:
+        return _policy_kpi_lib
+    import torch  # noqa: F401
+    if not POLICY_KPI_LIB_PATH.exists():
+        raise EngineUnavailable(f'{POLICY_KPI_LIB_PATH} not found: the policy KPI extension is not built (run __graft_entry__.build())')
+    lib = ctypes.CDLL(str(POLICY_KPI_LIB_PATH))
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    lib.clpk_abi_version.restype = ctypes.c_int
+    lib.clpk_core_abi_version.restype = ctypes.c_int
+    lib.clpk_last_error.restype = ctypes.c_char_p
+    lib.clpk_rollout_mlp_kpi_f32.restype = ctypes.c_int
+    lib.clpk_rollout_mlp_kpi_f32.argtypes = [ctypes.POINTER(Dims), vp, vp, vp, ctypes.POINTER(PolicyMLP), vp, vp, vp, vp, vp, vp, i32, i32, vp]
+    got, core = lib.clpk_abi_version(), lib.clpk_core_abi_version()
+    if got != POLICY_KPI_ABI_VERSION or core != abi.CL_ABI_VERSION:
+        raise EngineUnavailable(f'ABI mismatch: policy KPI library {got} (core {core}), headers {POLICY_KPI_ABI_VERSION} (core {abi.CL_ABI_VERSION}); '
+                                'rebuild the extension')
+    _policy_kpi_lib = lib
+    return lib
+
+
+def check_policy_kpi(rc: int):
+    if rc != 0:
+        raise EngineError(rc, load_policy_kpi().clpk_last_error().decode(errors='replace'))
+
+
+def policy_kpi_lds_bytes(nw: int, vec: int) -> int:
+    """Dynamic LDS of one `cl_rollout_policy_kpi_kernel` workgroup of ``nw`` waves at ``vec`` envs per lane: csrc/cl_policy_kpi.h's
+    `rollout_policy_kpi_lds_floats` -- the KPI kernel's ring [8][nw][tile], series [12][tile] + [16], baseline rows [8][4][32] + [5][32], then the
+    policy's staged rows [nw][2][3 x 32 + 8] (tests/test_policy_kpi_host.py holds it against the header's formula)."""
+    tile = 64 * vec
+    return 4 * (8 * nw * tile + 12 * tile + 16 + 8 * 4 * 32 + 5 * 32 + nw * 2 * (3 * 32 + 8))
 
 
 _lib = None

@@ -491,7 +491,7 @@ class StepEngine:
         self.t = t0 + k_steps
 
     def rollout_policy(self, k_steps: int, policy_tables, seed: int = 0, ret_env: Optional[torch.Tensor] = None,
-                       traj: Optional[torch.Tensor] = None, t0: Optional[int] = None):
+                       traj: Optional[torch.Tensor] = None, t0: Optional[int] = None, kpi: bool = False):
         """Fused K-step rollout driven by a CLOSED-LOOP policy in one launch (`clpol_rollout_mlp_f32`, ``libcitylearn_amd_policy.so``): every
         building's storage action of every step is a one-hidden-layer tanh MLP of its observation, evaluated inside the kernel from the soc and
         the previous net in its registers (`policy.MLPPolicy`; ``policy_tables`` = its `pack(...)` on this engine's device and tables).
@@ -499,13 +499,20 @@ class StepEngine:
         the library: record ``traj`` and replay its action plane through ``rollout(actions=..., fused=True)``, see `policy`'s docstring).
         ``seed`` keys the exploration noise (only drawn where the policy's sigma is not 0).  ``ret_env`` (``[n_env]``, optional) accumulates the
         district reward over the K steps; ``traj`` (float32 ``[k_steps, CLPOL_NT, n_bldg, n_env]``, optional) records every step's action,
-        reward, net and soc planes.  A launch continues where the previous one (or `reset`) stopped: the previous net travels in ``out_bldg``."""
+        reward, net and soc planes.  A launch continues where the previous one (or `reset`) stopped: the previous net travels in ``out_bldg``.
+
+        ``kpi=True`` (on an engine built with ``kpi=True``, otherwise `ValueError`) runs the same steps as ONE launch of
+        `cl_rollout_policy_kpi_kernel` (`clpk_rollout_mlp_kpi_f32`, ``libcitylearn_amd_policy_kpi.so``), which also keeps the streaming KPI
+        accumulators `evaluate()` / `state_dict()` read -- equal to the single-step path's on the recorded actions to ~1e-6 relative, like
+        ``rollout(fused=True)``.  ``kpi=False`` is the call above in every respect, its refusal of a ``kpi=True`` engine included."""
         from . import policy as _policy
+        if kpi and not self.kpi:
+            raise ValueError('rollout_policy(kpi=True) needs an engine built with kpi=True: this one keeps no KPI accumulators')
         if self.flex is not None:
             # (the library cannot see this: a battery + PV district with EV chargers / washing machines and a non-EV reward has CLD_LEAN set)
             raise NotImplementedError('rollout_policy: districts with flexible loads (EV chargers / washing machines) are not covered by the policy '
                                       'kernel -- it would leave their consumption out of net; use step() / capture_rollout')
-        lib = _lib.load_policy()
+        lib = _lib.load_policy_kpi() if kpi else _lib.load_policy()
         t0 = self.t if t0 is None else t0
         pt = policy_tables
         if (pt.n_rows, pt.n_bldg) != (self.n_ts_rows, self.n_bldg) or pt.pre.device != self.device:
@@ -520,9 +527,14 @@ class StepEngine:
                 raise ValueError(f'{name} must be a contiguous float32 tensor {shape} on {self.device}')
         mlp = pt.struct(seed)
         with torch.cuda.device(self.device):
-            _lib.check_policy(lib.clpol_rollout_mlp_f32(ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), ctypes.byref(mlp),
-                                                        _ptr(self.out_bldg), _ptr(self._out_env), _ptr(ret_env), _ptr(traj), int(t0), int(k_steps),
-                                                        self._stream()))
+            if kpi:
+                _lib.check_policy_kpi(lib.clpk_rollout_mlp_kpi_f32(
+                    ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), ctypes.byref(mlp), _ptr(self.out_bldg),
+                    _ptr(self._out_env), _ptr(ret_env), _ptr(traj), _ptr(self.kpi_bldg), _ptr(self.kpi_env), int(t0), int(k_steps), self._stream()))
+            else:
+                _lib.check_policy(lib.clpol_rollout_mlp_f32(ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), ctypes.byref(mlp),
+                                                            _ptr(self.out_bldg), _ptr(self._out_env), _ptr(ret_env), _ptr(traj), int(t0), int(k_steps),
+                                                            self._stream()))
         self._pending_t = None
         self.t = t0 + k_steps
 

@@ -8,8 +8,17 @@ scores a population of controllers by return: one parameter set per block of ``a
     env = VectorCityLearnEnv(schema, n_envs, observations='tensor', normalize_observations=True)
     ret, traj = env.rollout_policy(policy, 24, seed=3, record=True)    # ONE launch; traj [24, CLPOL_NT, n_bldg, n_envs]
 
-Streaming KPIs are not kept by this kernel.  To score a recorded rollout with them, replay its actions open-loop on a ``kpi=True`` env
-(battery + PV districts whose storage action column of building b is column b, as in the 2022 schemas):
+To score the controllers with CityLearn's KPIs, build the env with ``kpi=True`` and ask for them in the same call: ONE launch of
+`cl_rollout_policy_kpi_kernel` (csrc/cl_policy_kpi.h, ``libcitylearn_amd_policy_kpi.so``, include/citylearn_amd_policy_kpi.h) keeps the streaming
+accumulators next to the policy, and `evaluate()` works afterwards as after any other rollout -- no second env, no trajectory through memory:
+
+    kenv = VectorCityLearnEnv(schema, n_envs, observations='tensor', normalize_observations=True, kpi=True)
+    ret = kenv.rollout_policy(policy, 24, seed=3, kpi=True)
+    building_kpis, district_kpis = kenv.evaluate()
+
+``kpi=False`` (the default) is the launch without KPIs, which refuses a ``kpi=True`` env.  For envs built WITHOUT KPIs the route is the
+replay: record the rollout, then feed its action plane open-loop to a second, ``kpi=True`` env (battery + PV districts whose storage action
+column of building b is column b, as in the 2022 schemas):
 
     kenv = VectorCityLearnEnv(schema, n_envs, kpi=True)
     kenv.rollout(24, actions=traj[:, policy.CLPOL_T_ACTION].contiguous(), fused=True)      # policy = this module

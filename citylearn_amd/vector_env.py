@@ -413,7 +413,7 @@ class VectorCityLearnEnv:
         self._t += k_steps
         return ret
 
-    def rollout_policy(self, policy, k_steps: int, seed: int = 0, record: bool = False, set_of_block=None):
+    def rollout_policy(self, policy, k_steps: int, seed: int = 0, record: bool = False, set_of_block=None, kpi: bool = False):
         """Advance ``k_steps`` steps in ONE launch with a closed-loop `policy.MLPPolicy` in the loop (`StepEngine.rollout_policy`): each
         building's storage action is the MLP of the observation vector this env would hand out for it (``observation_names`` of the building --
         normalised or not as the env was built; an env built with ``observations='planes'`` uses the plain ``'current'`` layout).  Returns the
@@ -421,7 +421,12 @@ class VectorCityLearnEnv:
         (`policy.CLPOL_T_ACTION / _REWARD / _NET / _SOC`).  ``set_of_block``: which of the policy's parameter sets drives each block of
         ``abi.CL_ROW0_BLOCK`` envs (a population of controllers in one launch).  The tables are packed once per (policy object, its
         `version`, episode window) and cached: **change a policy's weights through `MLPPolicy.update()` / `invalidate()`**, arrays edited in
-        place keep driving the old tables.  Same episode-end and stage / plugin checks as :meth:`rollout`; battery + PV districts without streaming KPIs."""
+        place keep driving the old tables.  Same episode-end and stage / plugin checks as :meth:`rollout`; battery + PV districts.
+        ``kpi=True`` (an env built with ``kpi=True``, otherwise `ValueError`): the same launch also keeps the streaming KPI accumulators
+        (`cl_rollout_policy_kpi_kernel`), so `evaluate()` scores the controllers afterwards as after any other rollout.  ``kpi=False`` (the
+        default) is the launch without KPIs, which a ``kpi=True`` env is refused."""
+        if kpi and not self.kpi:
+            raise ValueError('rollout_policy(kpi=True) needs VectorCityLearnEnv(..., kpi=True): this env keeps no KPI accumulators')
         if self.stage is not None or self._plugin is not None:
             raise NotImplementedError('rollout_policy() needs a district without the LSTM temperature stage and a fused reward; use step()')
         if self.engine.flex is not None:
@@ -444,7 +449,7 @@ class VectorCityLearnEnv:
             cache[key] = (policy, policy.pack(layout, self.tables, device=self.device, set_of_block=sob))
         ret = torch.zeros(self.n_envs, dtype=torch.float32, device=self.device)
         traj = torch.empty((k_steps, _policy.CLPOL_NT, e.n_bldg, self.n_envs), dtype=torch.float32, device=self.device) if record else None
-        e.rollout_policy(k_steps, cache[key][1], seed=seed, ret_env=ret, traj=traj, t0=self._t)
+        e.rollout_policy(k_steps, cache[key][1], seed=seed, ret_env=ret, traj=traj, t0=self._t, kpi=kpi)
         self._t += k_steps
         return (ret, traj) if record else ret
 

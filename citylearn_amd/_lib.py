@@ -19,6 +19,7 @@ LIB_PATH = PKG / 'libcitylearn_amd.so'
 TUNE_LIB_PATH = PKG / 'libcitylearn_amd_tune.so'
 POLICY_LIB_PATH = PKG / 'libcitylearn_amd_policy.so'
 POLICY_KPI_LIB_PATH = PKG / 'libcitylearn_amd_policy_kpi.so'
+POLICY_FULL_LIB_PATH = PKG / 'libcitylearn_amd_policy_full.so'
 CSRC = PKG / 'csrc'
 # -amdgpu-mfma-vgpr-form: MFMA accumulators stay in VGPRs (gfx950's register file is unified), which removes the
 # v_accvgpr_read copies in front of the LSTM activations (64 per window step)
@@ -66,6 +67,14 @@ class Flex(ctypes.Structure):
 class PolicyMLP(ctypes.Structure):
     """``clpol_mlp`` (include/citylearn_amd_policy.h): the packed tables of a per-building MLP policy (`policy.MLPPolicy.pack`)."""
     _fields_ = [('n_hidden', ctypes.c_int32), ('n_sets', ctypes.c_int32), ('flags', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('pre', ctypes.c_void_p), ('dep', ctypes.c_void_p), ('out', ctypes.c_void_p), ('set_of_block', ctypes.c_void_p),
+                ('net_reset', ctypes.c_void_p), ('act_low', ctypes.c_void_p), ('act_high', ctypes.c_void_p), ('sigma', ctypes.c_void_p),
+                ('seed', ctypes.c_uint64)]
+
+
+class PolicyFullMLP(ctypes.Structure):
+    """``clpf_mlp`` (include/citylearn_amd_policy_full.h): the packed tables of a per-building storage MLP policy (`policy.StorageMLPPolicy.pack`)."""
+    _fields_ = [('n_hidden', ctypes.c_int32), ('n_sets', ctypes.c_int32), ('n_device_cols', ctypes.c_int32), ('reserved', ctypes.c_int32),
                 ('pre', ctypes.c_void_p), ('dep', ctypes.c_void_p), ('out', ctypes.c_void_p), ('set_of_block', ctypes.c_void_p),
                 ('net_reset', ctypes.c_void_p), ('act_low', ctypes.c_void_p), ('act_high', ctypes.c_void_p), ('sigma', ctypes.c_void_p),
                 ('seed', ctypes.c_uint64)]
@@ -230,6 +239,57 @@ def policy_kpi_lds_bytes(nw: int, vec: int) -> int:
     policy's staged rows [nw][2][3 x 32 + 8] (tests/test_policy_kpi_host.py holds it against the header's formula)."""
     tile = 64 * vec
     return 4 * (8 * nw * tile + 12 * tile + 16 + 8 * 4 * 32 + 5 * 32 + nw * 2 * (3 * 32 + 8))
+
+
+# The closed-loop rollout of THERMAL districts (csrc/cl_policy_full.hip + cl_policy_full.h; include/citylearn_amd_policy_full.h): the fourth product
+# library, one per kernel family.  Compiled WITH SLP vectorisation like the main unit: the packed thermal unit of cl_full.h wants v_pk_*_f32.
+POLICY_FULL_HEADER = abi.HEADER.parent / 'citylearn_amd_policy_full.h'
+POLICY_FULL_SOURCES = [CSRC / 'cl_policy_full.hip']
+POLICY_FULL_ABI_VERSION = int(re.search(r'#define\s+CLPF_ABI_VERSION\s+(\d+)', POLICY_FULL_HEADER.read_text()).group(1))
+POLICY_FULL_SYMBOLS = sorted(set(re.findall(r'\b(clpf_\w+)\s*\(', abi._strip_comments(POLICY_FULL_HEADER.read_text()))))
+
+
+def build_policy_full(force: bool = False, verbose: bool = False) -> Path:
+    """Compile csrc/cl_policy_full.hip for gfx950 into the in-tree ``libcitylearn_amd_policy_full.so``."""
+    deps = sorted(CSRC.glob('*.hip')) + sorted(CSRC.glob('*.h')) + [abi.HEADER, POLICY_FULL_HEADER]
+    return _compile(POLICY_FULL_SOURCES, POLICY_FULL_LIB_PATH, deps, force, verbose)
+
+
+_policy_full_lib = None
+
+
+def load_policy_full() -> ctypes.CDLL:
+    """``libcitylearn_amd_policy_full.so`` (after torch, like `load`); refuses a build from another version of its own or the core header."""
+    global _policy_full_lib
+    if _policy_full_lib is not None:
+        return _policy_full_lib
+    import torch  # noqa: F401
+    if not POLICY_FULL_LIB_PATH.exists():
+        raise EngineUnavailable(f'{POLICY_FULL_LIB_PATH} not found: the thermal policy extension is not built (run __graft_entry__.build())')
+    lib = ctypes.CDLL(str(POLICY_FULL_LIB_PATH))
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+    lib.clpf_abi_version.restype = ctypes.c_int
+    lib.clpf_core_abi_version.restype = ctypes.c_int
+    lib.clpf_last_error.restype = ctypes.c_char_p
+    lib.clpf_rollout_mlp_f32.restype = ctypes.c_int
+    lib.clpf_rollout_mlp_f32.argtypes = [ctypes.POINTER(Dims), vp, vp, vp, ctypes.POINTER(PolicyFullMLP), vp, vp, vp, vp, i32, i32, vp]
+    got, core = lib.clpf_abi_version(), lib.clpf_core_abi_version()
+    if got != POLICY_FULL_ABI_VERSION or core != abi.CL_ABI_VERSION:
+        raise EngineUnavailable(f'ABI mismatch: thermal policy library {got} (core {core}), headers {POLICY_FULL_ABI_VERSION} (core {abi.CL_ABI_VERSION}); '
+                                'rebuild the extension')
+    _policy_full_lib = lib
+    return lib
+
+
+def check_policy_full(rc: int):
+    if rc != 0:
+        raise EngineError(rc, load_policy_full().clpf_last_error().decode(errors='replace'))
+
+
+def policy_full_lds_bytes(nw: int, vec: int) -> int:
+    """Dynamic LDS of one `cl_rollout_full_policy_kernel` workgroup of ``nw`` waves at ``vec`` envs per lane: csrc/cl_policy_full.h's
+    `rollout_full_policy_lds_floats` -- the district reduction's rows [nw][4][tile], then the staged policy rows [nw][(5 + 4) x 32 + 4 x 8]."""
+    return 4 * (nw * 4 * 64 * vec + nw * ((5 + 4) * 32 + 4 * 8))
 
 
 _lib = None

@@ -1,0 +1,294 @@
+// cl_policy_full.h -- mode B of a THERMAL district with a CLOSED-LOOP policy: the K-step loop of cl_rollout_full_kernel<VEC, false, PREC, MARL>
+// (cl_rollout.h: the packed unit clv::unit_step in registers for K steps, one building per wave, never building-chunked) whose storage actions of
+// every (env, building, step) are the heads of a one-hidden-layer tanh MLP over that building's own observation vector, evaluated inside the loop
+// from the five observations that depend on the env -- the unit's four storage socs before the step and its net of the previous step, all in
+// registers already.  Included by cl_policy_full.hip only (libcitylearn_amd_policy_full.so, include/citylearn_amd_policy_full.h).
+//
+//     h_j    = tanh(pre[s][r][b][j] + sum_d dep[s][b][d][j] x_d)            x = (soc, cs, hs, ds, net_prev)
+//     mean_a = mid_a + half_a tanh(out[s][b][a][H] + sum_j out[s][b][a][j] h_j)       a over the heads (es, cs, hs, ds)
+//     act_a  = clamp(mean_a + sigma_a z_a, low_a, high_a)
+// The pieces are cl_policy.h's: `pre` through the constant address space (s_load_dwordx4 per four units); `dep` / `out` / bounds / sigma staged
+// once per launch in the wave's own LDS row and read back as broadcast 16-byte reads; a hidden unit as (1 - e) / (1 + e), e = v_exp_f32 of the
+// pre-scaled sum; tanhf for the output units; Box-Muller on the column's Philox stream.  What differs:
+//  * Which terms and heads exist is a property of the BUILDING (its CLF_* storage flags, its action columns), hence wave-uniform: per group of four
+//    hidden units every term / head sits behind a scalar branch, so a 2020 building pays for its 4 terms and <= 3 heads and not for zeros.
+//  * The heads are finished -- tanhf, noise, clamp -- in ONE loop over a = 0 .. 3 that is not unrolled, with the head's accumulator picked by
+//    wave-uniform selects: one copy of tanhf and of the Philox block in the code instead of four scheduled into each other
+//    (cl_rollout_full_kernel's note on its six inlined block functions).
+//  * No Philox cache: the blind kernel's per-wave LDS rows of drawn actions have no counterpart, a noisy head draws its block every step.
+// LDS per workgroup: the district reduction's [nw][NQ][tile] rows (MARL's exchange row and the return rows alias them) + nw x CLPF_ROW floats:
+// 52 KiB at the largest geometry (nw = 16, two envs per lane); the host refuses anything beyond the CU's 160 KiB.
+#pragma once
+
+#ifdef __HIPCC__
+namespace {
+
+constexpr int CLPF_GROUP = 4 * (CLPF_ND + CLPF_NA);            // floats of one group of four hidden units: [5 terms | 4 heads][4]
+constexpr int CLPF_HEADS = CLPF_GROUP * (CLPF_MAX_HIDDEN / 4);  // where the heads' {bias, mid, half, sigma | low, high, -, -} start
+constexpr int CLPF_ROW = CLPF_HEADS + 8 * CLPF_NA;              // floats of one building's staged row
+
+struct PolicyFullArgs {
+    RolloutArgs r;                         // r.s.actions == NULL, r.act_low / r.act_high: the columns' bounds, r.seed: ALREADY xor CLPF_NOISE_KEY
+    const float* __restrict__ pre;         // [n_sets][n_rows][n_bldg][H]
+    const float* __restrict__ dep;         // [n_sets][n_bldg][CLPF_ND][H]
+    const float* __restrict__ out;         // [n_sets][n_bldg][CLPF_NA][H + 1]
+    const int32_t* __restrict__ set_of_block;
+    const float* __restrict__ net_reset;   // [n_rows][n_bldg] or NULL
+    const float* __restrict__ sigma;       // [n_act_cols] or NULL
+    float* __restrict__ traj;              // [K][CLPF_NT][n_bldg][n_env] or NULL
+    int n_rows, n_hidden;
+};
+
+typedef float clpf_f4 __attribute__((ext_vector_type(4)));
+typedef const clpf_f4 __attribute__((address_space(4)))* clpf_c4ptr;
+
+constexpr size_t rollout_full_policy_lds_floats(int nw, int tile) { return (size_t)nw * NQ * tile + (size_t)nw * CLPF_ROW; }
+
+// a hidden unit's activation on the pre-scaled sum (cl_policy.h's form; the min keeps e finite: (1 - inf) * 0 is a NaN)
+CL_DEV float clpf_unit(float z) {
+    const float e = __builtin_amdgcn_exp2f(fminf(z, 64.0f));
+    return (1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e);
+}
+CL_DEV clv::f2 clpf_unit(clv::f2 z) { clv::f2 r; r.x = clpf_unit(z.x); r.y = clpf_unit(z.y); return r; }
+
+template <int VEC, int PREC, bool MARL>
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) cl_rollout_full_policy_kernel(const PolicyFullArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];     // [nw][NQ][64*VEC] | [nw][CLPF_ROW]
+    using F = typename Vec<VEC>::type;
+    const RolloutArgs& r = p.r;
+    const StepArgs& a = r.s;
+    constexpr int TILE = 64 * VEC;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // = the wave's building (host: nw == n_bldg)
+    const int tile_env0 = blockIdx.x * TILE;
+    const int env0 = tile_env0 + lane * VEC;
+    const bool live = env0 < a.n_env;
+    const long long plane = (long long)a.n_bldg * a.n_env;
+    const int rkind = (a.flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT;
+    const bool quirk = a.flags & CLD_REF_T0_QUIRK;
+    const int H = p.n_hidden;
+    const int blk = tile_env0 / CL_ROW0_BLOCK;
+    const int row0 = a.env_row0 ? a.env_row0[blk] : 0;              // workgroup-uniform
+    const int set = p.set_of_block ? p.set_of_block[blk] : 0;       // workgroup-uniform
+    float* const row = lds + (size_t)a.nw * NQ * TILE + (size_t)w * CLPF_ROW;
+
+    const uint32_t* __restrict__ f = a.params + (long long)w * CL_NP + CLP_F_FIRST;
+    [[maybe_unused]] const uint32_t* __restrict__ grow = PREC == 2 ? a.params + (long long)w * CL_NP : nullptr;
+    const uint32_t flags = clv::uword<false>(f, 0);
+    const int c_cs = (int)clv::uword<false>(f, 1), c_hs = (int)clv::uword<false>(f, 2), c_ds = (int)clv::uword<false>(f, 3), c_es = (int)clv::uword<false>(f, 4);
+    const long long off = (long long)w * a.n_env + env0;
+    const F zero = (F)(0.0f), one = (F)(1.0f);
+    clv::St<F> S = {zero, one, zero, zero, zero, zero};
+    // the previous step's net: what the reset observation shows in front of step 0, what the previous launch (or reset) left otherwise
+    F last_net = (F)((r.t0 == 0 && p.net_reset) ? p.net_reset[(long long)row0 * a.n_bldg + w] : 0.0f), last_rw = zero;
+    if (live) {
+        if (flags & CLF_BATTERY) {
+            S.soc = full_load<VEC>(a.state + CLS_B_SOC * plane + off); S.eff = full_load<VEC>(a.state + CLS_B_EFF * plane + off);
+            S.degcap = full_load<VEC>(a.state + CLS_B_DEGCAP * plane + off);
+        }
+        if (flags & CLF_COOL_STO) S.cs = full_load<VEC>(a.state + CLS_CS_SOC * plane + off);
+        if (flags & CLF_HEAT_STO) S.hs = full_load<VEC>(a.state + CLS_HS_SOC * plane + off);
+        if (flags & CLF_DHW_STO) S.ds = full_load<VEC>(a.state + CLS_DS_SOC * plane + off);
+        if (r.t0 != 0) last_net = full_load<VEC>(a.out_bldg + CLO_NET * plane + off);
+    }
+    // stage the building's step-independent policy rows (this wave's own LDS row; the barrier below orders them): lane j fetches hidden unit j's
+    // nine weights, lane a < 4 head a's bias, bounds and sigma
+    {
+        const long long sb = (long long)set * a.n_bldg + w;
+        if (lane < H) {
+            float* at = row + (lane >> 2) * CLPF_GROUP + (lane & 3);
+#pragma unroll
+            for (int d = 0; d < CLPF_ND; ++d) at[4 * d] = p.dep[(sb * CLPF_ND + d) * H + lane];
+#pragma unroll
+            for (int h = 0; h < CLPF_NA; ++h) at[4 * (CLPF_ND + h)] = p.out[(sb * CLPF_NA + h) * (H + 1) + lane];
+        }
+        if (lane < CLPF_NA) {
+            const int col = lane == CLPF_A_ES ? c_es : lane == CLPF_A_CS ? c_cs : lane == CLPF_A_HS ? c_hs : c_ds;
+            float* hp = row + CLPF_HEADS + 8 * lane;
+            const bool has = col >= 0;
+            const float lo = has ? r.act_low[col] : 0.0f, hi = has ? r.act_high[col] : 0.0f;
+            hp[0] = has ? p.out[(sb * CLPF_NA + lane) * (H + 1) + H] : 0.0f;
+            hp[1] = 0.5f * (hi + lo); hp[2] = 0.5f * (hi - lo);
+            hp[3] = (has && p.sigma) ? p.sigma[col] : 0.0f;
+            hp[4] = lo; hp[5] = hi; hp[6] = 0.0f; hp[7] = 0.0f;
+        }
+    }
+    __syncthreads();
+    // the `pre` rows of this wave's building in this workgroup's parameter set and episode window (inside the loop: + t n_bldg H)
+    const float* __restrict__ pre_w = p.pre + (((long long)set * p.n_rows + row0) * a.n_bldg + w) * H;
+    float ret[VEC], q_net[VEC], q_cost[VEC], q_em[VEC], q_rw[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) ret[i] = 0.0f;
+
+    for (int k = 0; k < r.k_steps; ++k) {
+        const int t = r.t0 + k;
+        float* const tr = p.traj ? p.traj + (long long)k * CLPF_NT * plane + off : nullptr;
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) q_net[i] = q_cost[i] = q_em[i] = q_rw[i] = 0.0f;
+
+        // ---- the policy: this building's storage actions from (table row, soc, cs, hs, ds, previous net) ----
+        clv::Ac<F> act = {zero, zero, zero, zero, zero, zero};
+        {
+            const clpf_c4ptr pq = (clpf_c4ptr)(const clpf_f4*)(pre_w + (long long)t * a.n_bldg * H);
+            F acc_es = zero, acc_cs = zero, acc_hs = zero, acc_ds = zero;
+#pragma unroll 1
+            for (int g = 0; g < H; g += 4) {
+                const float* grp = row + (g >> 2) * CLPF_GROUP;
+                const clpf_f4 pj = pq[g >> 2];
+                F z[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) z[u] = (F)(pj[u]);
+#define CLPF_TERM(d, x) { const clpf_f4 wd = *reinterpret_cast<const clpf_f4*>(grp + 4 * (d)); \
+                          _Pragma("unroll") for (int u = 0; u < 4; ++u) z[u] = clv::vfma((F)(wd[u]), x, z[u]); }
+                if (flags & CLF_BATTERY) CLPF_TERM(CLPF_D_SOC, S.soc)
+                if (flags & CLF_COOL_STO) CLPF_TERM(CLPF_D_CS, S.cs)
+                if (flags & CLF_HEAT_STO) CLPF_TERM(CLPF_D_HS, S.hs)
+                if (flags & CLF_DHW_STO) CLPF_TERM(CLPF_D_DS, S.ds)
+                CLPF_TERM(CLPF_D_NET, last_net)
+#undef CLPF_TERM
+#pragma unroll
+                for (int u = 0; u < 4; ++u) z[u] = clpf_unit(z[u]);
+#define CLPF_HEAD(h, acc) { const clpf_f4 wo = *reinterpret_cast<const clpf_f4*>(grp + 4 * (CLPF_ND + (h))); \
+                            _Pragma("unroll") for (int u = 0; u < 4; ++u) acc = clv::vfma((F)(wo[u]), z[u], acc); }
+                if (c_es >= 0) CLPF_HEAD(CLPF_A_ES, acc_es)
+                if (c_cs >= 0) CLPF_HEAD(CLPF_A_CS, acc_cs)
+                if (c_hs >= 0) CLPF_HEAD(CLPF_A_HS, acc_hs)
+                if (c_ds >= 0) CLPF_HEAD(CLPF_A_DS, acc_ds)
+#undef CLPF_HEAD
+            }
+#pragma unroll 1
+            for (int h = 0; h < CLPF_NA; ++h) {
+                const int col = h == CLPF_A_ES ? c_es : h == CLPF_A_CS ? c_cs : h == CLPF_A_HS ? c_hs : c_ds;
+                if (col < 0) continue;                                   // wave-uniform
+                const clpf_f4 hp = *reinterpret_cast<const clpf_f4*>(row + CLPF_HEADS + 8 * h);      // bias, mid, half, sigma
+                const float lo = row[CLPF_HEADS + 8 * h + 4], hi = row[CLPF_HEADS + 8 * h + 5];
+                const F acc = h == CLPF_A_ES ? acc_es : h == CLPF_A_CS ? acc_cs : h == CLPF_A_HS ? acc_hs : acc_ds;
+                float v[VEC];
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    float s;
+                    if constexpr (VEC == 1) s = acc; else s = acc[i];
+                    v[i] = fmaf(hp[2], tanhf(s + hp[0]), hp[1]);
+                }
+                // (through a float local: __builtin_bit_cast on the vector ELEMENT hp[3] copies from the start of the vector -- it read the bias)
+                const float sg_lane = hp[3];
+                const float sg = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sg_lane)));
+                if (sg != 0.0f) {                                        // wave-uniform
+                    // Box-Muller on two draws of the column's stream: counters 2t and 2t + 1 = words (0, 1) or (2, 3) of block t >> 1
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) {
+                        const cl::U4 bk = cl::philox_block(r.seed, (uint32_t)(env0 + i) + a.env_offset, (uint32_t)col, (uint32_t)t >> 1);
+                        const uint32_t w0 = bk.w[0], w1 = bk.w[1], w2 = bk.w[2], w3 = bk.w[3];
+                        const float u1 = cl::u01((t & 1) ? w2 : w0) + 0x1p-25f, u2 = cl::u01((t & 1) ? w3 : w1);
+                        // v_log_f32 is log2, v_cos_f32 takes revolutions
+                        const float rad = __builtin_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1));
+                        v[i] = fmaf(sg, rad * __builtin_amdgcn_cosf(u2), v[i]);
+                    }
+                }
+                F av;
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    const float c = fminf(fmaxf(v[i], lo), hi);
+                    if constexpr (VEC == 1) av = c; else av[i] = c;
+                }
+                if (h == CLPF_A_ES) act.es = av; else if (h == CLPF_A_CS) act.cs = av; else if (h == CLPF_A_HS) act.hs = av; else act.ds = av;
+            }
+        }
+
+        // ---- the packed thermal unit exactly as in cl_rollout_full_kernel (its note on the per-step re-read of the parameter block) ----
+        {
+            int z;
+            asm("s_mov_b32 %0, 0" : "=s"(z) : "s"(k));
+            const uint32_t* __restrict__ fz = f + z;
+            [[maybe_unused]] const uint32_t* __restrict__ gz = PREC == 2 ? grow + z : nullptr;
+            clv::FP B;
+            clv::load_fp<false>(B, fz);
+            B.f = fz;
+            cl::Row R;
+            cl::load_row_scalar<true>(R, a.ts + ((long long)(t + row0) * a.n_bldg + w) * CL_NF, B.flags, nullptr);
+            clv::Ou<F> O;
+            const bool first = quirk && t == 0;
+            if (R.outage) clv::unit_step<F, true, false, PREC>(B, R, t, first, act, S, O, gz);
+            else clv::unit_step<F, false, false, PREC>(B, R, t, first, act, S, O, gz);
+            const F rw = clv::unit_reward<F>(rkind, B, S, O.net);
+            last_net = O.net; last_rw = rw;
+            full_accumulate<VEC>(q_net, O.net); full_accumulate<VEC>(q_cost, O.cost); full_accumulate<VEC>(q_em, O.emission); full_accumulate<VEC>(q_rw, rw);
+        }
+        if (tr && live) {
+            full_store<VEC, false>(tr + (long long)(CLPF_T_ACTION + CLPF_A_ES) * plane, act.es);
+            full_store<VEC, false>(tr + (long long)(CLPF_T_ACTION + CLPF_A_CS) * plane, act.cs);
+            full_store<VEC, false>(tr + (long long)(CLPF_T_ACTION + CLPF_A_HS) * plane, act.hs);
+            full_store<VEC, false>(tr + (long long)(CLPF_T_ACTION + CLPF_A_DS) * plane, act.ds);
+            full_store<VEC, false>(tr + (long long)CLPF_T_NET * plane, last_net);
+            full_store<VEC, false>(tr + (long long)(CLPF_T_SOC + CLPF_D_SOC) * plane, (flags & CLF_BATTERY) ? S.soc : zero);
+            full_store<VEC, false>(tr + (long long)(CLPF_T_SOC + CLPF_D_CS) * plane, (flags & CLF_COOL_STO) ? S.cs : zero);
+            full_store<VEC, false>(tr + (long long)(CLPF_T_SOC + CLPF_D_HS) * plane, (flags & CLF_HEAT_STO) ? S.hs : zero);
+            full_store<VEC, false>(tr + (long long)(CLPF_T_SOC + CLPF_D_DS) * plane, (flags & CLF_DHW_STO) ? S.ds : zero);
+            if constexpr (!MARL) full_store<VEC, false>(tr + (long long)CLPF_T_REWARD * plane, last_rw);
+        }
+        if constexpr (MARL) {
+            // the MARL reward couples the buildings through the district net of THIS step: one LDS exchange per step
+            vstore<VEC>(lds + (size_t)w * TILE + lane * VEC, q_net);
+            __syncthreads();
+            float dnet[VEC];
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) dnet[i] = 0.0f;
+            for (int kk = 0; kk < a.nw; ++kk) {
+                float part[VEC];
+                vload<VEC>(part, lds + (size_t)kk * TILE + lane * VEC);
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) dnet[i] += part[i];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                float n_i, rw_i;
+                if constexpr (VEC == 1) n_i = last_net; else n_i = last_net[i];
+                rw_i = cl::marl_reward(n_i, dnet[i]);
+                if constexpr (VEC == 1) last_rw = rw_i; else last_rw[i] = rw_i;
+                ret[i] += rw_i;
+            }
+            if (tr && live) full_store<VEC, false>(tr + (long long)CLPF_T_REWARD * plane, last_rw);
+        } else {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) ret[i] += q_rw[i];
+        }
+    }
+
+    // ---- write back: carried state, the last step's per-building outputs, district sums, episode-return partials (cl_rollout_full_kernel's) ----
+    if (live) {
+        if (flags & CLF_BATTERY) {
+            full_store<VEC, false>(a.state + CLS_B_SOC * plane + off, S.soc); full_store<VEC, false>(a.state + CLS_B_EFF * plane + off, S.eff);
+            full_store<VEC, false>(a.state + CLS_B_DEGCAP * plane + off, S.degcap);
+        }
+        if (flags & CLF_COOL_STO) full_store<VEC, false>(a.state + CLS_CS_SOC * plane + off, S.cs);
+        if (flags & CLF_HEAT_STO) full_store<VEC, false>(a.state + CLS_HS_SOC * plane + off, S.hs);
+        if (flags & CLF_DHW_STO) full_store<VEC, false>(a.state + CLS_DS_SOC * plane + off, S.ds);
+        if (r.k_steps > 0) {
+            full_store<VEC, false>(a.out_bldg + CLO_NET * plane + off, last_net);
+            full_store<VEC, false>(a.out_bldg + CLO_REWARD * plane + off, last_rw);
+        }
+    }
+    if (r.k_steps > 0) {
+        if constexpr (MARL) {
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                if constexpr (VEC == 1) q_rw[i] = last_rw; else q_rw[i] = last_rw[i];
+            }
+        }
+        district_reduce<VEC>(a, lds, w, lane, env0, live, plane, MARL ? (int)CLR_DEFAULT : rkind, q_net, q_cost, q_em, q_rw, a.nw);
+    }
+    if (r.ret_env) {
+        __syncthreads();
+        vstore<VEC>(lds + (size_t)w * TILE + lane * VEC, ret);
+        __syncthreads();
+        for (int e = threadIdx.x; e < TILE; e += blockDim.x) {
+            float s = 0.0f;
+            for (int kk = 0; kk < a.nw; ++kk) s += lds[(size_t)kk * TILE + e];
+            if (tile_env0 + e < a.n_env) r.ret_env[tile_env0 + e] += s;
+        }
+    }
+}
+
+}  // namespace
+#endif  // __HIPCC__

@@ -504,15 +504,24 @@ class StepEngine:
         ``kpi=True`` (on an engine built with ``kpi=True``, otherwise `ValueError`) runs the same steps as ONE launch of
         `cl_rollout_policy_kpi_kernel` (`clpk_rollout_mlp_kpi_f32`, ``libcitylearn_amd_policy_kpi.so``), which also keeps the streaming KPI
         accumulators `evaluate()` / `state_dict()` read -- equal to the single-step path's on the recorded actions to ~1e-6 relative, like
-        ``rollout(fused=True)``.  ``kpi=False`` is the call above in every respect, its refusal of a ``kpi=True`` engine included."""
+        ``rollout(fused=True)``.  ``kpi=False`` is the call above in every respect, its refusal of a ``kpi=True`` engine included.
+
+        ``policy_tables`` from `policy.StorageMLPPolicy.pack` (a `StoragePolicyTables`) sends a THERMAL district of up to 16 buildings to
+        `cl_rollout_full_policy_kernel` (`clpf_rollout_mlp_f32`, ``libcitylearn_amd_policy_full.so``): up to four storage heads per building,
+        ``traj`` ``[k_steps, CLPF_NT, n_bldg, n_env]``; ``kpi=True`` raises `NotImplementedError` there."""
         from . import policy as _policy
+        storage = isinstance(policy_tables, _policy.StoragePolicyTables)
+        if storage and kpi:
+            raise NotImplementedError('rollout_policy(kpi=True): the thermal policy kernel (cl_rollout_full_policy_kernel) keeps no streaming KPIs -- '
+                                      'only battery + PV districts with an MLPPolicy have a closed-loop KPI kernel')
         if kpi and not self.kpi:
             raise ValueError('rollout_policy(kpi=True) needs an engine built with kpi=True: this one keeps no KPI accumulators')
         if self.flex is not None:
             # (the library cannot see this: a battery + PV district with EV chargers / washing machines and a non-EV reward has CLD_LEAN set)
             raise NotImplementedError('rollout_policy: districts with flexible loads (EV chargers / washing machines) are not covered by the policy '
                                       'kernel -- it would leave their consumption out of net; use step() / capture_rollout')
-        lib = _lib.load_policy_kpi() if kpi else _lib.load_policy()
+        lib = _lib.load_policy_full() if storage else _lib.load_policy_kpi() if kpi else _lib.load_policy()
+        n_planes = _policy.CLPF_NT if storage else _policy.CLPOL_NT
         t0 = self.t if t0 is None else t0
         pt = policy_tables
         if (pt.n_rows, pt.n_bldg) != (self.n_ts_rows, self.n_bldg) or pt.pre.device != self.device:
@@ -522,12 +531,16 @@ class StepEngine:
             raise ValueError(f'policy tables hold {pt.act_low.numel()} action columns, the engine {self.n_act_cols}')
         if pt.set_of_block is not None and pt.set_of_block.numel() != -(-self.n_env // abi.CL_ROW0_BLOCK):
             raise ValueError(f'set_of_block needs one entry per {abi.CL_ROW0_BLOCK} envs')
-        for name, x, shape in (('ret_env', ret_env, (self.n_env,)), ('traj', traj, (k_steps, _policy.CLPOL_NT, self.n_bldg, self.n_env))):
+        for name, x, shape in (('ret_env', ret_env, (self.n_env,)), ('traj', traj, (k_steps, n_planes, self.n_bldg, self.n_env))):
             if x is not None and (x.dtype != torch.float32 or x.device != self.device or tuple(x.shape) != shape or not x.is_contiguous()):
                 raise ValueError(f'{name} must be a contiguous float32 tensor {shape} on {self.device}')
         mlp = pt.struct(seed)
         with torch.cuda.device(self.device):
-            if kpi:
+            if storage:
+                _lib.check_policy_full(lib.clpf_rollout_mlp_f32(ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), ctypes.byref(mlp),
+                                                                _ptr(self.out_bldg), _ptr(self._out_env), _ptr(ret_env), _ptr(traj), int(t0), int(k_steps),
+                                                                self._stream()))
+            elif kpi:
                 _lib.check_policy_kpi(lib.clpk_rollout_mlp_kpi_f32(
                     ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), ctypes.byref(mlp), _ptr(self.out_bldg),
                     _ptr(self._out_env), _ptr(ret_env), _ptr(traj), _ptr(self.kpi_bldg), _ptr(self.kpi_env), int(t0), int(k_steps), self._stream()))

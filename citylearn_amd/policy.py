@@ -23,6 +23,16 @@ column of building b is column b, as in the 2022 schemas):
     kenv = VectorCityLearnEnv(schema, n_envs, kpi=True)
     kenv.rollout(24, actions=traj[:, policy.CLPOL_T_ACTION].contiguous(), fused=True)      # policy = this module
     building_kpis, district_kpis = kenv.evaluate()
+
+THERMAL districts -- cooling / heating / DHW storage beside the battery, the 2020 / 2021 schemas: no LSTM stage, no device actions, up to 16
+buildings -- take a `StorageMLPPolicy`: the same hidden layer with up to FOUR heads per building in the fixed order electrical, cooling, heating,
+DHW storage (a head whose action column the building lacks is ignored), fed by the building's four storage socs and its previous net.  One launch
+of `cl_rollout_full_policy_kernel` (csrc/cl_policy_full.h, ``libcitylearn_amd_policy_full.so``, include/citylearn_amd_policy_full.h):
+
+    spolicy = StorageMLPPolicy(w1, b1, w2, b2, sigma=0.1)          # w2 [n_sets, n_bldg, 4, H], b2 [n_sets, n_bldg, 4]
+    ret, traj = env.rollout_policy(spolicy, 24, seed=3, record=True)   # traj [24, CLPF_NT, n_bldg, n_envs]: policy.CLPF_T_ACTION + head, ..
+
+It keeps no streaming KPIs (``kpi=True`` raises `NotImplementedError`); `MLPPolicy` still refuses such a district.
 """
 from __future__ import annotations
 
@@ -35,7 +45,7 @@ import numpy as np
 import torch
 
 from . import _lib, abi
-from .observations import SRC_OUT, SRC_STATE, ObservationLayout
+from .observations import SRC_OUT, SRC_STATE, SRC_TEMP, ObservationLayout
 
 # tanh x = (1 - e) / (1 + e), e = 2^(ACT_SCALE x): what the kernel evaluates with one v_exp_f32 + one v_rcp_f32 per hidden unit; folded into
 # the packed first layer (`pre`, `dep`)
@@ -272,3 +282,199 @@ class MLPPolicy:
                             f32(net_reset), f32(low), f32(high), f32(sigma), sob, es, low_bldg, high_bldg,
                             np.zeros(n_bldg) if sigma is None else np.where(es >= 0, np.asarray(sigma, dtype=np.float64)[np.maximum(es, 0)], 0.0),
                             self.version)
+
+
+# ---- thermal districts: up to four storage heads per building (csrc/cl_policy_full.h, libcitylearn_amd_policy_full.so) -------------------------
+_HF = re.sub(r'/\*.*?\*/', ' ', _lib.POLICY_FULL_HEADER.read_text(), flags=re.S)
+FULL_CONSTANTS = {m.group(1): int(m.group(2).rstrip('ulUL'), 0) for m in re.finditer(r'#define\s+(CLPF_\w+)\s+(0x[0-9a-fA-F]+\w*|\d+)\b', _HF)}
+CLPF_NT, CLPF_ND, CLPF_NA, CLPF_MAX_HIDDEN = (FULL_CONSTANTS[k] for k in ('CLPF_NT', 'CLPF_ND', 'CLPF_NA', 'CLPF_MAX_HIDDEN'))
+CLPF_T_ACTION, CLPF_T_REWARD, CLPF_T_NET, CLPF_T_SOC = (FULL_CONSTANTS[k] for k in ('CLPF_T_ACTION', 'CLPF_T_REWARD', 'CLPF_T_NET', 'CLPF_T_SOC'))
+CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET = (FULL_CONSTANTS[k] for k in ('CLPF_D_SOC', 'CLPF_D_CS', 'CLPF_D_HS', 'CLPF_D_DS', 'CLPF_D_NET'))
+CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS = (FULL_CONSTANTS[k] for k in ('CLPF_A_ES', 'CLPF_A_CS', 'CLPF_A_HS', 'CLPF_A_DS'))
+assert FULL_CONSTANTS['CLPF_NOISE_KEY'] == CLPOL_NOISE_KEY                       # `noise_host` replays both kernels' streams
+HEAD_NAMES = ('electrical_storage', 'cooling_storage', 'heating_storage', 'dhw_storage')                  # heads in CLPF_A_* order
+# per head: the parameter slot of its action column; per first-layer term: (source kind, plane) of the observation and the storage's flag bit
+_HEAD_SLOTS = (abi.CLP_ACT_ELEC_STO, abi.CLP_ACT_COOL_STO, abi.CLP_ACT_HEAT_STO, abi.CLP_ACT_DHW_STO)
+_DEVICE_SLOTS = (('cooling_device', abi.CLP_ACT_COOL_DEV), ('heating_device', abi.CLP_ACT_HEAT_DEV), ('cooling_or_heating_device', abi.CLP_ACT_COH_DEV))
+_TERMS = {(SRC_STATE, abi.CLS_B_SOC): CLPF_D_SOC, (SRC_STATE, abi.CLS_CS_SOC): CLPF_D_CS, (SRC_STATE, abi.CLS_HS_SOC): CLPF_D_HS,
+          (SRC_STATE, abi.CLS_DS_SOC): CLPF_D_DS, (SRC_OUT, abi.CLO_NET): CLPF_D_NET}
+_TERM_FLAGS = (abi.CLF_BATTERY, abi.CLF_COOL_STO, abi.CLF_HEAT_STO, abi.CLF_DHW_STO, None)
+
+
+def head_columns(tab) -> np.ndarray:
+    """``[n_bldg, CLPF_NA]`` the action column of every building's electrical / cooling / heating / DHW storage (-1: none), as the kernel reads them."""
+    return np.ascontiguousarray(tab.params).view(np.int32)[:, list(_HEAD_SLOTS)].astype(np.int64)
+
+
+class StoragePolicyTables:
+    """`StorageMLPPolicy.pack`'s result: the tables of `clpf_mlp` as float32 tensors on one device (the layouts of the header)."""
+
+    def __init__(self, pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, cols, low_bldg, high_bldg, sigma_bldg, n_device_cols, version):
+        self.pre, self.dep, self.out, self.net_reset = pre, dep, out, net_reset
+        self.act_low, self.act_high, self.sigma, self.set_of_block = act_low, act_high, sigma, set_of_block
+        # host side, int64 / float64 [n_bldg, CLPF_NA]: every head's action column (-1: none), that column's bounds and sigma -- what
+        # `StorageMLPPolicy.actions_host(..., tables=this)` evaluates the reference with
+        self.cols, self.low_bldg, self.high_bldg, self.sigma_bldg = cols, low_bldg, high_bldg, sigma_bldg
+        self.n_device_cols = int(n_device_cols)
+        self.version = version
+        self.n_sets, self.n_rows, self.n_bldg, self.n_hidden = (int(x) for x in pre.shape)
+
+    def struct(self, seed: int) -> _lib.PolicyFullMLP:
+        p = lambda t: None if t is None else t.data_ptr()
+        return _lib.PolicyFullMLP(self.n_hidden, self.n_sets, self.n_device_cols, 0, p(self.pre), p(self.dep), p(self.out), p(self.set_of_block),
+                                  p(self.net_reset), p(self.act_low), p(self.act_high), p(self.sigma), int(seed) & (2 ** 64 - 1))
+
+
+class StorageMLPPolicy:
+    """``act_a = clamp(mid_a + half_a tanh(w2[a] . tanh(W1 obs + b1) + b2[a]) + sigma_a z_a, low_a, high_a)`` per building and head a, the heads in
+    the fixed order electrical, cooling, heating, DHW storage (`HEAD_NAMES`); `obs` = the building's own observation vector as the env defines
+    it, (low_a, high_a) = the bounds of the building's action column of that storage.  The heads of columns a building lacks are ignored.  For
+    thermal districts without the LSTM stage and without device actions (the 2020 / 2021 schemas): `cl_rollout_full_policy_kernel`.
+
+    ``w1 [n_sets, n_bldg, H, n_obs]``, ``b1 [n_sets, n_bldg, H]``, ``w2 [n_sets, n_bldg, 4, H]``, ``b2 [n_sets, n_bldg, 4]`` (kept in float64); a
+    leading dimension of 1 broadcasts.  ``H``: 4, 8, .. 32.  ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
+
+    The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
+
+    def __init__(self, w1, b1, w2, b2, sigma=None):
+        self.w1, self.b1, self.w2, self.b2 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2))
+        if self.w1.ndim != 4 or self.b1.ndim != 3 or self.w2.ndim != 4 or self.b2.ndim != 3:
+            raise ValueError(f'w1 [n_sets, n_bldg, H, n_obs], b1 [n_sets, n_bldg, H], w2 [n_sets, n_bldg, {CLPF_NA}, H], b2 [n_sets, n_bldg, {CLPF_NA}]')
+        self.n_hidden, self.n_obs = int(self.w1.shape[2]), int(self.w1.shape[3])
+        if self.n_hidden % 4 or not 4 <= self.n_hidden <= CLPF_MAX_HIDDEN:
+            raise ValueError(f'H={self.n_hidden}: the policy kernel takes 4, 8, .. {CLPF_MAX_HIDDEN} hidden units')
+        if self.b1.shape[2] != self.n_hidden or self.w2.shape[3] != self.n_hidden or self.w2.shape[2] != CLPF_NA or self.b2.shape[2] != CLPF_NA:
+            raise ValueError(f'b1 / w2 / b2 disagree with w1 about H, or do not have {CLPF_NA} heads')
+        self.n_sets = max(x.shape[0] for x in (self.w1, self.b1, self.w2, self.b2))
+        self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
+        self.version = 0
+
+    invalidate = MLPPolicy.invalidate
+    update = MLPPolicy.update
+
+    def _full(self, n_bldg: int):
+        S, H = self.n_sets, self.n_hidden
+        try:
+            return (np.broadcast_to(self.w1, (S, n_bldg, H, self.n_obs)), np.broadcast_to(self.b1, (S, n_bldg, H)),
+                    np.broadcast_to(self.w2, (S, n_bldg, CLPF_NA, H)), np.broadcast_to(self.b2, (S, n_bldg, CLPF_NA)))
+        except ValueError as e:
+            raise ValueError(f'the weights do not broadcast to {S} sets x {n_bldg} buildings: {e}') from None
+
+    # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
+    def actions_host(self, obs_vectors, tables: StoragePolicyTables, noise=None, set_index: int = 0) -> np.ndarray:
+        """float64 numpy evaluation of the plain MLP: ``obs_vectors [..., n_bldg, n_obs]`` -> actions ``[..., n_bldg, 4]`` (0 for a head whose
+        column the building lacks).  ``noise``: the standard normals z (same shape as the result; `noise_host` replays the kernel's), scaled by
+        each head's sigma.  The heads' columns, bounds and sigmas come from ``tables`` (a `pack` result).  Nothing is remembered between calls."""
+        x = np.asarray(obs_vectors, dtype=np.float64)
+        w1, b1, w2, b2 = (v[set_index] for v in self._full(x.shape[-2]))
+        lo, hi = tables.low_bldg, tables.high_bldg
+        h = np.tanh(np.einsum('bjc,...bc->...bj', w1, x) + b1)
+        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('baj,...bj->...ba', w2, h) + b2)
+        if noise is not None:
+            a = a + tables.sigma_bldg * np.asarray(noise, dtype=np.float64)
+        return np.where(tables.cols >= 0, np.clip(a, lo, hi), 0.0)
+
+    def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
+        """The same MLP (no noise) written in torch over the env's observation TENSOR: returns ``f(obs [n_envs, n_obs_total], i=None) ->
+        actions [n_act_cols, n_envs]`` -- a `VectorCityLearnEnv.capture_rollout` policy; what `rollout_policy` replaces with one launch."""
+        cols = building_columns(layout)
+        n_bldg = len(cols)
+        w1, b1, w2, b2 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(n_bldg))
+        idx = torch.as_tensor(np.array([c + [c[0]] * (self.n_obs - len(c)) for c in cols]), device=device)
+        mask = torch.as_tensor(np.array([[1.0] * len(c) + [0.0] * (self.n_obs - len(c)) for c in cols]), dtype=dtype, device=device)
+        hc = head_columns(tab)
+        low, high = layout.spec.action_limits()
+        bsel, asel = np.nonzero(hc >= 0)
+        rows = torch.as_tensor(hc[bsel, asel], device=device)
+        lo = torch.as_tensor(np.asarray(low)[hc[bsel, asel]], dtype=dtype, device=device)
+        hi = torch.as_tensor(np.asarray(high)[hc[bsel, asel]], dtype=dtype, device=device)
+        flat = torch.as_tensor(bsel * CLPF_NA + asel, device=device)
+        n_act = len(low)
+
+        def f(obs, i=None):
+            x = obs.to(dtype)[:, idx] * mask                                     # [E, B, n_obs]
+            h = torch.tanh(torch.einsum('bjc,ebc->ebj', w1, x) + b1)
+            o = torch.tanh(torch.einsum('baj,ebj->eba', w2, h) + b2).reshape(obs.shape[0], -1)[:, flat]      # [E, present heads]
+            a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
+            out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
+            out[rows] = a.t().to(torch.float32)
+            return out
+        return f
+
+    # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
+    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None) -> StoragePolicyTables:
+        """Split the first layer along the observation tables of `layout` over the episode tables `tab`, as `MLPPolicy.pack` does, with FIVE
+        env-dependent inputs: the building's own ``electrical_storage_soc`` / ``cooling_storage_soc`` / ``heating_storage_soc`` /
+        ``dhw_storage_soc`` and ``net_electricity_consumption`` go into ``dep`` (rows `CLPF_D_*`; the row of a storage the building lacks stays
+        0), everything else into ``pre``.  A building observation fed by anything else on the device -- the indoor temperature of the LSTM stage
+        (``SRC_TEMP``), a detail plane, another building's plane -- and a building with a cooling / heating device ACTION raise ``ValueError``
+        naming the column."""
+        obs = layout.episode(tab, reset_table=True)
+        cols = building_columns(layout)
+        n_bldg, T = len(cols), int(obs.table.shape[0])
+        if any(len(c) > self.n_obs for c in cols) or not any(len(c) == self.n_obs for c in cols):
+            raise ValueError(f'w1 takes {self.n_obs} observations, the buildings have {sorted(set(len(c) for c in cols))}')
+        w1, b1, w2, b2 = self._full(n_bldg)
+        S, H = self.n_sets, self.n_hidden
+        params_i = np.ascontiguousarray(tab.params).view(np.int32)
+        bflags = np.ascontiguousarray(tab.params).view(np.uint32)[:, abi.CLP_FLAGS]
+        table = obs.table
+        x = np.zeros((T, n_bldg, self.n_obs))
+        scale = np.zeros((n_bldg, CLPF_ND, self.n_obs))                  # [b][term][position in the building's vector]
+        net_reset = np.zeros((T, n_bldg))
+        for i, bcols in enumerate(cols):
+            for j, c in enumerate(bcols):
+                name = f'{layout.columns[c][1]!r} of building {i} (column {c})'
+                src = int(obs.col_src[c])
+                if src < 0:
+                    if T > 1 and not np.array_equal(obs.reset_table[1:, c], table[1:, c]):
+                        raise ValueError(f'observation {name} is reset to a value its table row does not hold (observation_mode="reference"?): '
+                                         'the policy kernel reads the tables of observation_mode="current"')
+                    x[:, i, j] = table[:, c]
+                    continue
+                kind, plane, b = src >> 28, (src >> 20) & 0xFF, src & 0xFFFFF
+                which = _TERMS.get((kind, plane))
+                if which is None or b != i or layout.columns[c][0] != i:
+                    raise ValueError(f'observation {name} is fed by device plane (kind {kind}, plane {plane}, building {b}): the thermal policy kernel '
+                                     "only has the building's own storage socs (CLS_B_SOC, CLS_CS_SOC, CLS_HS_SOC, CLS_DS_SOC) and "
+                                     'net_electricity_consumption (CLO_NET)' + (' -- the indoor temperature comes from the LSTM stage' if kind == SRC_TEMP else ''))
+                offset = table[1:, c] if T > 1 else np.zeros(1)
+                if np.ptp(offset) != 0.0:
+                    raise ValueError(f'observation {name}: a table offset that changes with the row')
+                x[:, i, j] = offset[0]
+                flag = _TERM_FLAGS[which]
+                if flag is None or int(bflags[i]) & flag:                # (a storage the building lacks: its plane stays 0, the kernel skips the term)
+                    scale[i, which, j] = float(obs.col_scale[c])
+                if which == CLPF_D_NET and scale[i, which, j] != 0.0:
+                    net_reset[:, i] = (obs.reset_table[:, c] - offset[0]) / scale[i, which, j]
+        for i in range(n_bldg):
+            for dname, slot in _DEVICE_SLOTS:
+                if params_i[i, slot] >= 0:
+                    raise ValueError(f'action {dname!r} of building {i} (column {int(params_i[i, slot])}): the thermal policy kernel has storage heads '
+                                     f'only {HEAD_NAMES}; a district with device actions runs through capture_rollout')
+        dev = torch.device(device)
+        f64 = lambda v: torch.from_numpy(np.array(v, dtype=np.float64)).to(dev)
+        pre = (torch.einsum('sbjc,tbc->stbj', f64(w1), f64(x)) + f64(b1)[:, None]) * ACT_SCALE
+        dep = torch.einsum('sbjc,bkc->sbkj', f64(w1), f64(scale)) * ACT_SCALE
+        out = torch.cat([f64(w2), f64(b2)[:, :, :, None]], dim=3)
+        hc = head_columns(tab)
+        n_act = int(params_i[:, abi.CLP_ACT_COOL_STO:abi.CLP_ACT_COH_DEV + 1].max()) + 1
+        low, high = layout.spec.action_limits()
+        if len(low) != n_act:
+            raise ValueError(f'{len(low)} action limits for {n_act} action columns')
+        at = lambda v, fill: np.where(hc >= 0, np.asarray(v, dtype=np.float64)[np.maximum(hc, 0)], fill)
+        sigma = None
+        if self.sigma is not None:
+            sigma = np.full(n_act, float(self.sigma)) if self.sigma.ndim == 0 else self.sigma
+            if sigma.shape != (n_act,) or np.any(sigma < 0):
+                raise ValueError(f'sigma: a non-negative scalar or [{n_act}] (one per action column)')
+        f32 = lambda v: None if v is None else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev)
+        sob = None
+        if set_of_block is not None:
+            sob = np.asarray(set_of_block, dtype=np.int64).reshape(-1)
+            if sob.min() < 0 or sob.max() >= S:
+                raise ValueError(f'set_of_block outside [0, {S})')
+            sob = torch.from_numpy(sob.astype(np.int32)).to(dev)
+        return StoragePolicyTables(pre.to(torch.float32).contiguous(), dep.to(torch.float32).contiguous(), out.to(torch.float32).contiguous(),
+                                   f32(net_reset), f32(low), f32(high), f32(sigma), sob, hc, at(low, -1.0), at(high, 1.0),
+                                   np.zeros(hc.shape) if sigma is None else at(sigma, 0.0), 0, self.version)      # (n_device_cols = 0: refused above)

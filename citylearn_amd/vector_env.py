@@ -424,7 +424,15 @@ class VectorCityLearnEnv:
         place keep driving the old tables.  Same episode-end and stage / plugin checks as :meth:`rollout`; battery + PV districts.
         ``kpi=True`` (an env built with ``kpi=True``, otherwise `ValueError`): the same launch also keeps the streaming KPI accumulators
         (`cl_rollout_policy_kpi_kernel`), so `evaluate()` scores the controllers afterwards as after any other rollout.  ``kpi=False`` (the
-        default) is the launch without KPIs, which a ``kpi=True`` env is refused."""
+        default) is the launch without KPIs, which a ``kpi=True`` env is refused.
+
+        A `policy.StorageMLPPolicy` drives a THERMAL district (cooling / heating / DHW storage beside the battery, no LSTM stage, no device
+        actions, up to 16 buildings) the same way through `cl_rollout_full_policy_kernel`: the trajectory then has `policy.CLPF_NT` planes
+        (`CLPF_T_ACTION` + head, `_REWARD`, `_NET`, `CLPF_T_SOC` + storage), and ``kpi=True`` raises `NotImplementedError`."""
+        from . import policy as _policy
+        storage = isinstance(policy, _policy.StorageMLPPolicy)
+        if storage and kpi:
+            raise NotImplementedError('rollout_policy(kpi=True): a StorageMLPPolicy runs in the thermal policy kernel, which keeps no streaming KPIs')
         if kpi and not self.kpi:
             raise ValueError('rollout_policy(kpi=True) needs VectorCityLearnEnv(..., kpi=True): this env keeps no KPI accumulators')
         if self.stage is not None or self._plugin is not None:
@@ -433,7 +441,6 @@ class VectorCityLearnEnv:
             raise NotImplementedError('rollout_policy() does not cover districts with flexible loads (EV chargers / washing machines); use step()')
         if self._t + k_steps > self.time_steps - 1:
             raise RuntimeError(f'{k_steps} steps from t={self._t} run past the episode end ({self.time_steps - 1} steps)')
-        from . import policy as _policy
         e = self.engine
         sob = None if set_of_block is None else tuple(int(x) for x in np.asarray(set_of_block).reshape(-1))
         key = (id(policy), int(policy.version), id(e), int(self.tables.start), int(self.tables.end), sob)
@@ -448,7 +455,7 @@ class VectorCityLearnEnv:
             cache.clear()                                     # (one live entry: tables of another window or engine are stale)
             cache[key] = (policy, policy.pack(layout, self.tables, device=self.device, set_of_block=sob))
         ret = torch.zeros(self.n_envs, dtype=torch.float32, device=self.device)
-        traj = torch.empty((k_steps, _policy.CLPOL_NT, e.n_bldg, self.n_envs), dtype=torch.float32, device=self.device) if record else None
+        traj = torch.empty((k_steps, _policy.CLPF_NT if storage else _policy.CLPOL_NT, e.n_bldg, self.n_envs), dtype=torch.float32, device=self.device) if record else None
         e.rollout_policy(k_steps, cache[key][1], seed=seed, ret_env=ret, traj=traj, t0=self._t, kpi=kpi)
         self._t += k_steps
         return (ret, traj) if record else ret

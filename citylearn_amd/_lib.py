@@ -17,9 +17,6 @@ from . import abi
 PKG = Path(__file__).resolve().parent
 LIB_PATH = PKG / 'libcitylearn_amd.so'
 TUNE_LIB_PATH = PKG / 'libcitylearn_amd_tune.so'
-POLICY_LIB_PATH = PKG / 'libcitylearn_amd_policy.so'
-POLICY_KPI_LIB_PATH = PKG / 'libcitylearn_amd_policy_kpi.so'
-POLICY_FULL_LIB_PATH = PKG / 'libcitylearn_amd_policy_full.so'
 CSRC = PKG / 'csrc'
 # -amdgpu-mfma-vgpr-form: MFMA accumulators stay in VGPRs (gfx950's register file is unified), which removes the
 # v_accvgpr_read copies in front of the LSTM activations (64 per window step)
@@ -144,93 +141,73 @@ def load_tune() -> ctypes.CDLL:
     return lib
 
 
-# The closed-loop rollout (csrc/cl_policy.hip + cl_policy.h; include/citylearn_amd_policy.h): a product library of its own, so that the main
-# library's symbol list, structs and translation units stay what they are.  No SLP vectorisation, like the other rollout kernels.
-POLICY_HEADER = abi.HEADER.parent / 'citylearn_amd_policy.h'
-POLICY_SOURCES = [(CSRC / 'cl_policy.hip', ['-fno-slp-vectorize'])]
-POLICY_ABI_VERSION = int(re.search(r'#define\s+CLPOL_ABI_VERSION\s+(\d+)', POLICY_HEADER.read_text()).group(1))
-POLICY_SYMBOLS = sorted(set(re.findall(r'\b(clpol_\w+)\s*\(', abi._strip_comments(POLICY_HEADER.read_text()))))
+class _Extension:
+    """One closed-loop rollout library: a product library of its own per kernel family, so that the main library's symbol list, structs and
+    translation units stay what they are (csrc/cl_<name>.hip, include/citylearn_amd_<name>.h, ``libcitylearn_amd_<name>.so``).  ``label`` names it
+    in messages, ``flags`` are the translation unit's own compiler flags, ``entry`` is its rollout entry point taking ``mlp`` and ``n_kpi`` KPI
+    planes, ``headers`` the other extension headers its header includes."""
+
+    def __init__(self, name, prefix, label, flags, entry, mlp, n_kpi=0, headers=()):
+        self.prefix, self.label, self.entry, self.mlp, self.n_kpi = prefix, label, entry, mlp, n_kpi
+        self.path = PKG / f'libcitylearn_amd_{name}.so'
+        self.header = abi.HEADER.parent / f'citylearn_amd_{name}.h'
+        self.sources = [(CSRC / f'cl_{name}.hip', flags)] if flags else [CSRC / f'cl_{name}.hip']
+        self.deps = [abi.HEADER, *headers, self.header]
+        text = self.header.read_text()
+        self.abi_version = int(re.search(rf'#define\s+{prefix.upper()}_ABI_VERSION\s+(\d+)', text).group(1))
+        self.symbols = sorted(set(re.findall(rf'\b({prefix}_\w+)\s*\(', abi._strip_comments(text))))
+        self._lib = None
+
+    def build(self, force: bool = False, verbose: bool = False) -> Path:
+        """Compile the extension's translation unit for gfx950 into its in-tree shared library."""
+        return _compile(self.sources, self.path, sorted(CSRC.glob('*.hip')) + sorted(CSRC.glob('*.h')) + self.deps, force, verbose)
+
+    def load(self) -> ctypes.CDLL:
+        """The library (after torch, like `load`); refuses a build from another version of its own or the core header."""
+        if self._lib is not None:
+            return self._lib
+        import torch  # noqa: F401
+        if not self.path.exists():
+            raise EngineUnavailable(f'{self.path} not found: the {self.label} extension is not built (run __graft_entry__.build())')
+        lib = ctypes.CDLL(str(self.path))
+        vp, i32 = ctypes.c_void_p, ctypes.c_int32
+        abi_version, core_abi_version, last_error, entry = (getattr(lib, f'{self.prefix}_{n}') for n in ('abi_version', 'core_abi_version', 'last_error', self.entry))
+        abi_version.restype = core_abi_version.restype = entry.restype = ctypes.c_int
+        last_error.restype = ctypes.c_char_p
+        entry.argtypes = [ctypes.POINTER(Dims), vp, vp, vp, ctypes.POINTER(self.mlp), vp, vp, vp, vp, *[vp] * self.n_kpi, i32, i32, vp]
+        got, core = abi_version(), core_abi_version()
+        if got != self.abi_version or core != abi.CL_ABI_VERSION:
+            raise EngineUnavailable(f'ABI mismatch: {self.label} library {got} (core {core}), headers {self.abi_version} (core {abi.CL_ABI_VERSION}); '
+                                    'rebuild the extension')
+        self._lib = lib
+        return lib
+
+    def check(self, rc: int):
+        if rc != 0:
+            raise EngineError(rc, getattr(self.load(), f'{self.prefix}_last_error')().decode(errors='replace'))
+
+    def rollout(self, *args):
+        """Call the entry point and raise `EngineError` on a refusal."""
+        self.check(getattr(self.load(), f'{self.prefix}_{self.entry}')(*args))
 
 
-def build_policy(force: bool = False, verbose: bool = False) -> Path:
-    """Compile csrc/cl_policy.hip for gfx950 into the in-tree ``libcitylearn_amd_policy.so``."""
-    return _compile(POLICY_SOURCES, POLICY_LIB_PATH, sorted(CSRC.glob('*.hip')) + sorted(CSRC.glob('*.h')) + [abi.HEADER, POLICY_HEADER], force, verbose)
+# The closed-loop rollout of battery + PV districts (no SLP vectorisation, like the other rollout kernels), the one that also keeps the streaming
+# KPIs, and the one of THERMAL districts (compiled WITH SLP vectorisation like the main unit: the packed thermal unit of cl_full.h wants v_pk_*_f32)
+POLICY = _Extension('policy', 'clpol', 'policy', ['-fno-slp-vectorize'], 'rollout_mlp_f32', PolicyMLP)
+POLICY_KPI = _Extension('policy_kpi', 'clpk', 'policy KPI', ['-fno-slp-vectorize'], 'rollout_mlp_kpi_f32', PolicyMLP, n_kpi=2, headers=[POLICY.header])
+POLICY_FULL = _Extension('policy_full', 'clpf', 'thermal policy', [], 'rollout_mlp_f32', PolicyFullMLP)
+EXTENSIONS = (POLICY, POLICY_KPI, POLICY_FULL)
 
-
-_policy_lib = None
-
-
-def load_policy() -> ctypes.CDLL:
-    """``libcitylearn_amd_policy.so`` (after torch, like `load`); refuses a build from another version of either header."""
-    global _policy_lib
-    if _policy_lib is not None:
-        return _policy_lib
-    import torch  # noqa: F401
-    if not POLICY_LIB_PATH.exists():
-        raise EngineUnavailable(f'{POLICY_LIB_PATH} not found: the policy extension is not built (run __graft_entry__.build())')
-    lib = ctypes.CDLL(str(POLICY_LIB_PATH))
-    vp, i32 = ctypes.c_void_p, ctypes.c_int32
-    lib.clpol_abi_version.restype = ctypes.c_int
-    lib.clpol_core_abi_version.restype = ctypes.c_int
-    lib.clpol_last_error.restype = ctypes.c_char_p
-    lib.clpol_rollout_mlp_f32.restype = ctypes.c_int
-    lib.clpol_rollout_mlp_f32.argtypes = [ctypes.POINTER(Dims), vp, vp, vp, ctypes.POINTER(PolicyMLP), vp, vp, vp, vp, i32, i32, vp]
-    got, core = lib.clpol_abi_version(), lib.clpol_core_abi_version()
-    if got != POLICY_ABI_VERSION or core != abi.CL_ABI_VERSION:
-        raise EngineUnavailable(f'ABI mismatch: policy library {got} (core {core}), headers {POLICY_ABI_VERSION} (core {abi.CL_ABI_VERSION}); '
-                                'rebuild the extension')
-    _policy_lib = lib
-    return lib
-
-
-def check_policy(rc: int):
-    if rc != 0:
-        raise EngineError(rc, load_policy().clpol_last_error().decode(errors='replace'))
-
-
-# The closed-loop rollout that keeps the streaming KPIs (csrc/cl_policy_kpi.hip + cl_policy_kpi.h; include/citylearn_amd_policy_kpi.h): once more a
-# library of its own -- the policy library's export list, ABI version and kernel set stay what they are, like the main library's.
-POLICY_KPI_HEADER = abi.HEADER.parent / 'citylearn_amd_policy_kpi.h'
-POLICY_KPI_SOURCES = [(CSRC / 'cl_policy_kpi.hip', ['-fno-slp-vectorize'])]
-POLICY_KPI_ABI_VERSION = int(re.search(r'#define\s+CLPK_ABI_VERSION\s+(\d+)', POLICY_KPI_HEADER.read_text()).group(1))
-POLICY_KPI_SYMBOLS = sorted(set(re.findall(r'\b(clpk_\w+)\s*\(', abi._strip_comments(POLICY_KPI_HEADER.read_text()))))
-
-
-def build_policy_kpi(force: bool = False, verbose: bool = False) -> Path:
-    """Compile csrc/cl_policy_kpi.hip for gfx950 into the in-tree ``libcitylearn_amd_policy_kpi.so``."""
-    deps = sorted(CSRC.glob('*.hip')) + sorted(CSRC.glob('*.h')) + [abi.HEADER, POLICY_HEADER, POLICY_KPI_HEADER]
-    return _compile(POLICY_KPI_SOURCES, POLICY_KPI_LIB_PATH, deps, force, verbose)
-
-
-_policy_kpi_lib = None
-
-
-def load_policy_kpi() -> ctypes.CDLL:
-    """``libcitylearn_amd_policy_kpi.so`` (after torch, like `load`); refuses a build from another version of its own or the core header."""
-    global _policy_kpi_lib
-    if _policy_kpi_lib is not None:
-        return _policy_kpi_lib
-    import torch  # noqa: F401
-    if not POLICY_KPI_LIB_PATH.exists():
-        raise EngineUnavailable(f'{POLICY_KPI_LIB_PATH} not found: the policy KPI extension is not built (run __graft_entry__.build())')
-    lib = ctypes.CDLL(str(POLICY_KPI_LIB_PATH))
-    vp, i32 = ctypes.c_void_p, ctypes.c_int32
-    lib.clpk_abi_version.restype = ctypes.c_int
-    lib.clpk_core_abi_version.restype = ctypes.c_int
-    lib.clpk_last_error.restype = ctypes.c_char_p
-    lib.clpk_rollout_mlp_kpi_f32.restype = ctypes.c_int
-    lib.clpk_rollout_mlp_kpi_f32.argtypes = [ctypes.POINTER(Dims), vp, vp, vp, ctypes.POINTER(PolicyMLP), vp, vp, vp, vp, vp, vp, i32, i32, vp]
-    got, core = lib.clpk_abi_version(), lib.clpk_core_abi_version()
-    if got != POLICY_KPI_ABI_VERSION or core != abi.CL_ABI_VERSION:
-        raise EngineUnavailable(f'ABI mismatch: policy KPI library {got} (core {core}), headers {POLICY_KPI_ABI_VERSION} (core {abi.CL_ABI_VERSION}); '
-                                'rebuild the extension')
-    _policy_kpi_lib = lib
-    return lib
-
-
-def check_policy_kpi(rc: int):
-    if rc != 0:
-        raise EngineError(rc, load_policy_kpi().clpk_last_error().decode(errors='replace'))
+# The names other code and the tests use: read-only views of the descriptions above (build / load / check read the description, so rebinding one
+# of these changes nothing -- change the description's attribute instead)
+POLICY_LIB_PATH, POLICY_HEADER, POLICY_SOURCES, POLICY_ABI_VERSION, POLICY_SYMBOLS = POLICY.path, POLICY.header, POLICY.sources, POLICY.abi_version, POLICY.symbols
+build_policy, load_policy, check_policy = POLICY.build, POLICY.load, POLICY.check
+POLICY_KPI_LIB_PATH, POLICY_KPI_HEADER, POLICY_KPI_SOURCES, POLICY_KPI_ABI_VERSION, POLICY_KPI_SYMBOLS = \
+    POLICY_KPI.path, POLICY_KPI.header, POLICY_KPI.sources, POLICY_KPI.abi_version, POLICY_KPI.symbols
+build_policy_kpi, load_policy_kpi, check_policy_kpi = POLICY_KPI.build, POLICY_KPI.load, POLICY_KPI.check
+POLICY_FULL_LIB_PATH, POLICY_FULL_HEADER, POLICY_FULL_SOURCES, POLICY_FULL_ABI_VERSION, POLICY_FULL_SYMBOLS = \
+    POLICY_FULL.path, POLICY_FULL.header, POLICY_FULL.sources, POLICY_FULL.abi_version, POLICY_FULL.symbols
+build_policy_full, load_policy_full, check_policy_full = POLICY_FULL.build, POLICY_FULL.load, POLICY_FULL.check
 
 
 def policy_kpi_lds_bytes(nw: int, vec: int) -> int:
@@ -239,51 +216,6 @@ def policy_kpi_lds_bytes(nw: int, vec: int) -> int:
     policy's staged rows [nw][2][3 x 32 + 8] (tests/test_policy_kpi_host.py holds it against the header's formula)."""
     tile = 64 * vec
     return 4 * (8 * nw * tile + 12 * tile + 16 + 8 * 4 * 32 + 5 * 32 + nw * 2 * (3 * 32 + 8))
-
-
-# The closed-loop rollout of THERMAL districts (csrc/cl_policy_full.hip + cl_policy_full.h; include/citylearn_amd_policy_full.h): the fourth product
-# library, one per kernel family.  Compiled WITH SLP vectorisation like the main unit: the packed thermal unit of cl_full.h wants v_pk_*_f32.
-POLICY_FULL_HEADER = abi.HEADER.parent / 'citylearn_amd_policy_full.h'
-POLICY_FULL_SOURCES = [CSRC / 'cl_policy_full.hip']
-POLICY_FULL_ABI_VERSION = int(re.search(r'#define\s+CLPF_ABI_VERSION\s+(\d+)', POLICY_FULL_HEADER.read_text()).group(1))
-POLICY_FULL_SYMBOLS = sorted(set(re.findall(r'\b(clpf_\w+)\s*\(', abi._strip_comments(POLICY_FULL_HEADER.read_text()))))
-
-
-def build_policy_full(force: bool = False, verbose: bool = False) -> Path:
-    """Compile csrc/cl_policy_full.hip for gfx950 into the in-tree ``libcitylearn_amd_policy_full.so``."""
-    deps = sorted(CSRC.glob('*.hip')) + sorted(CSRC.glob('*.h')) + [abi.HEADER, POLICY_FULL_HEADER]
-    return _compile(POLICY_FULL_SOURCES, POLICY_FULL_LIB_PATH, deps, force, verbose)
-
-
-_policy_full_lib = None
-
-
-def load_policy_full() -> ctypes.CDLL:
-    """``libcitylearn_amd_policy_full.so`` (after torch, like `load`); refuses a build from another version of its own or the core header."""
-    global _policy_full_lib
-    if _policy_full_lib is not None:
-        return _policy_full_lib
-    import torch  # noqa: F401
-    if not POLICY_FULL_LIB_PATH.exists():
-        raise EngineUnavailable(f'{POLICY_FULL_LIB_PATH} not found: the thermal policy extension is not built (run __graft_entry__.build())')
-    lib = ctypes.CDLL(str(POLICY_FULL_LIB_PATH))
-    vp, i32 = ctypes.c_void_p, ctypes.c_int32
-    lib.clpf_abi_version.restype = ctypes.c_int
-    lib.clpf_core_abi_version.restype = ctypes.c_int
-    lib.clpf_last_error.restype = ctypes.c_char_p
-    lib.clpf_rollout_mlp_f32.restype = ctypes.c_int
-    lib.clpf_rollout_mlp_f32.argtypes = [ctypes.POINTER(Dims), vp, vp, vp, ctypes.POINTER(PolicyFullMLP), vp, vp, vp, vp, i32, i32, vp]
-    got, core = lib.clpf_abi_version(), lib.clpf_core_abi_version()
-    if got != POLICY_FULL_ABI_VERSION or core != abi.CL_ABI_VERSION:
-        raise EngineUnavailable(f'ABI mismatch: thermal policy library {got} (core {core}), headers {POLICY_FULL_ABI_VERSION} (core {abi.CL_ABI_VERSION}); '
-                                'rebuild the extension')
-    _policy_full_lib = lib
-    return lib
-
-
-def check_policy_full(rc: int):
-    if rc != 0:
-        raise EngineError(rc, load_policy_full().clpf_last_error().decode(errors='replace'))
 
 
 def policy_full_lds_bytes(nw: int, vec: int) -> int:

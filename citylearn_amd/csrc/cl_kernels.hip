@@ -1585,38 +1585,6 @@ extern "C" __attribute__((visibility("hidden"))) int cl_tu_launch_lean(int vec, 
 
 namespace {
 
-int check_dims(const cl_dims* d) {
-    if (!d) return fail(CL_ENULL, "dims is NULL");
-    if (d->n_env <= 0 || d->n_bldg <= 0 || d->n_steps <= 0 || d->n_act_cols < 0)
-        return fail(CL_EINVAL, "bad dims: n_env=%d n_bldg=%d n_steps=%d n_act_cols=%d", d->n_env, d->n_bldg,
-                    d->n_steps, d->n_act_cols);
-    if (d->n_env % 4 != 0) return fail(CL_EALIGN, "n_env=%d must be a multiple of 4 (pad the env batch)", d->n_env);
-    if (d->n_ts_rows != 0 && d->n_ts_rows < d->n_steps)
-        return fail(CL_EINVAL, "n_ts_rows=%d < n_steps=%d", d->n_ts_rows, d->n_steps);
-    if (reinterpret_cast<uintptr_t>(d->env_row0) & 3) return fail(CL_EALIGN, "env_row0 is not 4-byte aligned");
-    if (d->env_pitch != 0 && (d->env_pitch < d->n_env || d->env_pitch % 4 != 0))
-        return fail(CL_EINVAL, "env_pitch=%d must be 0 or a multiple of 4 >= n_env=%d", d->env_pitch, d->n_env);
-    const uint32_t rk = (d->flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT;
-    if (rk > CLR_EV) return fail(CL_EINVAL, "unknown reward kind %u", rk);
-    // the Philox counter word of the random streams is env_offset + env (32 bits): shards must not alias
-    if (d->env_offset < 0 || d->env_offset + (int64_t)d->n_env > (int64_t)1 << 32)
-        return fail(CL_ERANGE, "env_offset=%lld with n_env=%d leaves the 32-bit env index of the random streams", (long long)d->env_offset, d->n_env);
-    return CL_OK;
-}
-
-// cl_dims.env_pitch (0 = n_env); entry points that do not implement a pitch refuse one
-int pitch_of(const cl_dims* d) { return d->env_pitch ? d->env_pitch : d->n_env; }
-int no_pitch(const cl_dims* d, const char* who) {
-    if (pitch_of(d) != d->n_env) return fail(CL_EINVAL, "%s: env_pitch=%d != n_env=%d is not implemented for this call", who, d->env_pitch, d->n_env);
-    return CL_OK;
-}
-
-int check_ptr(const void* p, const char* name, bool required = true) {
-    if (!p) return required ? fail(CL_ENULL, "%s is NULL", name) : CL_OK;
-    if (reinterpret_cast<uintptr_t>(p) & 15) return fail(CL_EALIGN, "%s is not 16-byte aligned", name);
-    return CL_OK;
-}
-
 // Launch-geometry overrides travel with every call (cl_dims.tuning, include/citylearn_amd.h): the library holds no
 // mutable state besides the thread-local error string.
 const cl_tuning k_default_tuning = {};

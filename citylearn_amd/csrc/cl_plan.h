@@ -22,6 +22,41 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
+// The entry points' argument checks (`inline`: not every unit that includes this header calls them).
+// cl_dims as every entry point checks it.  `pitch` = false leaves env_pitch to the caller: the policy libraries' entry points take none and
+// say so in words of their own, behind their other refusals.
+inline int check_dims(const cl_dims* d, bool pitch = true) {
+    if (!d) return fail(CL_ENULL, "dims is NULL");
+    if (d->n_env <= 0 || d->n_bldg <= 0 || d->n_steps <= 0 || d->n_act_cols < 0)
+        return fail(CL_EINVAL, "bad dims: n_env=%d n_bldg=%d n_steps=%d n_act_cols=%d", d->n_env, d->n_bldg,
+                    d->n_steps, d->n_act_cols);
+    if (d->n_env % 4 != 0) return fail(CL_EALIGN, "n_env=%d must be a multiple of 4 (pad the env batch)", d->n_env);
+    if (d->n_ts_rows != 0 && d->n_ts_rows < d->n_steps)
+        return fail(CL_EINVAL, "n_ts_rows=%d < n_steps=%d", d->n_ts_rows, d->n_steps);
+    if (reinterpret_cast<uintptr_t>(d->env_row0) & 3) return fail(CL_EALIGN, "env_row0 is not 4-byte aligned");
+    if (pitch && d->env_pitch != 0 && (d->env_pitch < d->n_env || d->env_pitch % 4 != 0))
+        return fail(CL_EINVAL, "env_pitch=%d must be 0 or a multiple of 4 >= n_env=%d", d->env_pitch, d->n_env);
+    const uint32_t rk = (d->flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT;
+    if (rk > CLR_EV) return fail(CL_EINVAL, "unknown reward kind %u", rk);
+    // the Philox counter word of the random streams is env_offset + env (32 bits): shards must not alias
+    if (d->env_offset < 0 || d->env_offset + (int64_t)d->n_env > (int64_t)1 << 32)
+        return fail(CL_ERANGE, "env_offset=%lld with n_env=%d leaves the 32-bit env index of the random streams", (long long)d->env_offset, d->n_env);
+    return CL_OK;
+}
+
+// cl_dims.env_pitch (0 = n_env); entry points that do not implement a pitch refuse one
+inline int pitch_of(const cl_dims* d) { return d->env_pitch ? d->env_pitch : d->n_env; }
+inline int no_pitch(const cl_dims* d, const char* who) {
+    if (pitch_of(d) != d->n_env) return fail(CL_EINVAL, "%s: env_pitch=%d != n_env=%d is not implemented for this call", who, d->env_pitch, d->n_env);
+    return CL_OK;
+}
+
+inline int check_ptr(const void* p, const char* name, bool required = true) {
+    if (!p) return required ? fail(CL_ENULL, "%s is NULL", name) : CL_OK;
+    if (reinterpret_cast<uintptr_t>(p) & 15) return fail(CL_EALIGN, "%s is not 16-byte aligned", name);
+    return CL_OK;
+}
+
 constexpr int CL_OBS_FUSED_BLDG = 32;          // buildings a fused observation list can address (= the lean kernel's 2 x 16)
 // largest launch (env x building units) whose plane stores carry the non-temporal hint (see pstore)
 constexpr long long CL_NT_MAX_UNITS = 3ll << 20;

@@ -1,7 +1,9 @@
 // cl_policy.h -- mode B with a CLOSED-LOOP policy: the battery + PV K-step loop of cl_rollout_kernel<VEC, false, 2> (cl_rollout.h) whose
 // electrical-storage action of every (env, building, step) is a one-hidden-layer tanh MLP over that building's own observation vector, evaluated
 // inside the loop from the two observations that depend on the env -- the unit's soc before the step and its net of the previous step, both in
-// registers already.  Included by cl_policy.hip only (libcitylearn_amd_policy.so, include/citylearn_amd_policy.h), behind cl_kernels.hip's helpers.
+// registers already.  Included by cl_policy.hip (libcitylearn_amd_policy.so, include/citylearn_amd_policy.h) and, for the staged-row layout and the two lean
+// entry points' shared host checks, by cl_policy_kpi.hip; behind cl_kernels.hip's helpers.  PolicyArgs, the hidden unit and the Box-Muller draw are
+// cl_policy_common.h's, shared with the thermal policy kernel too.
 //
 // The split (cl_lstm.h's `dyn_pre`, for an MLP): a building's observation is obs[c] = table[row][c] + col_scale[c] * plane[c] with a plane for two
 // columns only, so  W1 obs + b1 = pre[row] + ws * soc + wn * net_prev  with `pre` one H-vector per (parameter set, table row, building) the host
@@ -24,27 +26,13 @@
 // LDS per workgroup: the district reduction's [nw][NQ][tile] rows (MARL's exchange row and the return rows alias them) + nw x 2 x CLPOL_ROW floats:
 // 49 KiB at the largest geometry (nw = 16, two envs per lane); the host refuses anything beyond the CU's 160 KiB.
 #pragma once
+#include "cl_policy_common.h"
 
 #ifdef __HIPCC__
 namespace {
 
 constexpr int CLPOL_MAX_H = 32;
 constexpr int CLPOL_ROW = 3 * CLPOL_MAX_H + 8;       // floats of one building's staged row: [H/4][3][4] weights | bias, mid, half, sigma, low, high, pad x 2
-
-struct PolicyArgs {
-    RolloutArgs r;                         // r.s.actions == NULL, r.act_low / r.act_high: the columns' bounds, r.seed: ALREADY xor CLPOL_NOISE_KEY
-    const float* __restrict__ pre;         // [n_sets][n_rows][n_bldg][H]
-    const float* __restrict__ dep;         // [n_sets][n_bldg][2][H]
-    const float* __restrict__ out;         // [n_sets][n_bldg][H + 1]
-    const int32_t* __restrict__ set_of_block;
-    const float* __restrict__ net_reset;   // [n_rows][n_bldg] or NULL
-    const float* __restrict__ sigma;       // [n_act_cols] or NULL
-    float* __restrict__ traj;              // [K][CLPOL_NT][n_bldg][n_env] or NULL
-    int n_rows, n_hidden;
-};
-
-typedef float clpol_f4 __attribute__((ext_vector_type(4)));
-typedef const clpol_f4 __attribute__((address_space(4)))* clpol_c4ptr;
 
 constexpr size_t rollout_policy_lds_floats(int nw, int tile) { return (size_t)nw * NQ * tile + (size_t)nw * 2 * CLPOL_ROW; }
 
@@ -170,9 +158,7 @@ __global__ void __launch_bounds__(1024) cl_rollout_policy_kernel(const PolicyArg
                     for (int u = 0; u < 4; ++u) {
 #pragma unroll
                         for (int i = 0; i < VEC; ++i) {
-                            const float z = fmaf(wn[u], last_net[m][i], fmaf(ws[u], St[m][i].soc, pj[u]));
-                            const float e = __builtin_amdgcn_exp2f(fminf(z, 64.0f));
-                            acc[i] = fmaf(wo[u], (1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e), acc[i]);
+                            acc[i] = fmaf(wo[u], clpol_unit(fmaf(wn[u], last_net[m][i], fmaf(ws[u], St[m][i].soc, pj[u]))), acc[i]);
                         }
                     }
                 }
@@ -191,11 +177,7 @@ __global__ void __launch_bounds__(1024) cl_rollout_policy_kernel(const PolicyArg
                     }
 #pragma unroll
                     for (int i = 0; i < VEC; ++i) {
-                        const uint32_t w0 = rnd[m][i].w0, w1 = rnd[m][i].w1, w2 = rnd[m][i].w2, w3 = rnd[m][i].w3;
-                        const float u1 = cl::u01((t & 1) ? w2 : w0) + 0x1p-25f, u2 = cl::u01((t & 1) ? w3 : w1);
-                        // v_log_f32 is log2, v_cos_f32 takes revolutions
-                        const float rad = __builtin_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1));
-                        a_es[i] = fmaf(sg, rad * __builtin_amdgcn_cosf(u2), a_es[i]);
+                        a_es[i] = fmaf(sg, clpol_gauss(rnd[m][i].w0, rnd[m][i].w1, rnd[m][i].w2, rnd[m][i].w3, t), a_es[i]);
                     }
                 }
 #pragma unroll
@@ -304,6 +286,27 @@ __global__ void __launch_bounds__(1024) cl_rollout_policy_kernel(const PolicyArg
             if (tile_env0 + e < a.n_env) r.ret_env[tile_env0 + e] += s;
         }
     }
+}
+
+// ---- host: what clpol_rollout_mlp_f32 and clpk_rollout_mlp_kpi_f32 share beyond cl_policy_common.h ----
+int check_lean_policy_mlp(const clpol_mlp* mlp) {
+    if (!mlp) return fail(CL_ENULL, "mlp is NULL");
+    if (int rc = check_policy_sizes(*mlp, CLPOL_MAX_HIDDEN)) return rc;
+    if (mlp->flags || mlp->reserved) return fail(CL_EINVAL, "clpol_mlp.flags / .reserved must be 0");
+    return CL_OK;
+}
+
+// The lean rollout's geometry: two buildings per wave, two envs per lane where the 128-env workgroups come in (nearly) full rounds of one per CU
+// (`what`: "policy" or "policy KPI", for the refusal)
+int lean_policy_geometry(const cl_dims* dims, const cl_tuning& tun, const char* what, int& nw, int& vec) {
+    nw = tun.nw ? tun.nw : (dims->n_bldg + 1) / 2;
+    // (nw > n_bldg: a wave without any building would read its parameter row -- row `w` -- past the end of the table)
+    if (nw * 2 < dims->n_bldg || nw < 1 || nw > 16 || nw > dims->n_bldg) return fail(CL_EINVAL, "bad nw %d", nw);
+    const long long wg2 = (dims->n_env + 127) / 128, rounds2 = (wg2 + 255) / 256;
+    const bool full_rounds = dims->n_env >= 32768 && wg2 * 100 >= rounds2 * 256 * 85;
+    vec = tun.vec ? tun.vec : (full_rounds ? 2 : 1);
+    if (vec != 1 && vec != 2) return fail(CL_EINVAL, "no %s rollout kernel at %d envs per lane", what, vec);
+    return CL_OK;
 }
 
 }  // namespace

@@ -7,7 +7,7 @@
 //     h_j    = tanh(pre[s][r][b][j] + sum_d dep[s][b][d][j] x_d)            x = (soc, cs, hs, ds, net_prev)
 //     mean_a = mid_a + half_a tanh(out[s][b][a][H] + sum_j out[s][b][a][j] h_j)       a over the heads (es, cs, hs, ds)
 //     act_a  = clamp(mean_a + sigma_a z_a, low_a, high_a)
-// The pieces are cl_policy.h's: `pre` through the constant address space (s_load_dwordx4 per four units); `dep` / `out` / bounds / sigma staged
+// The pieces are cl_policy.h's (the hidden unit and the Box-Muller draw literally: cl_policy_common.h): `pre` through the constant address space (s_load_dwordx4 per four units); `dep` / `out` / bounds / sigma staged
 // once per launch in the wave's own LDS row and read back as broadcast 16-byte reads; a hidden unit as (1 - e) / (1 + e), e = v_exp_f32 of the
 // pre-scaled sum; tanhf for the output units; Box-Muller on the column's Philox stream.  What differs:
 //  * Which terms and heads exist is a property of the BUILDING (its CLF_* storage flags, its action columns), hence wave-uniform: per group of four
@@ -19,6 +19,7 @@
 // LDS per workgroup: the district reduction's [nw][NQ][tile] rows (MARL's exchange row and the return rows alias them) + nw x CLPF_ROW floats:
 // 52 KiB at the largest geometry (nw = 16, two envs per lane); the host refuses anything beyond the CU's 160 KiB.
 #pragma once
+#include "cl_policy_common.h"
 
 #ifdef __HIPCC__
 namespace {
@@ -27,32 +28,13 @@ constexpr int CLPF_GROUP = 4 * (CLPF_ND + CLPF_NA);            // floats of one 
 constexpr int CLPF_HEADS = CLPF_GROUP * (CLPF_MAX_HIDDEN / 4);  // where the heads' {bias, mid, half, sigma | low, high, -, -} start
 constexpr int CLPF_ROW = CLPF_HEADS + 8 * CLPF_NA;              // floats of one building's staged row
 
-struct PolicyFullArgs {
-    RolloutArgs r;                         // r.s.actions == NULL, r.act_low / r.act_high: the columns' bounds, r.seed: ALREADY xor CLPF_NOISE_KEY
-    const float* __restrict__ pre;         // [n_sets][n_rows][n_bldg][H]
-    const float* __restrict__ dep;         // [n_sets][n_bldg][CLPF_ND][H]
-    const float* __restrict__ out;         // [n_sets][n_bldg][CLPF_NA][H + 1]
-    const int32_t* __restrict__ set_of_block;
-    const float* __restrict__ net_reset;   // [n_rows][n_bldg] or NULL
-    const float* __restrict__ sigma;       // [n_act_cols] or NULL
-    float* __restrict__ traj;              // [K][CLPF_NT][n_bldg][n_env] or NULL
-    int n_rows, n_hidden;
-};
-
-typedef float clpf_f4 __attribute__((ext_vector_type(4)));
-typedef const clpf_f4 __attribute__((address_space(4)))* clpf_c4ptr;
-
 constexpr size_t rollout_full_policy_lds_floats(int nw, int tile) { return (size_t)nw * NQ * tile + (size_t)nw * CLPF_ROW; }
 
-// a hidden unit's activation on the pre-scaled sum (cl_policy.h's form; the min keeps e finite: (1 - inf) * 0 is a NaN)
-CL_DEV float clpf_unit(float z) {
-    const float e = __builtin_amdgcn_exp2f(fminf(z, 64.0f));
-    return (1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e);
-}
-CL_DEV clv::f2 clpf_unit(clv::f2 z) { clv::f2 r; r.x = clpf_unit(z.x); r.y = clpf_unit(z.y); return r; }
+// cl_policy_common.h's hidden unit on the packed pair
+CL_DEV clv::f2 clpol_unit(clv::f2 z) { clv::f2 r; r.x = clpol_unit(z.x); r.y = clpol_unit(z.y); return r; }
 
 template <int VEC, int PREC, bool MARL>
-__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) cl_rollout_full_policy_kernel(const PolicyFullArgs p) {
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) cl_rollout_full_policy_kernel(const PolicyArgs p) {
     extern __shared__ __attribute__((aligned(16))) float lds[];     // [nw][NQ][64*VEC] | [nw][CLPF_ROW]
     using F = typename Vec<VEC>::type;
     const RolloutArgs& r = p.r;
@@ -129,16 +111,16 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
         // ---- the policy: this building's storage actions from (table row, soc, cs, hs, ds, previous net) ----
         clv::Ac<F> act = {zero, zero, zero, zero, zero, zero};
         {
-            const clpf_c4ptr pq = (clpf_c4ptr)(const clpf_f4*)(pre_w + (long long)t * a.n_bldg * H);
+            const clpol_c4ptr pq = (clpol_c4ptr)(const clpol_f4*)(pre_w + (long long)t * a.n_bldg * H);
             F acc_es = zero, acc_cs = zero, acc_hs = zero, acc_ds = zero;
 #pragma unroll 1
             for (int g = 0; g < H; g += 4) {
                 const float* grp = row + (g >> 2) * CLPF_GROUP;
-                const clpf_f4 pj = pq[g >> 2];
+                const clpol_f4 pj = pq[g >> 2];
                 F z[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) z[u] = (F)(pj[u]);
-#define CLPF_TERM(d, x) { const clpf_f4 wd = *reinterpret_cast<const clpf_f4*>(grp + 4 * (d)); \
+#define CLPF_TERM(d, x) { const clpol_f4 wd = *reinterpret_cast<const clpol_f4*>(grp + 4 * (d)); \
                           _Pragma("unroll") for (int u = 0; u < 4; ++u) z[u] = clv::vfma((F)(wd[u]), x, z[u]); }
                 if (flags & CLF_BATTERY) CLPF_TERM(CLPF_D_SOC, S.soc)
                 if (flags & CLF_COOL_STO) CLPF_TERM(CLPF_D_CS, S.cs)
@@ -147,8 +129,8 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
                 CLPF_TERM(CLPF_D_NET, last_net)
 #undef CLPF_TERM
 #pragma unroll
-                for (int u = 0; u < 4; ++u) z[u] = clpf_unit(z[u]);
-#define CLPF_HEAD(h, acc) { const clpf_f4 wo = *reinterpret_cast<const clpf_f4*>(grp + 4 * (CLPF_ND + (h))); \
+                for (int u = 0; u < 4; ++u) z[u] = clpol_unit(z[u]);
+#define CLPF_HEAD(h, acc) { const clpol_f4 wo = *reinterpret_cast<const clpol_f4*>(grp + 4 * (CLPF_ND + (h))); \
                             _Pragma("unroll") for (int u = 0; u < 4; ++u) acc = clv::vfma((F)(wo[u]), z[u], acc); }
                 if (c_es >= 0) CLPF_HEAD(CLPF_A_ES, acc_es)
                 if (c_cs >= 0) CLPF_HEAD(CLPF_A_CS, acc_cs)
@@ -160,7 +142,7 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
             for (int h = 0; h < CLPF_NA; ++h) {
                 const int col = h == CLPF_A_ES ? c_es : h == CLPF_A_CS ? c_cs : h == CLPF_A_HS ? c_hs : c_ds;
                 if (col < 0) continue;                                   // wave-uniform
-                const clpf_f4 hp = *reinterpret_cast<const clpf_f4*>(row + CLPF_HEADS + 8 * h);      // bias, mid, half, sigma
+                const clpol_f4 hp = *reinterpret_cast<const clpol_f4*>(row + CLPF_HEADS + 8 * h);      // bias, mid, half, sigma
                 const float lo = row[CLPF_HEADS + 8 * h + 4], hi = row[CLPF_HEADS + 8 * h + 5];
                 const F acc = h == CLPF_A_ES ? acc_es : h == CLPF_A_CS ? acc_cs : h == CLPF_A_HS ? acc_hs : acc_ds;
                 float v[VEC];
@@ -174,15 +156,10 @@ __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4))) 
                 const float sg_lane = hp[3];
                 const float sg = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sg_lane)));
                 if (sg != 0.0f) {                                        // wave-uniform
-                    // Box-Muller on two draws of the column's stream: counters 2t and 2t + 1 = words (0, 1) or (2, 3) of block t >> 1
 #pragma unroll
-                    for (int i = 0; i < VEC; ++i) {
+                    for (int i = 0; i < VEC; ++i) {                      // (no cache: the block is drawn every step)
                         const cl::U4 bk = cl::philox_block(r.seed, (uint32_t)(env0 + i) + a.env_offset, (uint32_t)col, (uint32_t)t >> 1);
-                        const uint32_t w0 = bk.w[0], w1 = bk.w[1], w2 = bk.w[2], w3 = bk.w[3];
-                        const float u1 = cl::u01((t & 1) ? w2 : w0) + 0x1p-25f, u2 = cl::u01((t & 1) ? w3 : w1);
-                        // v_log_f32 is log2, v_cos_f32 takes revolutions
-                        const float rad = __builtin_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1));
-                        v[i] = fmaf(sg, rad * __builtin_amdgcn_cosf(u2), v[i]);
+                        v[i] = fmaf(sg, clpol_gauss(bk.w[0], bk.w[1], bk.w[2], bk.w[3], t), v[i]);
                     }
                 }
                 F av;

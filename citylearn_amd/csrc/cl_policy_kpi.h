@@ -2,14 +2,15 @@
 // the action source of cl_rollout_policy_kernel (cl_policy.h).  Included by cl_policy_kpi.hip only (libcitylearn_amd_policy_kpi.so,
 // include/citylearn_amd_policy_kpi.h), behind cl_kernels.hip's helpers, cl_rollout.h and cl_policy.h.
 //
-// Nothing here is new arithmetic: a step is the two existing kernels' step, statement for statement, and every accumulation keeps their order --
-// they are what tests/test_gpu_policy_kpi_rollout.py compares this kernel with.
+// Nothing here is new arithmetic, and every accumulation keeps the order of the two kernels that tests/test_gpu_policy_kpi_rollout.py compares this
+// one with.
 //  * From cl_rollout_kpi_kernel: the four control sums per unit in registers; the control / baseline district series in LDS (kpi_series_get / _put /
 //    _advance); the S = 8 ring of wave partial nets folded in wave order; the env block's `brow` / `bsum` baseline rows kept by its head workgroup;
 //    MARL reading the ring slot it just wrote behind ONE barrier per step; tables through the constant address space.
-//  * From cl_rollout_policy_kernel: `pre` through s_load_dwordx4; `dep` / `out` / the column's bounds staged once per launch in each wave's own LDS
-//    rows and read back as broadcast ds_read_b128; the v_exp_f32 / v_rcp_f32 hidden tanh; Box-Muller noise on the stream keyed
-//    seed ^ CLPOL_NOISE_KEY; set_of_block; net_reset at t == 0 and the previous launch's out_bldg[CLO_NET] otherwise; the optional record.
+//  * From cl_rollout_policy_kernel, written out again (as shared functions these pieces changed the generated code of both kernels,
+//    profiles/policy_refactor_isa.md): `pre` through s_load_dwordx4; `dep` / `out` / the column's bounds staged once per launch in each wave's own LDS
+//    rows and read back as broadcast ds_read_b128; Box-Muller noise on the stream keyed seed ^ CLPOL_NOISE_KEY; set_of_block; net_reset at t == 0 and
+//    the previous launch's out_bldg[CLO_NET] otherwise; the optional record.  The hidden unit and the Box-Muller draw are cl_policy_common.h's.
 // LDS per workgroup: cl_rollout_kpi_kernel's region (rollout_kpi_lds_floats) followed by nw x 2 x CLPOL_ROW floats (rollout_policy_kpi_lds_floats):
 // 55 296 bytes at 17 buildings (nw = 9) and two envs per lane, 89 792 at the largest geometry (nw = 16, two envs per lane); above 64 KiB -- from
 // nw = 12 at two envs per lane -- the launch opts in, above the CU's 160 KiB the host refuses.
@@ -178,9 +179,7 @@ __global__ void __launch_bounds__(1024) cl_rollout_policy_kpi_kernel(const Polic
                     for (int u = 0; u < 4; ++u) {
 #pragma unroll
                         for (int i = 0; i < VEC; ++i) {
-                            const float z = fmaf(wn[u], last_net[m][i], fmaf(ws[u], St[m][i].soc, pj[u]));
-                            const float e = __builtin_amdgcn_exp2f(fminf(z, 64.0f));
-                            acc[i] = fmaf(wo[u], (1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e), acc[i]);
+                            acc[i] = fmaf(wo[u], clpol_unit(fmaf(wn[u], last_net[m][i], fmaf(ws[u], St[m][i].soc, pj[u]))), acc[i]);
                         }
                     }
                 }
@@ -199,11 +198,7 @@ __global__ void __launch_bounds__(1024) cl_rollout_policy_kpi_kernel(const Polic
                     }
 #pragma unroll
                     for (int i = 0; i < VEC; ++i) {
-                        const uint32_t w0 = rnd[m][i].w0, w1 = rnd[m][i].w1, w2 = rnd[m][i].w2, w3 = rnd[m][i].w3;
-                        const float u1 = cl::u01((t & 1) ? w2 : w0) + 0x1p-25f, u2 = cl::u01((t & 1) ? w3 : w1);
-                        // v_log_f32 is log2, v_cos_f32 takes revolutions
-                        const float rad = __builtin_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1));
-                        a_es[i] = fmaf(sg, rad * __builtin_amdgcn_cosf(u2), a_es[i]);
+                        a_es[i] = fmaf(sg, clpol_gauss(rnd[m][i].w0, rnd[m][i].w1, rnd[m][i].w2, rnd[m][i].w3, t), a_es[i]);
                     }
                 }
 #pragma unroll

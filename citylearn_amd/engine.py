@@ -520,7 +520,9 @@ class StepEngine:
             # (the library cannot see this: a battery + PV district with EV chargers / washing machines and a non-EV reward has CLD_LEAN set)
             raise NotImplementedError('rollout_policy: districts with flexible loads (EV chargers / washing machines) are not covered by the policy '
                                       'kernel -- it would leave their consumption out of net; use step() / capture_rollout')
-        lib = _lib.load_policy_full() if storage else _lib.load_policy_kpi() if kpi else _lib.load_policy()
+        ext = _lib.POLICY_FULL if storage else _lib.POLICY_KPI if kpi else _lib.POLICY
+        ext.load()          # (here, not only inside ext.rollout: a missing library is reported in front of the argument checks below)
+        kpi_planes = (_ptr(self.kpi_bldg), _ptr(self.kpi_env)) if kpi else ()
         n_planes = _policy.CLPF_NT if storage else _policy.CLPOL_NT
         t0 = self.t if t0 is None else t0
         pt = policy_tables
@@ -536,18 +538,8 @@ class StepEngine:
                 raise ValueError(f'{name} must be a contiguous float32 tensor {shape} on {self.device}')
         mlp = pt.struct(seed)
         with torch.cuda.device(self.device):
-            if storage:
-                _lib.check_policy_full(lib.clpf_rollout_mlp_f32(ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), ctypes.byref(mlp),
-                                                                _ptr(self.out_bldg), _ptr(self._out_env), _ptr(ret_env), _ptr(traj), int(t0), int(k_steps),
-                                                                self._stream()))
-            elif kpi:
-                _lib.check_policy_kpi(lib.clpk_rollout_mlp_kpi_f32(
-                    ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), ctypes.byref(mlp), _ptr(self.out_bldg),
-                    _ptr(self._out_env), _ptr(ret_env), _ptr(traj), _ptr(self.kpi_bldg), _ptr(self.kpi_env), int(t0), int(k_steps), self._stream()))
-            else:
-                _lib.check_policy(lib.clpol_rollout_mlp_f32(ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), ctypes.byref(mlp),
-                                                            _ptr(self.out_bldg), _ptr(self._out_env), _ptr(ret_env), _ptr(traj), int(t0), int(k_steps),
-                                                            self._stream()))
+            ext.rollout(ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), ctypes.byref(mlp), _ptr(self.out_bldg),
+                        _ptr(self._out_env), _ptr(ret_env), _ptr(traj), *kpi_planes, int(t0), int(k_steps), self._stream())
         self._pending_t = None
         self.t = t0 + k_steps
 

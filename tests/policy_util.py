@@ -111,3 +111,10 @@ def f32_torch_deviation(pol, x, pt, device='cpu', noise=None):
         a = a + t(pt.sigma_bldg) * t(noise)
     a = torch.clamp(a, lo, hi)
     return float(np.abs(a.cpu().numpy().astype(np.float64) - ref).max())
+
+
+def exports(path):
+    """The dynamic symbols a shared library defines (`nm -D --defined-only`), sorted."""
+    import subprocess
+    out = subprocess.run(['nm', '-D', '--defined-only', str(path)], capture_output=True, text=True, check=True).stdout
+    return sorted(line.split()[-1] for line in out.splitlines() if ' T ' in line)

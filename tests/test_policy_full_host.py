@@ -4,7 +4,6 @@ validation (before any HIP call), registers / scratch / LDS of every instantiati
 unsplit MLP in float64, its refusals, and the conditioning of the closed loop the GPU tests run (tests/test_gpu_policy_full_rollout.py)."""
 import ctypes
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ from golden_util import golden
 from citylearn_amd import _lib, abi, policy
 from citylearn_amd.observations import ObservationLayout
 from policy_full_util import HostObservations5, f32_torch_deviation, host_closed_loop, make_storage_policy, thermal_district
+from policy_util import exports
 from test_isa_guards import _asm
 
 
@@ -30,9 +30,7 @@ def lib():
 # ---- 1. the library -------------------------------------------------------------------------------------------------------------------
 def test_library_exports_exactly_the_header(lib):
     assert _lib.POLICY_FULL_SYMBOLS == ['clpf_abi_version', 'clpf_core_abi_version', 'clpf_last_error', 'clpf_rollout_mlp_f32']
-    out = subprocess.run(['nm', '-D', '--defined-only', str(_lib.POLICY_FULL_LIB_PATH)], capture_output=True, text=True, check=True).stdout
-    names = sorted(line.split()[-1] for line in out.splitlines() if ' T ' in line)
-    assert names == _lib.POLICY_FULL_SYMBOLS, names
+    assert exports(_lib.POLICY_FULL_LIB_PATH) == _lib.POLICY_FULL_SYMBOLS
     assert lib.clpf_abi_version() == _lib.POLICY_FULL_ABI_VERSION == 1 and lib.clpf_core_abi_version() == abi.CL_ABI_VERSION
     assert not [k for k in abi.CONSTANTS if k.startswith('CLPF')] and not [k for k in policy.CONSTANTS if k.startswith('CLPF')]
 

@@ -4,7 +4,6 @@ any HIP call), the generated gfx950 code of every instantiation, the packer's sp
 the conditioning of the closed loop the GPU tests run (tests/test_gpu_policy_rollout.py)."""
 import ctypes
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,7 +12,7 @@ import torch
 from golden_util import golden
 from citylearn_amd import _lib, abi, policy
 from citylearn_amd.observations import ObservationLayout
-from policy_util import HostObservations, f32_torch_deviation, host_closed_loop, make_policy
+from policy_util import HostObservations, exports, f32_torch_deviation, host_closed_loop, make_policy
 from test_isa_guards import _asm, _count
 
 
@@ -30,14 +29,12 @@ def lib():
 # ---- 1. the library -------------------------------------------------------------------------------------------------------------------
 def test_policy_library_exports_exactly_the_header(lib):
     assert _lib.POLICY_SYMBOLS == ['clpol_abi_version', 'clpol_core_abi_version', 'clpol_last_error', 'clpol_rollout_mlp_f32']
-    out = subprocess.run(['nm', '-D', '--defined-only', str(_lib.POLICY_LIB_PATH)], capture_output=True, text=True, check=True).stdout
-    names = sorted(line.split()[-1] for line in out.splitlines() if ' T ' in line)
-    assert names == _lib.POLICY_SYMBOLS, names
+    assert exports(_lib.POLICY_LIB_PATH) == _lib.POLICY_SYMBOLS
     assert lib.clpol_abi_version() == _lib.POLICY_ABI_VERSION == 1 and lib.clpol_core_abi_version() == abi.CL_ABI_VERSION
     # the main library is what it was: its own symbols, nothing of this feature
     _lib.build()
-    out = subprocess.run(['nm', '-D', '--defined-only', str(_lib.LIB_PATH)], capture_output=True, text=True, check=True).stdout
-    assert sorted(line.split()[-1] for line in out.splitlines() if ' T ' in line) == abi.EXPORTED_SYMBOLS and 'clpol' not in out
+    main = exports(_lib.LIB_PATH)
+    assert main == abi.EXPORTED_SYMBOLS and not [s for s in main if 'clpol' in s]
     assert len(abi.EXPORTED_SYMBOLS) == 15 and not [k for k in abi.CONSTANTS if k.startswith('CLPOL')]
 
 

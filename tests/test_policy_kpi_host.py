@@ -3,13 +3,13 @@ csrc/cl_policy_kpi.h, library ``libcitylearn_amd_policy_kpi.so``) as far as it c
 argument validation (before any HIP call), the generated gfx950 code of every instantiation the host can select, and the LDS formula."""
 import ctypes
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from citylearn_amd import _lib, abi
 from test_isa_guards import _asm, _count
+from policy_util import exports
 from test_policy_host import _dims
 
 KPI = abi.CLD_LEAN | abi.CLD_KPI
@@ -25,22 +25,17 @@ def lib():
     return lib
 
 
-def _exports(path):
-    out = subprocess.run(['nm', '-D', '--defined-only', str(path)], capture_output=True, text=True, check=True).stdout
-    return sorted(line.split()[-1] for line in out.splitlines() if ' T ' in line)
-
-
 # ---- 1. the libraries -----------------------------------------------------------------------------------------------------------------
 def test_three_libraries_export_exactly_their_headers(lib):
     assert _lib.POLICY_KPI_SYMBOLS == ['clpk_abi_version', 'clpk_core_abi_version', 'clpk_last_error', 'clpk_rollout_mlp_kpi_f32']
-    assert _exports(_lib.POLICY_KPI_LIB_PATH) == _lib.POLICY_KPI_SYMBOLS
+    assert exports(_lib.POLICY_KPI_LIB_PATH) == _lib.POLICY_KPI_SYMBOLS
     assert lib.clpk_abi_version() == _lib.POLICY_KPI_ABI_VERSION == 1 and lib.clpk_core_abi_version() == abi.CL_ABI_VERSION
     # the policy library and the main library are what they were
     _lib.build_policy()
-    assert _exports(_lib.POLICY_LIB_PATH) == _lib.POLICY_SYMBOLS == ['clpol_abi_version', 'clpol_core_abi_version', 'clpol_last_error', 'clpol_rollout_mlp_f32']
+    assert exports(_lib.POLICY_LIB_PATH) == _lib.POLICY_SYMBOLS == ['clpol_abi_version', 'clpol_core_abi_version', 'clpol_last_error', 'clpol_rollout_mlp_f32']
     assert _lib.POLICY_ABI_VERSION == 1
     _lib.build()
-    main = _exports(_lib.LIB_PATH)
+    main = exports(_lib.LIB_PATH)
     assert main == abi.EXPORTED_SYMBOLS and len(main) == 15 and not [s for s in main if s.startswith(('clpol_', 'clpk_'))]
     assert not [k for k in abi.CONSTANTS if k.startswith(('CLPOL', 'CLPK'))]
 
@@ -164,6 +159,7 @@ def test_lds_formula():
     # 2880 nw > 57 664, i.e. never (nw <= 16)
     over = lambda vec: [nw for nw in range(1, 17) if _lib.policy_kpi_lds_bytes(nw, vec) > 64 * 1024]
     assert over(2) == list(range(12, 17)) and over(1) == []
-    # the launcher opts in above 64 KiB and the entry point refuses above the CU's LDS
-    launcher = (_lib.CSRC / 'cl_policy_kpi.hip').read_text()
-    assert 'if (lds > 64 * 1024) if (hipError_t e = ensure_dynamic_lds(' in launcher and 'if (lds > CL_LDS_PER_CU) return fail(' in launcher
+    # the launcher opts in above 64 KiB and the entry point refuses above the CU's LDS: both through cl_policy_common.h's one copy
+    shared, unit = (_lib.CSRC / 'cl_policy_common.h').read_text(), (_lib.CSRC / 'cl_policy_kpi.hip').read_text()
+    assert 'if (lds > 64 * 1024) if (hipError_t e = ensure_dynamic_lds(' in shared and 'if (lds > CL_LDS_PER_CU) return fail(' in shared
+    assert 'CL_POLICY_LAUNCH(cl_rollout_policy_kpi_kernel<V, P>)' in unit and 'check_policy_lds(lds, "policy KPI", nw, vec)' in unit

@@ -196,7 +196,9 @@ class _Extension:
 POLICY = _Extension('policy', 'clpol', 'policy', ['-fno-slp-vectorize'], 'rollout_mlp_f32', PolicyMLP)
 POLICY_KPI = _Extension('policy_kpi', 'clpk', 'policy KPI', ['-fno-slp-vectorize'], 'rollout_mlp_kpi_f32', PolicyMLP, n_kpi=2, headers=[POLICY.header])
 POLICY_FULL = _Extension('policy_full', 'clpf', 'thermal policy', [], 'rollout_mlp_f32', PolicyFullMLP)
-EXTENSIONS = (POLICY, POLICY_KPI, POLICY_FULL)
+# ... and the thermal one that also keeps the streaming KPIs (cl_policy_full_kpi.hip, with SLP vectorisation like cl_policy_full.hip)
+POLICY_FULL_KPI = _Extension('policy_full_kpi', 'clpfk', 'thermal policy KPI', [], 'rollout_mlp_kpi_f32', PolicyFullMLP, n_kpi=2, headers=[POLICY_FULL.header])
+EXTENSIONS = (POLICY, POLICY_KPI, POLICY_FULL, POLICY_FULL_KPI)
 
 # The names other code and the tests use: read-only views of the descriptions above (build / load / check read the description, so rebinding one
 # of these changes nothing -- change the description's attribute instead)
@@ -208,6 +210,9 @@ build_policy_kpi, load_policy_kpi, check_policy_kpi = POLICY_KPI.build, POLICY_K
 POLICY_FULL_LIB_PATH, POLICY_FULL_HEADER, POLICY_FULL_SOURCES, POLICY_FULL_ABI_VERSION, POLICY_FULL_SYMBOLS = \
     POLICY_FULL.path, POLICY_FULL.header, POLICY_FULL.sources, POLICY_FULL.abi_version, POLICY_FULL.symbols
 build_policy_full, load_policy_full, check_policy_full = POLICY_FULL.build, POLICY_FULL.load, POLICY_FULL.check
+POLICY_FULL_KPI_LIB_PATH, POLICY_FULL_KPI_HEADER, POLICY_FULL_KPI_SOURCES, POLICY_FULL_KPI_ABI_VERSION, POLICY_FULL_KPI_SYMBOLS = \
+    POLICY_FULL_KPI.path, POLICY_FULL_KPI.header, POLICY_FULL_KPI.sources, POLICY_FULL_KPI.abi_version, POLICY_FULL_KPI.symbols
+build_policy_full_kpi, load_policy_full_kpi, check_policy_full_kpi = POLICY_FULL_KPI.build, POLICY_FULL_KPI.load, POLICY_FULL_KPI.check
 
 
 def policy_kpi_lds_bytes(nw: int, vec: int) -> int:
@@ -222,6 +227,13 @@ def policy_full_lds_bytes(nw: int, vec: int) -> int:
     """Dynamic LDS of one `cl_rollout_full_policy_kernel` workgroup of ``nw`` waves at ``vec`` envs per lane: csrc/cl_policy_full.h's
     `rollout_full_policy_lds_floats` -- the district reduction's rows [nw][4][tile], then the staged policy rows [nw][(5 + 4) x 32 + 4 x 8]."""
     return 4 * (nw * 4 * 64 * vec + nw * ((5 + 4) * 32 + 4 * 8))
+
+
+def policy_full_kpi_lds_bytes(nw: int) -> int:
+    """Dynamic LDS of one `cl_rollout_full_policy_kpi_kernel` workgroup of ``nw`` waves (one env per lane): csrc/cl_policy_full_kpi.h's
+    `rollout_full_policy_kpi_lds_floats` -- the ring of both district series [8][2][nw][64], the two series [2][12][64], the staged policy rows
+    [nw][(5 + 4) x 32 + 4 x 8], the units' twelve sums [nw][12][64] (tests/test_policy_full_kpi_host.py holds it against the header's formula)."""
+    return 4 * (8 * 2 * nw * 64 + 2 * 12 * 64 + nw * ((5 + 4) * 32 + 4 * 8) + nw * 12 * 64)
 
 
 _lib = None

@@ -67,7 +67,7 @@ struct FP {
 template <bool LP>
 CL_DEV uint32_t uword(const uint32_t* __restrict__ f, int k) {
     if constexpr (LP) return (uint32_t)__builtin_amdgcn_readfirstlane((int)f[k]);
-    else return f[k];
+    else return CL_TAB(f)[k];
 }
 
 // (Tried instead of LP for the launches that are not building-chunked: the tank and battery words fetched by VECTOR loads from the

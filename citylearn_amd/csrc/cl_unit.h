@@ -80,7 +80,15 @@ struct Bp {         // what stays live for the whole unit
     int a_cs, a_hs, a_ds, a_cd, a_hd, a_coh;
 };
 
-CL_DEV float pw(const uint32_t* __restrict__ p, int slot) { return __uint_as_float(p[slot]); }
+#ifdef CL_TU_CONST_TABLES
+// (cl_policy_full_kpi.hip: every read of the READ-ONLY tables through the constant address space -- a scalar load whatever surrounds it, where a
+//  K loop that holds a barrier turns a plain global read into a vector load per lane: cl_rollout.h's note on as_const.  Never on an LDS copy.)
+typedef const uint32_t __attribute__((address_space(4)))* cl_ctab;
+#define CL_TAB(p) ((::cl::cl_ctab)(const uint32_t*)(p))
+#else
+#define CL_TAB(p) (p)
+#endif
+CL_DEV float pw(const uint32_t* __restrict__ p, int slot) { return __uint_as_float(CL_TAB(p)[slot]); }
 
 // a * b that is never fused into a following add: the district cost is a sum of rounded per-building products (citylearn.py:1909-1918),
 // and whether `q += net * price` became an fma used to depend on the instantiation (one vs two vs four envs per lane).
@@ -270,7 +278,7 @@ CL_DEV double div_rn(double a, double b, double rb) {
 }
 
 CL_DEV double pd(const uint32_t* __restrict__ p, int k) {           // k-th double of the CLP_D_* block (8-byte aligned: CL_NP and CLP_D_FIRST are even)
-    const uint64_t bits = (uint64_t)p[CLP_D_FIRST + 2 * k] | ((uint64_t)p[CLP_D_FIRST + 2 * k + 1] << 32);
+    const uint64_t bits = (uint64_t)CL_TAB(p)[CLP_D_FIRST + 2 * k] | ((uint64_t)CL_TAB(p)[CLP_D_FIRST + 2 * k + 1] << 32);
     double d;
     __builtin_memcpy(&d, &bits, 8);
     return d;
@@ -380,7 +388,7 @@ struct BattC {
 };
 
 CL_DEV double pc(const uint32_t* __restrict__ p, int k) {           // k-th double of the CLP_C_* block (8-byte aligned)
-    const uint64_t bits = (uint64_t)p[CLP_C_FIRST + 2 * k] | ((uint64_t)p[CLP_C_FIRST + 2 * k + 1] << 32);
+    const uint64_t bits = (uint64_t)CL_TAB(p)[CLP_C_FIRST + 2 * k] | ((uint64_t)CL_TAB(p)[CLP_C_FIRST + 2 * k + 1] << 32);
     double d;
     __builtin_memcpy(&d, &bits, 8);
     return d;

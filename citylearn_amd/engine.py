@@ -508,19 +508,22 @@ class StepEngine:
 
         ``policy_tables`` from `policy.StorageMLPPolicy.pack` (a `StoragePolicyTables`) sends a THERMAL district of up to 16 buildings to
         `cl_rollout_full_policy_kernel` (`clpf_rollout_mlp_f32`, ``libcitylearn_amd_policy_full.so``): up to four storage heads per building,
-        ``traj`` ``[k_steps, CLPF_NT, n_bldg, n_env]``; ``kpi=True`` raises `NotImplementedError` there."""
+        ``traj`` ``[k_steps, CLPF_NT, n_bldg, n_env]``.  With ``kpi=True`` on an engine built with ``kpi=True`` the same steps are ONE launch of
+        `cl_rollout_full_policy_kpi_kernel` (`clpfk_rollout_mlp_kpi_f32`, ``libcitylearn_amd_policy_full_kpi.so``), which keeps every env's
+        twelve per-building sums and both district series and, under the float64 chain, leaves the last step's `CLD_DETAIL_MIN` planes in
+        ``out_bldg``; on an engine built without KPIs it raises `NotImplementedError`."""
         from . import policy as _policy
         storage = isinstance(policy_tables, _policy.StoragePolicyTables)
-        if storage and kpi:
-            raise NotImplementedError('rollout_policy(kpi=True): the thermal policy kernel (cl_rollout_full_policy_kernel) keeps no streaming KPIs -- '
-                                      'only battery + PV districts with an MLPPolicy have a closed-loop KPI kernel')
+        if storage and kpi and not self.kpi:
+            raise NotImplementedError('rollout_policy(kpi=True) with StoragePolicyTables: this engine was built without the streaming KPI accumulators -- '
+                                      'build it with kpi=True (the thermal policy KPI kernel, cl_rollout_full_policy_kpi_kernel, needs them)')
         if kpi and not self.kpi:
             raise ValueError('rollout_policy(kpi=True) needs an engine built with kpi=True: this one keeps no KPI accumulators')
         if self.flex is not None:
             # (the library cannot see this: a battery + PV district with EV chargers / washing machines and a non-EV reward has CLD_LEAN set)
             raise NotImplementedError('rollout_policy: districts with flexible loads (EV chargers / washing machines) are not covered by the policy '
                                       'kernel -- it would leave their consumption out of net; use step() / capture_rollout')
-        ext = _lib.POLICY_FULL if storage else _lib.POLICY_KPI if kpi else _lib.POLICY
+        ext = (_lib.POLICY_FULL_KPI if kpi else _lib.POLICY_FULL) if storage else _lib.POLICY_KPI if kpi else _lib.POLICY
         ext.load()          # (here, not only inside ext.rollout: a missing library is reported in front of the argument checks below)
         kpi_planes = (_ptr(self.kpi_bldg), _ptr(self.kpi_env)) if kpi else ()
         n_planes = _policy.CLPF_NT if storage else _policy.CLPOL_NT

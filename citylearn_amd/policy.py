@@ -32,7 +32,17 @@ of `cl_rollout_full_policy_kernel` (csrc/cl_policy_full.h, ``libcitylearn_amd_po
     spolicy = StorageMLPPolicy(w1, b1, w2, b2, sigma=0.1)          # w2 [n_sets, n_bldg, 4, H], b2 [n_sets, n_bldg, 4]
     ret, traj = env.rollout_policy(spolicy, 24, seed=3, record=True)   # traj [24, CLPF_NT, n_bldg, n_envs]: policy.CLPF_T_ACTION + head, ..
 
-It keeps no streaming KPIs (``kpi=True`` raises `NotImplementedError`); `MLPPolicy` still refuses such a district.
+On an env built with ``kpi=True`` the same call with ``kpi=True`` is ONE launch of `cl_rollout_full_policy_kpi_kernel`
+(csrc/cl_policy_full_kpi.h, ``libcitylearn_amd_policy_full_kpi.so``, include/citylearn_amd_policy_full_kpi.h) that also keeps every env's
+streaming KPI accumulators, so `evaluate()` scores the controllers afterwards -- no record, no second env:
+
+    kenv = VectorCityLearnEnv(schema, n_envs, kpi=True)
+    ret = kenv.rollout_policy(spolicy, 24, seed=3, kpi=True)
+    building_kpis, district_kpis = kenv.evaluate()
+
+(``kpi=True`` on an env built without KPIs raises `NotImplementedError`.)  `MLPPolicy` still refuses such a district.  Open: thermal districts
+of more than 16 buildings (building-chunked), heads for device actions, and the outage branch of the thermal policy kernels, which no fixture
+without the LSTM stage exercises.
 """
 from __future__ import annotations
 

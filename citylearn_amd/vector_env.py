@@ -428,11 +428,14 @@ class VectorCityLearnEnv:
 
         A `policy.StorageMLPPolicy` drives a THERMAL district (cooling / heating / DHW storage beside the battery, no LSTM stage, no device
         actions, up to 16 buildings) the same way through `cl_rollout_full_policy_kernel`: the trajectory then has `policy.CLPF_NT` planes
-        (`CLPF_T_ACTION` + head, `_REWARD`, `_NET`, `CLPF_T_SOC` + storage), and ``kpi=True`` raises `NotImplementedError`."""
+        (`CLPF_T_ACTION` + head, `_REWARD`, `_NET`, `CLPF_T_SOC` + storage).  ``kpi=True`` on an env built with ``kpi=True`` keeps the streaming KPI
+        accumulators in the same single launch (`cl_rollout_full_policy_kpi_kernel`), so `evaluate()` works afterwards without a record or a
+        second env; on an env built without KPIs it raises `NotImplementedError`."""
         from . import policy as _policy
         storage = isinstance(policy, _policy.StorageMLPPolicy)
-        if storage and kpi:
-            raise NotImplementedError('rollout_policy(kpi=True): a StorageMLPPolicy runs in the thermal policy kernel, which keeps no streaming KPIs')
+        if storage and kpi and not self.kpi:
+            raise NotImplementedError('rollout_policy(kpi=True) with a StorageMLPPolicy: this env was built without the streaming KPI accumulators -- '
+                                      'build it with VectorCityLearnEnv(..., kpi=True)')
         if kpi and not self.kpi:
             raise ValueError('rollout_policy(kpi=True) needs VectorCityLearnEnv(..., kpi=True): this env keeps no KPI accumulators')
         if self.stage is not None or self._plugin is not None:

@@ -40,9 +40,9 @@ streaming KPI accumulators, so `evaluate()` scores the controllers afterwards --
     ret = kenv.rollout_policy(spolicy, 24, seed=3, kpi=True)
     building_kpis, district_kpis = kenv.evaluate()
 
-(``kpi=True`` on an env built without KPIs raises `NotImplementedError`.)  `MLPPolicy` still refuses such a district.  Open: thermal districts
-of more than 16 buildings (building-chunked), heads for device actions, and the outage branch of the thermal policy kernels, which no fixture
-without the LSTM stage exercises.
+(``kpi=True`` on an env built without KPIs raises `NotImplementedError`.)  `MLPPolicy` still refuses such a district.  A district with power
+outages goes through the same two kernels (their outage branch is tested on g2020_cz1 with chosen outage rows: tests/policy_full_util.py
+`outage_district`).  Open: thermal districts of more than 16 buildings (building-chunked) and heads for device actions.
 """
 from __future__ import annotations
 

@@ -68,7 +68,11 @@ class COracle:
         for i, b in enumerate(spec.buildings):
             e = b.electrical_storage
             flags = (1 if e.present else 0) | (2 if b.heating_device.is_heat_pump else 0) | (4 if b.dhw_device.is_heat_pump else 0) \
-                | (8 if b.outage.simulate else 0) | (16 if b.is_dynamics else 0)
+                | (8 if b.outage.simulate else 0) | (16 if b.is_dynamics else 0) \
+                | (32 if isinstance(b.cooling_storage.capacity, np.float32) else 0) | (64 if isinstance(b.heating_storage.capacity, np.float32) else 0)
+            # bits 5 and 6 mirror the TYPE the loader produced: an autosized capacity is an np.float32 scalar, and under NumPy 2 (NEP 50) `action * capacity`
+            # with it is a float32 product where a Python-float capacity gives a double one.  oracle.py inherits that from the installed NumPy; under
+            # NumPy 1's value-based promotion the two would part in the last float32 bit of that product.
             P[i, OP['FLAGS']] = flags
             P[i, OP['DT']] = b.seconds_per_time_step / 3600
             P[i, OP['R']] = b.time_step_ratio

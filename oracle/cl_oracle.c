@@ -8,7 +8,15 @@
  * (tests/golden/<fixture>/reference.npz) -- max |error| <= 1e-6 on every quantity.
  *
  * Arithmetic is double with float rounding wherever the reference stores into a float32 series
- * (energy_model.py:151-155, 797-803; building.py:2555-2564), which is what makes it track the reference.
+ * (energy_model.py:151-155, 797-803; building.py:2555-2564) AND wherever the reference's own arithmetic is float32: a float32
+ * series element combined with another one, with a float32 heat-pump COP or with a Python float stays float32 (the Python float
+ * is converted first), and turns double only when it meets the np.float64 time_step_ratio.  oracle/oracle.py has the same
+ * promotions by construction; this file states them with f32().  Stepped from reset, t = 0, 1, 2, .. the two are equal bit for
+ * bit (tests/test_policy_full_host.py pins that on a thermal district under an outage).  One promotion depends on an object's
+ * history and not on t: Battery.degrade divides by a Python float until the first charge() of an episode has made the degraded
+ * capacity np.float64.  This file takes `t == 0` for "first charge()"; a caller that starts mid-episode or teacher-forces the state
+ * (the GPU parity tests do) gets the double quotient on its first step where oracle.py, fresh from reset(), gets the float32
+ * one -- one float32 rounding of a degradation of ~1e-5 of the capacity, far inside every tolerance this oracle is used at.
  * Reference citations are relative to /root/reference/citylearn/.
  *
  * Build: gcc -O2 -fPIC -shared -fopenmp oracle/cl_oracle.c -o oracle/libcl_oracle.so -lm
@@ -22,7 +30,8 @@
 /* per-building parameters, doubles */
 enum {
     OP_FLAGS = 0,        /* bit0 battery present, bit1 heating is heat pump, bit2 dhw is heat pump, bit3 simulate outage,
-                            bit4 dynamics building */
+                            bit4 dynamics building, bit5 / bit6 the cooling / heating tank's capacity is a float32 scalar (autosized), so
+                            that `action * capacity` is a float32 product (building.py:1675, 1720, 1765) */
     OP_DT, OP_R,
     OP_B_CAP, OP_B_POW, OP_B_LOSS, OP_B_CLC, OP_B_DOD, OP_B_EFF0, OP_B_SOC0,
     OP_B_CPC_X /*3*/, OP_B_CPC_Y = OP_B_CPC_X + 3 /*3*/, OP_B_PEC_X = OP_B_CPC_Y + 3 /*5*/, OP_B_PEC_Y = OP_B_PEC_X + 5 /*5*/,
@@ -73,7 +82,7 @@ typedef struct {
 /* StorageDevice.charge (energy_model.py:719-768) */
 static void base_charge(tank_t* k, double energy, double cap, double loss_r, double rte, double r) {
     energy *= r;
-    double e_init = f32(k->prev_soc * cap) * (1.0 - loss_r);     /* float32 product, then float64 (r is np.float64) */
+    double e_init = f32(k->prev_soc * f32(cap)) * (1.0 - loss_r);     /* float32 product, then float64 (r is np.float64) */
     if (e_init < 0) e_init = 0;
     double e_fin;
     if (energy >= 0) { e_fin = e_init + energy * rte; if (e_fin > cap) e_fin = cap; }
@@ -88,7 +97,7 @@ static void tank_charge(tank_t* k, double energy, const double* tp, double r) {
     energy *= r;
     if (energy >= 0) { if (energy > tp[4]) energy = tp[4]; }
     else { if (energy < -tp[5]) energy = -tp[5]; }
-    base_charge(k, energy, tp[0], tp[1] * r, sqrt(tp[2]), r);
+    base_charge(k, energy, tp[0], tp[1] * r, pow(tp[2], 0.5), r);
 }
 
 typedef struct {
@@ -103,7 +112,7 @@ typedef struct {
 static double flex(const unit_t* u) {            /* building.py:640-668 */
     if (!u->outage) return INFINITY;
     double solar = -(u->row[OT_PV_POW] * u->row[OT_SOLAR_WKW] / 1000.0);
-    double used = f32(f32(f32(f32(f32(u->c_cool * u->r) + f32(u->c_heat * u->r)) + f32(u->c_dhw * u->r)) + f32(u->c_ns * u->r)) + f32(u->c_b * u->r));
+    double used = u->c_cool * u->r + u->c_heat * u->r + u->c_dhw * u->r + u->c_ns * u->r + u->c_b * u->r;   /* float32 x np.float64: double */
     double cap = fabs(solar) - used;
     return cap > 0 ? cap : 0;
 }
@@ -117,25 +126,27 @@ static double max_out(const unit_t* u, double pow, double c, double cop) {
 static void end_use_device(unit_t* u, double* c, double demand, const tank_t* k, double pow, double cop, double* e_dev) {
     double storage_output = k->eb < 0 ? -k->eb : 0.0;           /* building.py:525-541 */
     double mo = max_out(u, pow, *c, cop);
-    double out = demand - storage_output;
-    if (mo < out) out = mo;
+    double out = f32(demand - storage_output), cons;              /* float32 - float32 */
+    if (mo < out) { out = mo; cons = out / cop; }                 /* the device's limit is double (.. * r) */
+    else cons = f32(out / f32(cop));                              /* float32 / (float32 COP | Python float) */
     *e_dev = f32(out);
-    double cons = out / cop;
     *c = f32(*c + (cons > 0 ? cons : 0));
 }
 
-static void end_use_storage(unit_t* u, double* c, double demand, tank_t* k, const double* tp, double action, double cscale,
-                            double pow, double cop) {
-    double energy = action * cscale;
+static void end_use_storage(unit_t* u, double* c, double demand, tank_t* k, const double* tp, double action, double cap, double dt,
+                            int cap_is_f32, double pow, double cop) {
+    /* action * capacity [* dt]: float32 products when the capacity is a float32 scalar, Python floats otherwise */
+    double energy = cap_is_f32 ? f32(action * cap) : action * cap;
+    energy = cap_is_f32 ? f32(energy * f32(dt)) : energy * dt;
     if (energy > 0.0) { double mo = max_out(u, pow, *c, cop); if (mo < energy) energy = mo; }
     else { if (energy < -demand) energy = -demand; }
     tank_charge(k, energy / u->r, tp, u->r);
     double charged = k->eb > 0 ? k->eb : 0.0;
-    *c = f32(*c + charged / cop);
+    *c = f32(*c + f32(charged / f32(cop)));                       /* float32 balance / (float32 COP | Python float) */
 }
 
 /* update_electrical_storage + Battery.charge (building.py:1791-1812, energy_model.py:1027-1141) */
-static void battery_charge(unit_t* u, tank_t* es, double* eff, double* degcap, double a_es) {
+static void battery_charge(unit_t* u, tank_t* es, double* eff, double* degcap, double a_es, int fresh) {
     const double* p = u->p;
     if (!((int)p[OP_FLAGS] & 1)) return;
     double energy = a_es * p[OP_B_POW] * u->dt;
@@ -144,7 +155,7 @@ static void battery_charge(unit_t* u, tank_t* es, double* eff, double* degcap, d
     energy = energy / u->r * u->r;                       /* _convert_energy_for_storage, then charge()'s own * r */
     double action_energy = energy;
     const double cap = p[OP_B_CAP], powr = p[OP_B_POW];
-    double e_init = f32(es->prev_soc * cap) * (1.0 - p[OP_B_LOSS] * u->r);
+    double e_init = f32(es->prev_soc * f32(cap)) * (1.0 - p[OP_B_LOSS] * u->r);
     if (e_init < 0) e_init = 0;
     double socn = e_init / (cap > ZDP ? cap : ZDP);
     const double* cx = p + OP_B_CPC_X; const double* cy = p + OP_B_CPC_Y;
@@ -157,7 +168,7 @@ static void battery_charge(unit_t* u, tank_t* es, double* eff, double* degcap, d
         energy = m;
         x = action_energy < pmax ? action_energy : pmax;
     } else {
-        double lim = f32(f32(es->prev_soc - (1.0 - p[OP_B_DOD])) * cap) * sqrt(*eff);
+        double lim = f32(f32(es->prev_soc - f32(1.0 - p[OP_B_DOD])) * f32(cap)) * pow(*eff, 0.5);
         lim = lim > 0 ? -lim : -0.0;
         double m = -pmax; if (lim > m) m = lim; if (energy > m) m = energy;
         energy = m;
@@ -167,8 +178,11 @@ static void battery_charge(unit_t* u, tank_t* es, double* eff, double* degcap, d
     const double* ex = p + OP_B_PEC_X; const double* ey = p + OP_B_PEC_Y;
     i = interp_index(x, ex, 5);
     *eff = ey[i] + (x - ex[i]) * (ey[i + 1] - ey[i]) / (ex[i + 1] - ex[i]);
-    base_charge(es, energy, cap, p[OP_B_LOSS] * u->r, sqrt(*eff), u->r);
-    double deg = f32(p[OP_B_CLC] * cap * fabs(es->eb) / (2 * (*degcap > ZDP ? *degcap : ZDP))) * u->r;
+    base_charge(es, energy, cap, p[OP_B_LOSS] * u->r, pow(*eff, 0.5), u->r);
+    /* energy_model.py:1130-1141: (Python float x float32 balance) is float32; the divisor is a Python float until the first degradation
+       of an episode has made capacity_history np.float64 */
+    double wear = f32(f32(p[OP_B_CLC] * cap) * fabs(es->eb)), den = 2 * (*degcap > ZDP ? *degcap : ZDP);
+    double deg = (fresh ? f32(wear / f32(den)) : wear / den) * u->r;
     *degcap = *degcap - deg; if (*degcap < 0) *degcap = 0;
     u->c_b = f32(u->c_b + es->eb);
 }
@@ -201,8 +215,8 @@ void cl_oracle_step(int n_env, int n_bldg, const double* params, const double* t
             const int first = t0_quirk && t == 0;
             u.c_cool = u.c_heat = u.c_dhw = u.c_ns = u.c_b = 0;
             if (first) {   /* reset-time update_variables (citylearn.py:1884 -> building.py:2618-2652) */
-                u.c_cool = f32(row[OT_COOL] / u.cop_c); u.c_heat = f32(row[OT_HEAT] / t0_heat_div);
-                u.c_dhw = f32(row[OT_DHW] / u.cop_d); u.c_ns = f32(row[OT_NSL]);
+                u.c_cool = f32(row[OT_COOL] / f32(u.cop_c)); u.c_heat = f32(row[OT_HEAT] / f32(t0_heat_div));
+                u.c_dhw = f32(row[OT_DHW] / f32(u.cop_d)); u.c_ns = f32(row[OT_NSL]);
             }
 #define ACT(slot) ((int)p[slot] >= 0 ? (double)actions[(size_t)(int)p[slot] * n_env + e] : 0.0)
             double a_cs = ACT(OP_ACT_CS), a_hs = ACT(OP_ACT_HS), a_ds = ACT(OP_ACT_DS), a_es = ACT(OP_ACT_ES);
@@ -232,46 +246,46 @@ void cl_oracle_step(int n_env, int n_bldg, const double* params, const double* t
             double eff = S[OS_EFF], degcap = S[OS_DEGCAP];
             double e_cool = f32(cool_dem), e_heat = f32(heat_dem), e_dhw = f32(dhw_dem), e_ns = f32(row[OT_NSL]);
             /* order (building.py:1567-1634): battery first when discharging, storage before device when discharging */
-            if (a_es < 0.0) battery_charge(&u, &es, &eff, &degcap, a_es);
+            if (a_es < 0.0) battery_charge(&u, &es, &eff, &degcap, a_es, t == 0);
             {
                 const double* tcs = p + OP_CS; const double* ths = p + OP_HS; const double* tds = p + OP_DS;
                 if (a_cs < 0.0) {
-                    end_use_storage(&u, &u.c_cool, cool_dem, &cs, tcs, a_cs, tcs[0], p[OP_CD_POW], u.cop_c);
+                    end_use_storage(&u, &u.c_cool, cool_dem, &cs, tcs, a_cs, tcs[0], 1.0, flags & 32, p[OP_CD_POW], u.cop_c);
                     end_use_device(&u, &u.c_cool, cool_dem, &cs, p[OP_CD_POW], u.cop_c, &e_cool);
                 } else {
                     end_use_device(&u, &u.c_cool, cool_dem, &cs, p[OP_CD_POW], u.cop_c, &e_cool);
-                    end_use_storage(&u, &u.c_cool, cool_dem, &cs, tcs, a_cs, tcs[0], p[OP_CD_POW], u.cop_c);
+                    end_use_storage(&u, &u.c_cool, cool_dem, &cs, tcs, a_cs, tcs[0], 1.0, flags & 32, p[OP_CD_POW], u.cop_c);
                 }
                 if (a_hs < 0.0) {
-                    end_use_storage(&u, &u.c_heat, heat_dem, &hs, ths, a_hs, tcs[0] * u.dt, p[OP_HD_POW], u.cop_h);
+                    end_use_storage(&u, &u.c_heat, heat_dem, &hs, ths, a_hs, tcs[0], u.dt, flags & 32, p[OP_HD_POW], u.cop_h);
                     end_use_device(&u, &u.c_heat, heat_dem, &hs, p[OP_HD_POW], u.cop_h, &e_heat);
                 } else {
                     end_use_device(&u, &u.c_heat, heat_dem, &hs, p[OP_HD_POW], u.cop_h, &e_heat);
-                    end_use_storage(&u, &u.c_heat, heat_dem, &hs, ths, a_hs, tcs[0] * u.dt, p[OP_HD_POW], u.cop_h);
+                    end_use_storage(&u, &u.c_heat, heat_dem, &hs, ths, a_hs, tcs[0], u.dt, flags & 32, p[OP_HD_POW], u.cop_h);
                 }
                 if (a_ds < 0.0) {
-                    end_use_storage(&u, &u.c_dhw, dhw_dem, &ds, tds, a_ds, ths[0] * u.dt, p[OP_DD_POW], u.cop_d);
+                    end_use_storage(&u, &u.c_dhw, dhw_dem, &ds, tds, a_ds, ths[0], u.dt, flags & 64, p[OP_DD_POW], u.cop_d);
                     end_use_device(&u, &u.c_dhw, dhw_dem, &ds, p[OP_DD_POW], u.cop_d, &e_dhw);
                 } else {
                     end_use_device(&u, &u.c_dhw, dhw_dem, &ds, p[OP_DD_POW], u.cop_d, &e_dhw);
-                    end_use_storage(&u, &u.c_dhw, dhw_dem, &ds, tds, a_ds, ths[0] * u.dt, p[OP_DD_POW], u.cop_d);
+                    end_use_storage(&u, &u.c_dhw, dhw_dem, &ds, tds, a_ds, ths[0], u.dt, flags & 64, p[OP_DD_POW], u.cop_d);
                 }
                 double f = flex(&u);
                 double d = row[OT_NSL] < f ? row[OT_NSL] : f;      /* building.py:1784-1789 */
                 e_ns = f32(d);
                 u.c_ns = f32(u.c_ns + d);
             }
-            if (!(a_es < 0.0)) battery_charge(&u, &es, &eff, &degcap, a_es);
+            if (!(a_es < 0.0)) battery_charge(&u, &es, &eff, &degcap, a_es, t == 0);
             if (first) {   /* second t == 0 pass of update_variables (building.py:2618-2652) */
-                u.c_cool = f32(u.c_cool + (e_cool + cs.eb) / u.cop_c);
-                u.c_heat = f32(u.c_heat + (e_heat + hs.eb) / t0_heat_div);
-                u.c_dhw = f32(u.c_dhw + (e_dhw + ds.eb) / u.cop_d);
+                u.c_cool = f32(u.c_cool + f32(f32(e_cool + cs.eb) / f32(u.cop_c)));        /* float32 throughout */
+                u.c_heat = f32(u.c_heat + f32(f32(e_heat + hs.eb) / f32(t0_heat_div)));
+                u.c_dhw = f32(u.c_dhw + f32(f32(e_dhw + ds.eb) / f32(u.cop_d)));
                 u.c_ns = f32(u.c_ns + e_ns);
                 u.c_b = f32(u.c_b + es.eb);
             }
             double net = 0.0;
             if (!u.outage)
-                net = f32(f32(f32(f32(f32(u.c_cool * u.r) + f32(u.c_heat * u.r)) + f32(u.c_dhw * u.r)) + f32(u.c_ns * u.r)) + f32(u.c_b * u.r)) + solar;
+                net = u.c_cool * u.r + u.c_heat * u.r + u.c_dhw * u.r + u.c_ns * u.r + u.c_b * u.r + solar;   /* building.py:2685-2693: float32 x np.float64, double */
             double net32 = f32(net);
             S[OS_SOC] = es.soc; S[OS_EFF] = eff; S[OS_DEGCAP] = degcap; S[OS_CS] = cs.soc; S[OS_HS] = hs.soc; S[OS_DS] = ds.soc;
             O[OO_NET] = net32; O[OO_EB] = es.eb;
@@ -305,7 +319,7 @@ void cl_oracle_step(int n_env, int n_bldg, const double* params, const double* t
             if (reward_kind == 1) {
                 double n = -O[OO_NET];
                 double sg = n > 0 ? 1 : (n < 0 ? -1 : 0);
-                O[OO_REWARD] = sg * 0.01 * n * n * (d_net > 0 ? d_net : 0);
+                O[OO_REWARD] = sg * 0.01 * (n * n) * (d_net > 0 ? d_net : 0);
             }
             d_rw += O[OO_REWARD];
         }

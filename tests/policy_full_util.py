@@ -1,6 +1,8 @@
 """Shared by tests/test_policy_full_host.py and tests/test_gpu_policy_full_rollout.py: the test policies of thermal districts (ONE weight scale,
 fixed by the CPU conditioning test), the observation vectors of a batch rebuilt on the host from `ObservationTables` with FIVE env-dependent
 planes, and the closed loop on the CPU oracle with the four heads scattered into the action columns."""
+import copy
+from dataclasses import replace
 from functools import lru_cache
 
 import numpy as np
@@ -39,11 +41,18 @@ def make_storage_policy(layout: ObservationLayout, H: int, n_sets: int = 1, seed
     return StorageMLPPolicy(w1, b1, w2, b2, sigma=sigma)
 
 
+OUTAGE_SUFFIX = '_outage'
+OUTAGE_NAMES = ('g2020_cz1_outage', 't1_outage', 't2_outage', 't16_outage')
+
+
 @lru_cache(maxsize=None)
 def thermal_district(name: str):
     """Districts cut from / repeated out of g2020_cz1's nine buildings (buildings 2 and 3 have no DHW storage): 't1' building 0; 't2' buildings
-    1 and 2 -- one with and one without DHW; 't16' / 't17' tiled + jittered to 16 (nw = 16, the kernel's limit) / 17 buildings (refused)."""
+    1 and 2 -- one with and one without DHW; 't16' / 't17' tiled + jittered to 16 (nw = 16, the kernel's limit) / 17 buildings (refused).
+    '<name>_outage': `outage_district` of that district."""
     from citylearn_amd.synthetic import tile_district
+    if name.endswith(OUTAGE_SUFFIX):
+        return outage_district(name[:-len(OUTAGE_SUFFIX)])
     g = golden('g2020_cz1')
     if name == 'g2020_cz1':
         return g.spec()
@@ -52,6 +61,45 @@ def thermal_district(name: str):
     if name == 't2':
         return g.spec(buildings=[1, 2])
     return tile_district(g.spec(), {'t16': 16, 't17': 17}[name])
+
+
+def outage_rows(i: int):
+    """The episode steps at which building i of an outage district is without the grid: none for i % 3 == 2 (those waves take the kernel's
+    branch without outage in the same workgroup at the same step); for the others 5 + i % 9 .. 8 + i % 9 (staggered per building, straddling
+    a launch boundary at step 6), 22 .. 26 (common to all: across the day boundary at t = 24 and a KPI fold at step 24) and 40 .. 41.  Never
+    step 0, which `reset()` books before any kernel runs (tests/test_gpu_check.py)."""
+    if i % 3 == 2:
+        return []
+    return list(range(5 + i % 9, 9 + i % 9)) + list(range(22, 27)) + [40, 41]
+
+
+@lru_cache(maxsize=None)
+def outage_district(name: str):
+    """`thermal_district(name)` with a power outage: every building a `copy.copy` with a `series` dict of its own whose 'power_outage' is 1
+    on `outage_rows(i)` of episode 0, `outage.simulate` on (deterministic signal), and the three tanks charged to 0.5 where they have a
+    capacity (the battery starts as the schema has it), so that a storage has something to discharge when the grid goes away.  No LSTM stage,
+    no device action: the policy packer accepts it.  The cached original and the shared series arrays are left as they are."""
+    src = thermal_district(name)
+    start, _ = src.episode_window(0)
+    out = []
+    for i, b in enumerate(src.buildings):
+        c = copy.copy(b)
+        c.series = dict(b.series)
+        signal = np.zeros_like(b.series['power_outage'])
+        signal[[start + r for r in outage_rows(i)]] = 1
+        c.series['power_outage'] = signal
+        c.outage = replace(b.outage, simulate=True, stochastic=False)
+        for key in ('cooling_storage', 'heating_storage', 'dhw_storage'):
+            tank = getattr(b, key)
+            if tank.capacity > 0:
+                setattr(c, key, replace(tank, initial_soc=0.5))
+        out.append(c)
+    return replace(src, buildings=out)
+
+
+def outage_mask(tab, K: int):
+    """bool [K, n_bldg]: the (step, building) pairs of the first K rows of the episode tables that carry an outage."""
+    return tab.outage[:K] > 0
 
 
 class HostObservations5:

@@ -5,8 +5,11 @@ csrc/cl_policy_full_kpi.h, ``libcitylearn_amd_policy_full_kpi.so``).
 Nothing here compares the kernel with itself, except where two launches of it must agree (split launches, env blocks).  The references: the
 SINGLE-STEP path with `kpi=True` fed the recorded actions (`cl_step_full_kpi_kernel` in fp32; under the float64 chain the step with the
 `CLD_DETAIL_MIN` planes + `cl_kpi_kernel`), at tests/test_gpu_policy_full_rollout.py::_replay's and tests/test_gpu_rollout_kpi.py's two-paths
-tolerances; the float64 MLP on the recorded inputs; the CPU oracle's closed loop.  Untested, as in the parent kernel: the outage branch (no
-fixture without the LSTM stage has outage rows).  Measured readings: profiles/policy_full_kpi_parity.md."""
+tolerances; the float64 MLP on the recorded inputs; the CPU oracle's closed loop.  The outage branch (`clv::unit_step<.., OUT = true>`, `saw_outage` and the
+two sums CLK_UNSERVED_OUTAGE / CLK_EXPECTED_OUTAGE) runs on the outage districts of tests/policy_full_util.py (`outage_district`: g2020_cz1 and
+its cuts with chosen outage rows and charged tanks; no LSTM stage, so the packer accepts them) -- tests 2, 3, 5, 6 and 7 each have a case there;
+the single-step reference is itself pinned on that district against the C oracle by tests/test_gpu_outage_thermal.py.  Measured readings:
+profiles/policy_full_kpi_parity.md."""
 import numpy as np
 import pytest
 import torch
@@ -15,7 +18,7 @@ from golden_util import check_worst, golden, record_worst
 from citylearn_amd import _lib, abi, policy
 from citylearn_amd.engine import StepEngine
 from citylearn_amd.observations import ObservationLayout
-from policy_full_util import host_closed_loop, make_storage_policy, thermal_district
+from policy_full_util import host_closed_loop, make_storage_policy, outage_mask, thermal_district
 from test_gpu_policy_full_rollout import A, KINDS, N, NA, R, S, _scatter, _teacher_forced
 from test_gpu_rollout_geometry import _bar, _prec
 from test_gpu_rollout_kpi import REWARD_CLASS, _finalised_close
@@ -61,10 +64,23 @@ def _compare_kpi(b, a, what=''):
     assert torch.equal(b.kpi_bldg[OUTAGE], a.kpi_bldg[OUTAGE])
 
 
-def _replay(ref, pt, traj, eng, ret, label):
+def _outage_sums_moved(eng, before, has):
+    """The two outage sums against their values `before` the launch(es): bit-equal for the buildings without an outage row (`has` [n_bldg] bool),
+    moved for the others -- the expected energy for every env, the unserved energy for some env of every such building -- and
+    0 <= unserved <= expected everywhere."""
+    has = torch.as_tensor(np.asarray(has), device=eng.kpi_bldg.device)
+    now = eng.kpi_bldg[OUTAGE]
+    assert torch.equal(now[:, ~has], before[:, ~has])
+    assert bool((now[1][has] > before[1][has]).all()) and bool((now[0][has] > before[0][has]).any(dim=1).all())
+    assert bool((now[0] >= 0).all()) and bool((now[0] <= now[1]).all())
+
+
+def _replay(ref, pt, traj, eng, ret, label, tab=None):
     """The recorded head planes scattered to action columns and fed step by step to `ref.step()` (a `kpi=True` engine in the state the launch
-    started from): tests/test_gpu_policy_full_rollout.py::_replay's tolerances, then the KPI planes and (chain) the CLD_DETAIL_MIN planes."""
+    started from): tests/test_gpu_policy_full_rollout.py::_replay's tolerances, then the KPI planes and (chain) the CLD_DETAIL_MIN planes.
+    `tab`: the episode tables of a district with outage rows (from step 0; one episode window)."""
     K = traj.shape[0]
+    t_first = ref.t
     worst = {}
     ret_ref = torch.zeros(ref.n_env, device='cuda')
     reset_outage = ref.kpi_bldg[OUTAGE].clone()
@@ -77,7 +93,7 @@ def _replay(ref, pt, traj, eng, ret, label):
         torch.testing.assert_close(traj[k, N], ref.net, rtol=2e-5, atol=2e-5)
         torch.testing.assert_close(traj[k, R], ref.reward_bldg, rtol=2e-5, atol=2e-5)
     worst.update(state=_bar(eng.state, ref.state), out_env=_bar(eng.out_env, ref.out_env), kpi_bldg=_bar(eng.kpi_bldg, ref.kpi_bldg),
-                 kpi_env=_bar(eng.kpi_env, ref.kpi_env), **{'return': _bar(ret, ret_ref)})
+                 kpi_env=_bar(eng.kpi_env, ref.kpi_env), kpi_outage=_bar(eng.kpi_bldg[OUTAGE], ref.kpi_bldg[OUTAGE]), **{'return': _bar(ret, ret_ref)})
     if eng.f64_chain:
         worst['detail'] = _bar(eng.out_bldg[DETAIL_MIN], ref.out_bldg[DETAIL_MIN])
     print(label, {k: round(v, 4) for k, v in worst.items()})
@@ -91,7 +107,13 @@ def _replay(ref, pt, traj, eng, ret, label):
     if eng.f64_chain:
         torch.testing.assert_close(eng.out_bldg[DETAIL_MIN], ref.out_bldg[DETAIL_MIN], rtol=2e-5, atol=2e-5)
         assert float(eng.out_bldg[abi.CLO_EXPECTED].abs().sum()) > 0
-    assert torch.equal(eng.kpi_bldg[OUTAGE], reset_outage)
+    m = None if tab is None else outage_mask(tab, t_first + K)[t_first:]
+    if m is None or not m.any():
+        assert torch.equal(eng.kpi_bldg[OUTAGE], reset_outage)
+    else:
+        assert torch.equal(traj[:, N] == 0, torch.as_tensor(m, device='cuda')[:, :, None].expand(-1, -1, traj.shape[3]))
+        _outage_sums_moved(eng, reset_outage, m.any(axis=0))
+        _outage_sums_moved(ref, reset_outage, m.any(axis=0))
     assert torch.equal(traj[K - 1, N], eng.net) and torch.equal(traj[K - 1, S], eng.soc) and torch.equal(traj[K - 1, R], eng.reward_bldg)
 
 
@@ -111,7 +133,8 @@ def _check_2(name, kind, E, f64):
     ret, traj = _roll(eng, pt, K, seed=5)
     assert eng.last_kernels == f"cl_rollout_full_policy_kpi_kernel<{_prec(f64)}, {'true' if kind == 'MARL' else 'false'}>", eng.last_kernels
     ref = StepEngine(tab, E, reward=kind, kpi=True, f64_maps=f64)
-    _replay(ref, pt, traj, eng, ret, f'thermal policy kpi rollout vs single steps {name} {kind} E={E} f64_maps={f64}')
+    _replay(ref, pt, traj, eng, ret, f'thermal policy kpi rollout vs single steps {name} {kind} E={E} f64_maps={f64}', tab=tab)
+    assert bool(tab.outage[:K].any()) == name.endswith('_outage')
     assert eng.t == K and float(eng.kpi_env[abi.CLKE_DAY_N].min()) == 1.0 == float(eng.kpi_env[abi.CLKE_PER_COND + abi.CLKE_DAY_N].min())
     assert bool((eng.kpi_bldg[abi.CLK_B_NET] != 0).all())           # every env keeps its own baseline, not only its block's first
     return eng
@@ -125,23 +148,49 @@ def test_2_kpis_equal_single_steps(kind, f64, E):
     _check_2('g2020_cz1', kind, E, f64)
 
 
+@pytest.mark.parametrize('E', [64, 260])
+@pytest.mark.parametrize('f64', ['chain', False])
+@pytest.mark.parametrize('kind', KINDS)
+def test_2_kpis_equal_single_steps_under_an_outage(kind, f64, E):
+    """The same on the nine-building outage district: the launch meets outage rows 5 .. 16 (staggered) and 22 .. 26 (common, across the day
+    group and a fold), in six of its nine waves.  The two outage sums: bit-equal to the single-step path's (`_compare_kpi`), moved for the
+    buildings with outage rows, at their reset value for buildings 2, 5 and 8, 0 <= unserved <= expected (`_replay`)."""
+    _check_2('g2020_cz1_outage', kind, E, f64)
+
+
 @pytest.mark.parametrize('f64', ['chain', False])
 @pytest.mark.parametrize('kind', ['RewardFunction', 'MARL'])
-@pytest.mark.parametrize('name', ['t1', 't2', 't16'])
+@pytest.mark.parametrize('name', ['t1', 't2', 't16', 't1_outage', 't2_outage', 't16_outage'])
 def test_2_kpis_equal_single_steps_on_the_geometry_districts(name, kind, f64):
-    """One building (one wave folds both series), two (one without DHW storage), sixteen (the largest LDS request: above 64 KiB, the launch opts in)."""
+    """One building (one wave folds both series), two (one without DHW storage), sixteen (the largest LDS request: above 64 KiB, the launch opts in);
+    and their outage versions (the one wave at times on an outage row alone; sixteen with five buildings that never see one)."""
     eng = _check_2(name, kind, 64, f64)
-    assert (_lib.policy_full_kpi_lds_bytes(eng.n_bldg) > 65536) == (name == 't16')
+    assert (_lib.policy_full_kpi_lds_bytes(eng.n_bldg) > 65536) == name.startswith('t16')
 
 
 # ---- 3. finalised KPIs ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('f64', ['chain', False])
 def test_3_finalised_kpis(f64):
     """`VectorCityLearnEnv(kpi=True).rollout_policy(spolicy, 57, kpi=True)` + `evaluate()` against an env that steps the recorded actions."""
+    _check_3(f64, golden('g2020_cz1').schema_path, 'g2020_cz1')
+
+
+@pytest.mark.parametrize('f64', ['chain', False])
+def test_3_finalised_kpis_under_an_outage(f64):
+    """The same through an env built from the nine-building outage district's spec: every outage row of the fixture is inside the 57 steps, and
+    the two unserved-energy KPIs of the district come out finite and positive (on the plain district the outage one is 0 / 0)."""
+    got = _check_3(f64, thermal_district('g2020_cz1_outage'), 'g2020_cz1_outage')
+    for name in ('power_outage_normalized_unserved_energy_total', 'annual_normalized_unserved_energy_total'):
+        v = got[1][name]
+        assert bool(torch.isfinite(v).all()) and bool((v > 0).all()) and bool((v <= 1).all()), (name, v)
+    per_building = got[0]['power_outage_normalized_unserved_energy_total']
+    assert bool(torch.isfinite(per_building[[0, 1, 3, 4, 6, 7]]).all()) and not bool(torch.isfinite(per_building[[2, 5, 8]]).any())
+
+
+def _check_3(f64, schema, name):
     from citylearn_amd.vector_env import VectorCityLearnEnv
-    g = golden('g2020_cz1')
     E, K = 64, 57
-    mk = lambda: VectorCityLearnEnv(g.schema_path, E, kpi=True, reward_function=REWARD_CLASS, f64_maps=f64)
+    mk = lambda: VectorCityLearnEnv(schema, E, kpi=True, reward_function=REWARD_CLASS, f64_maps=f64)
     a, b = mk(), mk()
     b.engine.trace_kernels()
     layout = ObservationLayout(b.spec, 'current', False)
@@ -158,7 +207,8 @@ def test_3_finalised_kpis(f64):
     _finalised_close(got, want)
     assert got[0] and got[1] and any(bool(torch.isfinite(v).all()) for v in got[1].values())
     fin = lambda g_, r_: max([_bar(g_[n], r_[n]) for n in r_ if bool(torch.isfinite(r_[n]).any())] or [0.0])
-    record_worst({'building': fin(got[0], want[0]), 'district': fin(got[1], want[1])}, f'thermal policy kpi finalised g2020_cz1 f64_maps={f64}')
+    record_worst({'building': fin(got[0], want[0]), 'district': fin(got[1], want[1])}, f'thermal policy kpi finalised {name} f64_maps={f64}')
+    return got
 
 
 # ---- 4. the policy is still the policy ------------------------------------------------------------------------------------------------
@@ -196,20 +246,44 @@ def test_4_free_running_against_the_cpu():
 def test_5_split_launches_and_checkpoint_are_bit_identical(f64):
     """Launches of 1, 5, 24 and 25 steps, with a `state_dict` round trip into a fresh engine in between, equal one 55-step launch bit for bit --
     the record, the state, the outputs and every KPI plane (the folds of the district series close on the absolute step index).  MARL, noise on."""
+    _check_5(f64, 'g2020_cz1', (1, 5, 24, 25))
+
+
+@pytest.mark.parametrize('split', [(1, 5, 24, 25), (30, 25), (27, 13, 15)], ids=lambda x: '+'.join(map(str, x)))
+@pytest.mark.parametrize('f64', ['chain', False])
+def test_5_split_launches_under_an_outage(f64, split):
+    """The same on the nine-building outage district, every KPI plane bit for bit.  1 + 5 + 24 + 25: the first launch meets no outage row (it
+    must not store the two outage sums), the boundary at step 6 lies inside the first outage of buildings 0 and 1.  30 + 25 and 27 + 13 + 15: a
+    launch that saw no outage row of a building (the middle one, rows 27 .. 39: of none) must leave alone the sums an earlier launch moved."""
+    _check_5(f64, 'g2020_cz1_outage', split)
+
+
+def _check_5(f64, district, split):
     E = 320
-    spec, tab, layout, pol, pt, one = _setup(E, f64, 'MARL', sigma=0.1)
+    spec, tab, layout, pol, pt, one = _setup(E, f64, 'MARL', sigma=0.1, district=district)
     ret1, traj1 = _roll(one, pt, 55, seed=3)
+    assert one.last_kernels == f'cl_rollout_full_policy_kpi_kernel<{_prec(f64)}, true>', one.last_kernels
     mk = lambda: StepEngine(tab, E, reward='MARL', kpi=True, f64_maps=f64)
     eng = mk()
     ret, parts = torch.zeros(E, device='cuda'), []
-    for n, K in enumerate((1, 5, 24, 25)):
+    reset_outage = eng.kpi_bldg[OUTAGE].clone()
+    m = outage_mask(tab, 55)
+    for n, K in enumerate(split):
         if n == 2:
             sd = eng.state_dict()
             eng = mk()
             eng.load_state_dict(sd)
         traj = torch.empty((K, policy.CLPF_NT, eng.n_bldg, E), device='cuda')
+        before = eng.kpi_bldg[OUTAGE].clone()
         eng.rollout_policy(K, pt, seed=3, ret_env=ret, traj=traj, kpi=True)
         parts.append(traj)
+        if m.any():
+            seen = m[eng.t - K:eng.t].any(axis=0)
+            _outage_sums_moved(eng, before, seen)
+            if not seen.any() and eng.t > 26:  # (the sums an earlier launch moved are still there)
+                assert not torch.equal(before, reset_outage)
+    if m.any():
+        _outage_sums_moved(one, reset_outage, m.any(axis=0))
     assert eng.t == 55 and torch.equal(torch.cat(parts), traj1)
     assert torch.equal(eng.state, one.state) and torch.equal(eng.out_bldg, one.out_bldg) and torch.equal(eng.out_env, one.out_env)
     assert torch.equal(eng.kpi_bldg, one.kpi_bldg) and torch.equal(eng.kpi_env, one.kpi_env)
@@ -232,18 +306,48 @@ def test_6_month_boundary_inside_a_launch():
     assert eng.t == 740 and float(eng.kpi_env[mon].min()) == 1.0 == float(eng.kpi_env[mon].max())
 
 
+def test_6_launch_ending_on_an_outage_row():
+    """K = 25 on the nine-building outage district: the last step (24) lies inside the common outage 22 .. 26, so the `CLD_DETAIL_MIN` planes the
+    chain launch leaves in `out_bldg` for the next KPI pass are an OUTAGE step's (expected and served energy, baseline net, delivered demands)
+    -- against the single steps (`_replay`: 2e-5), and the served energy of an outage row differs from the expected one somewhere."""
+    E, K = 64, 25
+    spec, tab, layout, pol, pt, eng = _setup(E, 'chain', sigma=0.1, district='g2020_cz1_outage')
+    ref = StepEngine(tab, E, kpi=True, f64_maps='chain')
+    ret, traj = _roll(eng, pt, K, seed=4)
+    assert eng.last_kernels == 'cl_rollout_full_policy_kpi_kernel<2, false>', eng.last_kernels
+    _replay(ref, pt, traj, eng, ret, 'thermal policy kpi rollout vs single steps g2020_cz1_outage launch ending on an outage row', tab=tab)
+    dark = torch.as_tensor(outage_mask(tab, K)[K - 1], device='cuda')
+    assert dark.tolist() == [i % 3 != 2 for i in range(9)] and not eng.net[dark].any() and bool((eng.net[~dark] != 0).all())
+    ex, sv = eng.out_bldg[abi.CLO_EXPECTED], eng.out_bldg[abi.CLO_SERVED]
+    assert bool((sv[dark] <= ex[dark]).all()) and bool((sv[dark] < ex[dark]).any()) and bool((ex[dark] > 0).all())
+
+
 # ---- 7. windows, sets, offsets ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('f64', ['chain', False])
 def test_7_windows_sets_and_env_offsets(f64):
     """Two env blocks with different `env_row0` and different parameter sets in one 512-env launch: each block equals, bit for bit, a 256-env
     engine of its own with that window, that set and its env offset -- the KPI planes too."""
-    spec = golden('g2020_cz1').spec()
+    _check_7(f64, 'g2020_cz1')
+
+
+@pytest.mark.parametrize('f64', ['chain', False])
+def test_7_windows_sets_and_env_offsets_under_an_outage(f64):
+    """The same on the nine-building outage district: the outage rows lie in block 0's window (rows 0 .. 29) only -- block 1 (rows 131 .. 160)
+    keeps its outage sums at the reset value while block 0's move, in one launch."""
+    _check_7(f64, 'g2020_cz1_outage')
+
+
+def _check_7(f64, district):
+    spec = thermal_district(district)
     tab = spec.episode_tables(0)
     layout = ObservationLayout(spec, 'current', True)
     pol = make_storage_policy(layout, 16, n_sets=2, seed=2, sigma=0.1)
     K, n_steps, rows = 30, 200, [0, 131]
     whole = StepEngine(tab, 512, kpi=True, f64_maps=f64, n_steps=n_steps, env_row0=rows)
+    whole.trace_kernels()
+    reset_outage = whole.kpi_bldg[OUTAGE].clone()
     _, traj = _roll(whole, pol.pack(layout, tab, device='cuda:0', set_of_block=[0, 1]), K, seed=9)
+    assert whole.last_kernels == f'cl_rollout_full_policy_kpi_kernel<{_prec(f64)}, false>', whole.last_kernels
     assert not torch.equal(traj[:, A:A + NA, :, :256], traj[:, A:A + NA, :, 256:])
     for g in range(2):
         part = StepEngine(tab, 256, kpi=True, f64_maps=f64, n_steps=n_steps, env_row0=[rows[g]], env_offset=256 * g)
@@ -255,6 +359,15 @@ def test_7_windows_sets_and_env_offsets(f64):
         assert torch.equal(part.kpi_bldg, whole.kpi_bldg[:, :, sl]) and torch.equal(part.kpi_env, whole.kpi_env[:, sl]), g
     base = whole.kpi_bldg[abi.CLK_B_NET]
     assert bool((base != 0).all()) and float(base[0, 0]) != float(base[0, 256])
+    if tab.outage.any():
+        assert tab.outage[:K].any() and not tab.outage[rows[1]:rows[1] + K].any()
+        now = whole.kpi_bldg[OUTAGE]
+        assert torch.equal(now[:, :, 256:], reset_outage[:, :, 256:])
+        has = torch.as_tensor(tab.outage[:K].any(axis=0), device='cuda')
+        assert torch.equal(now[:, ~has, :256], reset_outage[:, ~has, :256]) and bool((now[1][has][:, :256] > reset_outage[1][has][:, :256]).all())
+        assert bool((now[0] >= 0).all()) and bool((now[0] <= now[1]).all()) and bool((now[0][has][:, :256] > 0).any(dim=1).all())
+    else:
+        assert torch.equal(whole.kpi_bldg[OUTAGE], reset_outage)
 
 
 # ---- 8. refusals and defaults -----------------------------------------------------------------------------------------------------------

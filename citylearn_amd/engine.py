@@ -512,9 +512,8 @@ class StepEngine:
         `cl_rollout_full_policy_kpi_kernel` (`clpfk_rollout_mlp_kpi_f32`, ``libcitylearn_amd_policy_full_kpi.so``), which keeps every env's
         twelve per-building sums and both district series and, under the float64 chain, leaves the last step's `CLD_DETAIL_MIN` planes in
         ``out_bldg``; on an engine built without KPIs it raises `NotImplementedError`."""
-        from . import policy as _policy
-        storage = isinstance(policy_tables, _policy.StoragePolicyTables)
-        if storage and kpi and not self.kpi:
+        kind = policy_tables.kind           # (`policy._Kind`: the libraries, the trajectory's plane count and what a build without KPIs raises)
+        if kpi and not self.kpi and kind.no_kpi_error is NotImplementedError:
             raise NotImplementedError('rollout_policy(kpi=True) with StoragePolicyTables: this engine was built without the streaming KPI accumulators -- '
                                       'build it with kpi=True (the thermal policy KPI kernel, cl_rollout_full_policy_kpi_kernel, needs them)')
         if kpi and not self.kpi:
@@ -523,10 +522,9 @@ class StepEngine:
             # (the library cannot see this: a battery + PV district with EV chargers / washing machines and a non-EV reward has CLD_LEAN set)
             raise NotImplementedError('rollout_policy: districts with flexible loads (EV chargers / washing machines) are not covered by the policy '
                                       'kernel -- it would leave their consumption out of net; use step() / capture_rollout')
-        ext = (_lib.POLICY_FULL_KPI if kpi else _lib.POLICY_FULL) if storage else _lib.POLICY_KPI if kpi else _lib.POLICY
+        ext = kind.ext_kpi if kpi else kind.ext
         ext.load()          # (here, not only inside ext.rollout: a missing library is reported in front of the argument checks below)
         kpi_planes = (_ptr(self.kpi_bldg), _ptr(self.kpi_env)) if kpi else ()
-        n_planes = _policy.CLPF_NT if storage else _policy.CLPOL_NT
         t0 = self.t if t0 is None else t0
         pt = policy_tables
         if (pt.n_rows, pt.n_bldg) != (self.n_ts_rows, self.n_bldg) or pt.pre.device != self.device:
@@ -536,7 +534,7 @@ class StepEngine:
             raise ValueError(f'policy tables hold {pt.act_low.numel()} action columns, the engine {self.n_act_cols}')
         if pt.set_of_block is not None and pt.set_of_block.numel() != -(-self.n_env // abi.CL_ROW0_BLOCK):
             raise ValueError(f'set_of_block needs one entry per {abi.CL_ROW0_BLOCK} envs')
-        for name, x, shape in (('ret_env', ret_env, (self.n_env,)), ('traj', traj, (k_steps, n_planes, self.n_bldg, self.n_env))):
+        for name, x, shape in (('ret_env', ret_env, (self.n_env,)), ('traj', traj, (k_steps, kind.n_planes, self.n_bldg, self.n_env))):
             if x is not None and (x.dtype != torch.float32 or x.device != self.device or tuple(x.shape) != shape or not x.is_contiguous()):
                 raise ValueError(f'{name} must be a contiguous float32 tensor {shape} on {self.device}')
         mlp = pt.struct(seed)

@@ -46,10 +46,10 @@ outages goes through the same two kernels (their outage branch is tested on g202
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import re
-from typing import List, Optional
+from dataclasses import dataclass
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -61,11 +61,25 @@ from .observations import SRC_OUT, SRC_STATE, SRC_TEMP, ObservationLayout
 # the packed first layer (`pre`, `dep`)
 ACT_SCALE = -2.0 * math.log2(math.e)
 
-_H = re.sub(r'/\*.*?\*/', ' ', _lib.POLICY_HEADER.read_text(), flags=re.S)
-CONSTANTS = {m.group(1): int(m.group(2).rstrip('ulUL'), 0) for m in re.finditer(r'#define\s+(CLPOL_\w+)\s+(0x[0-9a-fA-F]+\w*|\d+)\b', _H)}
+
+def _header_constants(header, prefix: str) -> dict:
+    """The integer ``#define``s of an extension header that start with `prefix`."""
+    text = re.sub(r'/\*.*?\*/', ' ', header.read_text(), flags=re.S)
+    return {m.group(1): int(m.group(2).rstrip('ulUL'), 0) for m in re.finditer(rf'#define\s+({prefix}\w+)\s+(0x[0-9a-fA-F]+\w*|\d+)\b', text)}
+
+
+CONSTANTS = _header_constants(_lib.POLICY_HEADER, 'CLPOL_')
 CLPOL_NT, CLPOL_T_ACTION, CLPOL_T_REWARD, CLPOL_T_NET, CLPOL_T_SOC = (CONSTANTS[k] for k in ('CLPOL_NT', 'CLPOL_T_ACTION', 'CLPOL_T_REWARD',
                                                                                              'CLPOL_T_NET', 'CLPOL_T_SOC'))
 CLPOL_NOISE_KEY, CLPOL_MAX_HIDDEN = CONSTANTS['CLPOL_NOISE_KEY'], CONSTANTS['CLPOL_MAX_HIDDEN']
+# thermal districts: up to four storage heads per building (csrc/cl_policy_full.h, libcitylearn_amd_policy_full.so)
+FULL_CONSTANTS = _header_constants(_lib.POLICY_FULL_HEADER, 'CLPF_')
+CLPF_NT, CLPF_ND, CLPF_NA, CLPF_MAX_HIDDEN = (FULL_CONSTANTS[k] for k in ('CLPF_NT', 'CLPF_ND', 'CLPF_NA', 'CLPF_MAX_HIDDEN'))
+CLPF_T_ACTION, CLPF_T_REWARD, CLPF_T_NET, CLPF_T_SOC = (FULL_CONSTANTS[k] for k in ('CLPF_T_ACTION', 'CLPF_T_REWARD', 'CLPF_T_NET', 'CLPF_T_SOC'))
+CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET = (FULL_CONSTANTS[k] for k in ('CLPF_D_SOC', 'CLPF_D_CS', 'CLPF_D_HS', 'CLPF_D_DS', 'CLPF_D_NET'))
+CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS = (FULL_CONSTANTS[k] for k in ('CLPF_A_ES', 'CLPF_A_CS', 'CLPF_A_HS', 'CLPF_A_DS'))
+assert FULL_CONSTANTS['CLPF_NOISE_KEY'] == CLPOL_NOISE_KEY                       # `noise_host` replays both kernels' streams
+HEAD_NAMES = ('electrical_storage', 'cooling_storage', 'heating_storage', 'dhw_storage')                  # heads in CLPF_A_* order
 
 
 def building_columns(layout: ObservationLayout) -> List[List[int]]:
@@ -106,52 +120,110 @@ def noise_host(seed: int, env, col: int, t: int) -> np.ndarray:
     return np.sqrt(-2.0 * np.log(x)) * np.cos(2.0 * np.pi * u2)
 
 
-class PolicyTables:
-    """`MLPPolicy.pack`'s result: the tables of `clpol_mlp` as float32 tensors on one device (the layouts of the header)."""
+class _Tables:
+    """A policy's `pack` result: the tables of the kind's struct (`clpol_mlp` / `clpf_mlp`) as float32 tensors on one device (the layouts of
+    the header), and on the host what `actions_host(..., tables=this)` evaluates the reference with: ``cols`` (int64), ``low_bldg`` /
+    ``high_bldg`` / ``sigma_bldg`` (float64) -- every head's action column (-1: none), that column's bounds and sigma."""
+    kind: '_Kind'                                                        # set by the kind that names the class
 
-    def __init__(self, pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, es_cols, low_bldg, high_bldg, sigma_bldg, version):
+    def __init__(self, pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, cols, low_bldg, high_bldg, sigma_bldg, n_device_cols, version):
         self.pre, self.dep, self.out, self.net_reset = pre, dep, out, net_reset
         self.act_low, self.act_high, self.sigma, self.set_of_block = act_low, act_high, sigma, set_of_block
-        # host side, float64 / int64 [n_bldg]: every building's storage action column (-1: none), that column's bounds and sigma -- what
-        # `MLPPolicy.actions_host(..., tables=this)` evaluates the reference with
-        self.es_cols, self.low_bldg, self.high_bldg, self.sigma_bldg = es_cols, low_bldg, high_bldg, sigma_bldg
-        self.version = version                                           # `MLPPolicy.version` the tables were packed from
+        self.cols, self.low_bldg, self.high_bldg, self.sigma_bldg = cols, low_bldg, high_bldg, sigma_bldg
+        self.n_device_cols = int(n_device_cols)                          # (the struct's third word: 0, device action columns are refused)
+        self.version = version                                           # the policy's `version` the tables were packed from
         self.n_sets, self.n_rows, self.n_bldg, self.n_hidden = (int(x) for x in pre.shape)
 
-    def struct(self, seed: int) -> _lib.PolicyMLP:
+    def struct(self, seed: int):
         p = lambda t: None if t is None else t.data_ptr()
-        return _lib.PolicyMLP(self.n_hidden, self.n_sets, 0, 0, p(self.pre), p(self.dep), p(self.out), p(self.set_of_block), p(self.net_reset),
-                              p(self.act_low), p(self.act_high), p(self.sigma), int(seed) & (2 ** 64 - 1))
+        return self.kind.struct(self.n_hidden, self.n_sets, self.n_device_cols, 0, p(self.pre), p(self.dep), p(self.out), p(self.set_of_block),
+                                p(self.net_reset), p(self.act_low), p(self.act_high), p(self.sigma), int(seed) & (2 ** 64 - 1))
 
 
-class MLPPolicy:
-    """``a = clamp(mid + half tanh(w2 . tanh(W1 obs + b1) + b2) + sigma z, low, high)`` per building, `obs` = the building's own observation
-    vector as the env defines it (``ObservationLayout.building_names[i]``: normalised or not, whatever the env was built with), (low, high) =
-    the bounds of the building's electrical-storage action, z ~ N(0, 1).
+class PolicyTables(_Tables):
+    """`MLPPolicy.pack`'s result (`_Tables`), ``[n_bldg]`` on the host side: `es_cols` = every building's storage action column."""
 
-    ``w1 [n_sets, n_bldg, H, n_obs]``, ``b1 [n_sets, n_bldg, H]``, ``w2 [n_sets, n_bldg, H]``, ``b2 [n_sets, n_bldg]`` (anything array-like;
-    kept in float64); a leading dimension of 1 broadcasts -- shared weights over the buildings and / or one parameter set.  ``H``: 4, 8, .. 32.
-    ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
+    def __init__(self, pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, es_cols, low_bldg, high_bldg, sigma_bldg, version):
+        super().__init__(pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, es_cols, low_bldg, high_bldg, sigma_bldg, 0, version)
 
-    **The packed tables are a snapshot.**  `pack` reads the weights once; `VectorCityLearnEnv.rollout_policy` caches the packed tables per
-    (policy object, `version`, episode window).  Change the weights through :meth:`update` (or assign the arrays and call :meth:`invalidate`):
-    both bump `version`, so the next `rollout_policy` packs again.  Arrays edited in place without that keep driving the OLD policy."""
+    es_cols = property(lambda self: self.cols)
+
+
+class StoragePolicyTables(_Tables):
+    """`StorageMLPPolicy.pack`'s result (`_Tables`), ``[n_bldg, CLPF_NA]`` on the host side."""
+
+
+@dataclass(frozen=True)
+class _Kind:
+    """What tells the two policies apart, as data -- the packer, the references and `rollout_policy` read it and are written once."""
+    terms: Tuple[tuple, ...]          # the env-dependent inputs in `dep`'s row order: ((source kind, plane), building flag that gates the term | None)
+    head_slots: Tuple[int, ...]       # per head, the slot of `tab.params` that holds its action column
+    head_shape: Tuple[int, ...]       # the head axis of w2 / b2 / out / cols: () for the single head without one
+    refuse_device_actions: bool
+    only: str                         # the wrong-plane refusal: what the kernel does have
+    tables: type
+    struct: type
+    constants: dict                   # the header's
+    max_hidden: int
+    n_planes: int                     # of a recorded trajectory
+    ext: '_lib._Extension'            # the rollout library, and the one that also keeps the streaming KPIs
+    ext_kpi: '_lib._Extension'
+    no_kpi_error: type                # what `rollout_policy(kpi=True)` raises on a build without KPIs
+
+    def __post_init__(self):
+        self.tables.kind = self
+
+
+_DEVICE_SLOTS = (('cooling_device', abi.CLP_ACT_COOL_DEV), ('heating_device', abi.CLP_ACT_HEAT_DEV), ('cooling_or_heating_device', abi.CLP_ACT_COH_DEV))
+_LEAN = _Kind(terms=(((SRC_STATE, abi.CLS_B_SOC), None), ((SRC_OUT, abi.CLO_NET), None)), head_slots=(abi.CLP_ACT_ELEC_STO,), head_shape=(),
+              refuse_device_actions=False,
+              only="the policy kernel only has the building's own electrical_storage_soc (CLS_B_SOC) and net_electricity_consumption (CLO_NET)",
+              tables=PolicyTables, struct=_lib.PolicyMLP, constants=CONSTANTS, max_hidden=CLPOL_MAX_HIDDEN, n_planes=CLPOL_NT,
+              ext=_lib.POLICY, ext_kpi=_lib.POLICY_KPI, no_kpi_error=ValueError)
+_THERMAL = _Kind(terms=(((SRC_STATE, abi.CLS_B_SOC), abi.CLF_BATTERY), ((SRC_STATE, abi.CLS_CS_SOC), abi.CLF_COOL_STO), ((SRC_STATE, abi.CLS_HS_SOC), abi.CLF_HEAT_STO),
+                        ((SRC_STATE, abi.CLS_DS_SOC), abi.CLF_DHW_STO), ((SRC_OUT, abi.CLO_NET), None)),           # rows CLPF_D_SOC, _CS, _HS, _DS, _NET
+                 head_slots=(abi.CLP_ACT_ELEC_STO, abi.CLP_ACT_COOL_STO, abi.CLP_ACT_HEAT_STO, abi.CLP_ACT_DHW_STO), head_shape=(CLPF_NA,),    # CLPF_A_*
+                 refuse_device_actions=True,
+                 only="the thermal policy kernel only has the building's own storage socs (CLS_B_SOC, CLS_CS_SOC, CLS_HS_SOC, CLS_DS_SOC) and "
+                      'net_electricity_consumption (CLO_NET)',
+                 tables=StoragePolicyTables, struct=_lib.PolicyFullMLP, constants=FULL_CONSTANTS, max_hidden=CLPF_MAX_HIDDEN, n_planes=CLPF_NT,
+                 ext=_lib.POLICY_FULL, ext_kpi=_lib.POLICY_FULL_KPI, no_kpi_error=NotImplementedError)
+# (terms and heads above are written in the header's order)
+assert (CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET) == tuple(range(CLPF_ND)) and (CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS) == tuple(range(CLPF_NA))
+
+
+def _head_columns(tab, kind: _Kind) -> np.ndarray:
+    hc = np.ascontiguousarray(tab.params).view(np.int32)[:, list(kind.head_slots)].astype(np.int64)
+    return hc if kind.head_shape else hc[:, 0]
+
+
+def head_columns(tab) -> np.ndarray:
+    """``[n_bldg, CLPF_NA]`` the action column of every building's electrical / cooling / heating / DHW storage (-1: none), as the kernel reads them."""
+    return _head_columns(tab, _THERMAL)
+
+
+class _MLPBase:
+    """What `MLPPolicy` and `StorageMLPPolicy` share: everything but the class's `kind`, the contraction of the hidden layer with the head(s)
+    (`_heads`, `_heads_torch`) and the signature of `actions_host`."""
+    kind: _Kind
 
     def __init__(self, w1, b1, w2, b2, sigma=None):
         self.w1, self.b1, self.w2, self.b2 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2))
-        if self.w1.ndim != 4 or self.b1.ndim != 3 or self.w2.ndim != 3 or self.b2.ndim != 2:
-            raise ValueError('w1 [n_sets, n_bldg, H, n_obs], b1 [n_sets, n_bldg, H], w2 [n_sets, n_bldg, H], b2 [n_sets, n_bldg]')
+        hs = self.kind.head_shape
+        if self.w1.ndim != 4 or self.b1.ndim != 3 or self.w2.ndim != 3 + len(hs) or self.b2.ndim != 2 + len(hs):
+            heads = ''.join(f', {n}' for n in hs)
+            raise ValueError(f'w1 [n_sets, n_bldg, H, n_obs], b1 [n_sets, n_bldg, H], w2 [n_sets, n_bldg{heads}, H], b2 [n_sets, n_bldg{heads}]')
         self.n_hidden, self.n_obs = int(self.w1.shape[2]), int(self.w1.shape[3])
-        if self.n_hidden % 4 or not 4 <= self.n_hidden <= CLPOL_MAX_HIDDEN:
-            raise ValueError(f'H={self.n_hidden}: the policy kernel takes 4, 8, .. {CLPOL_MAX_HIDDEN} hidden units')
-        if self.b1.shape[2] != self.n_hidden or self.w2.shape[2] != self.n_hidden:
-            raise ValueError('b1 / w2 disagree with w1 about H')
+        if self.n_hidden % 4 or not 4 <= self.n_hidden <= self.kind.max_hidden:
+            raise ValueError(f'H={self.n_hidden}: the policy kernel takes 4, 8, .. {self.kind.max_hidden} hidden units')
+        if self.b1.shape[2] != self.n_hidden or self.w2.shape[2:] != hs + (self.n_hidden,) or self.b2.shape[2:] != hs:
+            raise ValueError('b1 / w2 / b2 disagree with w1 about H' + ''.join(f', or do not have {n} heads' for n in hs))
         self.n_sets = max(x.shape[0] for x in (self.w1, self.b1, self.w2, self.b2))
         self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
         self.version = 0
 
     def invalidate(self) -> None:
-        """Tell the caches that the weights changed (see the class docstring)."""
+        """Tell the caches that the weights changed (see `MLPPolicy`'s docstring)."""
         self.version += 1
 
     def update(self, w1=None, b1=None, w2=None, b2=None, sigma=None) -> None:
@@ -167,32 +239,22 @@ class MLPPolicy:
         self.invalidate()
 
     def _full(self, n_bldg: int):
-        S, H = self.n_sets, self.n_hidden
+        S, H, hs = self.n_sets, self.n_hidden, self.kind.head_shape
         try:
             return (np.broadcast_to(self.w1, (S, n_bldg, H, self.n_obs)), np.broadcast_to(self.b1, (S, n_bldg, H)),
-                    np.broadcast_to(self.w2, (S, n_bldg, H)), np.broadcast_to(self.b2, (S, n_bldg)))
+                    np.broadcast_to(self.w2, (S, n_bldg) + hs + (H,)), np.broadcast_to(self.b2, (S, n_bldg) + hs))
         except ValueError as e:
             raise ValueError(f'the weights do not broadcast to {S} sets x {n_bldg} buildings: {e}') from None
 
     # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
-    def actions_host(self, obs_vectors, noise=None, tables: Optional[PolicyTables] = None, low=None, high=None, sigma_bldg=None,
-                     set_index: int = 0) -> np.ndarray:
-        """float64 numpy evaluation of the plain MLP: ``obs_vectors [..., n_bldg, n_obs]`` -> actions ``[..., n_bldg]``.  ``noise``: the
-        standard normals z (same shape as the result; `noise_host` replays the kernel's), scaled by each building's sigma.  The bounds of the
-        buildings' storage actions and their sigmas (``[n_bldg]`` each) come from ``tables`` (a `pack` result: `low_bldg`, `high_bldg`,
-        `sigma_bldg`) or from the arguments; without either: -1 / 1 and the policy's scalar sigma.  Nothing is remembered between calls."""
+    def _actions_host(self, obs_vectors, lo, hi, noise, sigma, set_index: int) -> np.ndarray:
+        """``clip(mid + half tanh(heads) + sigma() noise, lo, hi)`` in float64 numpy (`sigma` is only called where there is noise)."""
         x = np.asarray(obs_vectors, dtype=np.float64)
-        n_bldg = x.shape[-2]
-        w1, b1, w2, b2 = (v[set_index] for v in self._full(n_bldg))
-        pick = lambda arg, attr, default: np.asarray(arg if arg is not None else getattr(tables, attr) if tables is not None else default, dtype=np.float64)
-        lo, hi = pick(low, 'low_bldg', -1.0), pick(high, 'high_bldg', 1.0)
+        w1, b1, w2, b2 = (v[set_index] for v in self._full(x.shape[-2]))
         h = np.tanh(np.einsum('bjc,...bc->...bj', w1, x) + b1)
-        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('bj,...bj->...b', w2, h) + b2)
+        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(self._heads(w2, h) + b2)
         if noise is not None:
-            if sigma_bldg is None and tables is None and self.sigma is not None and self.sigma.ndim:
-                raise ValueError('a per-column sigma needs `tables` (or `sigma_bldg`): which column drives which building')
-            sg = pick(sigma_bldg, 'sigma_bldg', 0.0 if self.sigma is None or self.sigma.ndim else float(self.sigma))
-            a = a + sg * np.asarray(noise, dtype=np.float64)
+            a = a + sigma() * np.asarray(noise, dtype=np.float64)
         return np.clip(a, lo, hi)
 
     def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
@@ -200,23 +262,22 @@ class MLPPolicy:
         ``f(obs [n_envs, n_obs_total], i=None) -> actions [n_act_cols, n_envs]`` -- a `VectorCityLearnEnv.capture_rollout` policy; what
         `rollout_policy` replaces with one launch, and what the tests compare it with."""
         cols = building_columns(layout)
-        n_bldg = len(cols)
-        w1, b1, w2, b2 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(n_bldg))
+        w1, b1, w2, b2 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(len(cols)))
         idx = torch.as_tensor(np.array([c + [c[0]] * (self.n_obs - len(c)) for c in cols]), device=device)
         mask = torch.as_tensor(np.array([[1.0] * len(c) + [0.0] * (self.n_obs - len(c)) for c in cols]), dtype=dtype, device=device)
-        params = np.ascontiguousarray(tab.params).view(np.int32)
-        es = params[:, abi.CLP_ACT_ELEC_STO].astype(np.int64)
-        n_act = int(params[:, abi.CLP_ACT_COOL_STO:abi.CLP_ACT_COH_DEV + 1].max()) + 1
+        hc = _head_columns(tab, self.kind)
         low, high = layout.spec.action_limits()
-        driven = np.nonzero(es >= 0)[0]
-        lo = torch.as_tensor(np.asarray(low)[es[driven]], dtype=dtype, device=device)
-        hi = torch.as_tensor(np.asarray(high)[es[driven]], dtype=dtype, device=device)
-        rows, drv = torch.as_tensor(es[driven], device=device), torch.as_tensor(driven, device=device)
+        sel = np.nonzero(hc >= 0)                                                # the heads that have a column
+        rows = torch.as_tensor(hc[sel], device=device)
+        lo = torch.as_tensor(np.asarray(low)[hc[sel]], dtype=dtype, device=device)
+        hi = torch.as_tensor(np.asarray(high)[hc[sel]], dtype=dtype, device=device)
+        flat = torch.as_tensor(np.ravel_multi_index(sel, hc.shape), device=device)
+        n_act = len(low)
 
         def f(obs, i=None):
             x = obs.to(dtype)[:, idx] * mask                                     # [E, B, n_obs]
             h = torch.tanh(torch.einsum('bjc,ebc->ebj', w1, x) + b1)
-            o = torch.tanh((w2 * h).sum(dim=2) + b2)[:, drv]                     # [E, driven]
+            o = torch.tanh(self._heads_torch(w2, h) + b2).reshape(obs.shape[0], -1)[:, flat]          # [E, present heads]
             a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
             out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
             out[rows] = a.t().to(torch.float32)
@@ -224,22 +285,25 @@ class MLPPolicy:
         return f
 
     # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
-    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None) -> PolicyTables:
+    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None):
         """Split the first layer along the observation tables of `layout` over the episode tables `tab` (``layout.episode(tab,
         reset_table=True)``): the env-independent columns of every table row go into ``pre`` (one matmul in float64 on `device`, rounded
-        once), the ``col_scale`` of the two env-dependent columns -- the building's own ``electrical_storage_soc`` and
-        ``net_electricity_consumption`` -- into ``dep``, their table offsets into ``pre``.  A building observation fed by anything else on the
+        once), the ``col_scale`` of the env-dependent columns (the kind's terms, all the building's own) into ``dep``, one row per term (the
+        row of a storage the building lacks stays 0), their table offsets into ``pre``.  A building observation fed by anything else on the
         device raises ``ValueError`` naming the column.  ``set_of_block``: the parameter set of every block of ``abi.CL_ROW0_BLOCK`` envs."""
+        kind = self.kind
         obs = layout.episode(tab, reset_table=True)
         cols = building_columns(layout)
         n_bldg, T = len(cols), int(obs.table.shape[0])
         if any(len(c) > self.n_obs for c in cols) or not any(len(c) == self.n_obs for c in cols):
             raise ValueError(f'w1 takes {self.n_obs} observations, the buildings have {sorted(set(len(c) for c in cols))}')
         w1, b1, w2, b2 = self._full(n_bldg)
-        S, H = self.n_sets, self.n_hidden
-        table = obs.table.copy()
+        params_i = np.ascontiguousarray(tab.params).view(np.int32)
+        bflags = np.ascontiguousarray(tab.params).view(np.uint32)[:, abi.CLP_FLAGS]
+        term_of = {src: k for k, (src, _) in enumerate(kind.terms)}
+        table = obs.table
         x = np.zeros((T, n_bldg, self.n_obs))
-        scale = np.zeros((n_bldg, 2, self.n_obs))                        # [b][soc | net][position in the building's vector]
+        scale = np.zeros((n_bldg, len(kind.terms), self.n_obs))          # [b][term][position in the building's vector]
         net_reset = np.zeros((T, n_bldg))
         for i, bcols in enumerate(cols):
             for j, c in enumerate(bcols):
@@ -252,222 +316,32 @@ class MLPPolicy:
                                          'the policy kernel reads the tables of observation_mode="current"')
                     x[:, i, j] = table[:, c]
                     continue
-                kind, plane, b = src >> 28, (src >> 20) & 0xFF, src & 0xFFFFF
-                which = 0 if (kind, plane) == (SRC_STATE, abi.CLS_B_SOC) else 1 if (kind, plane) == (SRC_OUT, abi.CLO_NET) else None
+                kind_, plane, b = src >> 28, (src >> 20) & 0xFF, src & 0xFFFFF
+                which = term_of.get((kind_, plane))
                 if which is None or b != i or layout.columns[c][0] != i:
-                    raise ValueError(f'observation {name} is fed by device plane (kind {kind}, plane {plane}, building {b}): the policy kernel '
-                                     "only has the building's own electrical_storage_soc (CLS_B_SOC) and net_electricity_consumption (CLO_NET)")
+                    raise ValueError(f'observation {name} is fed by device plane (kind {kind_}, plane {plane}, building {b}): {kind.only}'
+                                     + (' -- the indoor temperature comes from the LSTM stage' if kind_ == SRC_TEMP else ''))
                 offset = table[1:, c] if T > 1 else np.zeros(1)
                 if np.ptp(offset) != 0.0:
                     raise ValueError(f'observation {name}: a table offset that changes with the row')
                 x[:, i, j] = offset[0]
-                scale[i, which, j] = float(obs.col_scale[c])
-                if which == 1 and scale[i, 1, j] != 0.0:
-                    net_reset[:, i] = (obs.reset_table[:, c] - offset[0]) / scale[i, 1, j]
-        dev = torch.device(device)
-        f64 = lambda v: torch.from_numpy(np.array(v, dtype=np.float64)).to(dev)
-        pre = (torch.einsum('sbjc,tbc->stbj', f64(w1), f64(x)) + f64(b1)[:, None]) * ACT_SCALE
-        dep = torch.einsum('sbjc,bkc->sbkj', f64(w1), f64(scale)) * ACT_SCALE
-        out = torch.cat([f64(w2), f64(b2)[:, :, None]], dim=2)
-        es = np.ascontiguousarray(tab.params).view(np.int32)[:, abi.CLP_ACT_ELEC_STO].astype(np.int64)
-        n_act = int(np.ascontiguousarray(tab.params).view(np.int32)[:, abi.CLP_ACT_COOL_STO:abi.CLP_ACT_COH_DEV + 1].max()) + 1
-        low, high = layout.spec.action_limits()
-        if len(low) != n_act:
-            raise ValueError(f'{len(low)} action limits for {n_act} action columns')
-        low_bldg = np.where(es >= 0, np.asarray(low, dtype=np.float64)[np.maximum(es, 0)], -1.0)
-        high_bldg = np.where(es >= 0, np.asarray(high, dtype=np.float64)[np.maximum(es, 0)], 1.0)
-        sigma = None
-        if self.sigma is not None:
-            sigma = np.full(n_act, float(self.sigma)) if self.sigma.ndim == 0 else self.sigma
-            if sigma.shape != (n_act,) or np.any(sigma < 0):
-                raise ValueError(f'sigma: a non-negative scalar or [{n_act}] (one per action column)')
-        f32 = lambda v: None if v is None else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev)
-        sob = None
-        if set_of_block is not None:
-            sob = np.asarray(set_of_block, dtype=np.int64).reshape(-1)
-            if sob.min() < 0 or sob.max() >= S:
-                raise ValueError(f'set_of_block outside [0, {S})')
-            sob = torch.from_numpy(sob.astype(np.int32)).to(dev)
-        return PolicyTables(pre.to(torch.float32).contiguous(), dep.to(torch.float32).contiguous(), out.to(torch.float32).contiguous(),
-                            f32(net_reset), f32(low), f32(high), f32(sigma), sob, es, low_bldg, high_bldg,
-                            np.zeros(n_bldg) if sigma is None else np.where(es >= 0, np.asarray(sigma, dtype=np.float64)[np.maximum(es, 0)], 0.0),
-                            self.version)
-
-
-# ---- thermal districts: up to four storage heads per building (csrc/cl_policy_full.h, libcitylearn_amd_policy_full.so) -------------------------
-_HF = re.sub(r'/\*.*?\*/', ' ', _lib.POLICY_FULL_HEADER.read_text(), flags=re.S)
-FULL_CONSTANTS = {m.group(1): int(m.group(2).rstrip('ulUL'), 0) for m in re.finditer(r'#define\s+(CLPF_\w+)\s+(0x[0-9a-fA-F]+\w*|\d+)\b', _HF)}
-CLPF_NT, CLPF_ND, CLPF_NA, CLPF_MAX_HIDDEN = (FULL_CONSTANTS[k] for k in ('CLPF_NT', 'CLPF_ND', 'CLPF_NA', 'CLPF_MAX_HIDDEN'))
-CLPF_T_ACTION, CLPF_T_REWARD, CLPF_T_NET, CLPF_T_SOC = (FULL_CONSTANTS[k] for k in ('CLPF_T_ACTION', 'CLPF_T_REWARD', 'CLPF_T_NET', 'CLPF_T_SOC'))
-CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET = (FULL_CONSTANTS[k] for k in ('CLPF_D_SOC', 'CLPF_D_CS', 'CLPF_D_HS', 'CLPF_D_DS', 'CLPF_D_NET'))
-CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS = (FULL_CONSTANTS[k] for k in ('CLPF_A_ES', 'CLPF_A_CS', 'CLPF_A_HS', 'CLPF_A_DS'))
-assert FULL_CONSTANTS['CLPF_NOISE_KEY'] == CLPOL_NOISE_KEY                       # `noise_host` replays both kernels' streams
-HEAD_NAMES = ('electrical_storage', 'cooling_storage', 'heating_storage', 'dhw_storage')                  # heads in CLPF_A_* order
-# per head: the parameter slot of its action column; per first-layer term: (source kind, plane) of the observation and the storage's flag bit
-_HEAD_SLOTS = (abi.CLP_ACT_ELEC_STO, abi.CLP_ACT_COOL_STO, abi.CLP_ACT_HEAT_STO, abi.CLP_ACT_DHW_STO)
-_DEVICE_SLOTS = (('cooling_device', abi.CLP_ACT_COOL_DEV), ('heating_device', abi.CLP_ACT_HEAT_DEV), ('cooling_or_heating_device', abi.CLP_ACT_COH_DEV))
-_TERMS = {(SRC_STATE, abi.CLS_B_SOC): CLPF_D_SOC, (SRC_STATE, abi.CLS_CS_SOC): CLPF_D_CS, (SRC_STATE, abi.CLS_HS_SOC): CLPF_D_HS,
-          (SRC_STATE, abi.CLS_DS_SOC): CLPF_D_DS, (SRC_OUT, abi.CLO_NET): CLPF_D_NET}
-_TERM_FLAGS = (abi.CLF_BATTERY, abi.CLF_COOL_STO, abi.CLF_HEAT_STO, abi.CLF_DHW_STO, None)
-
-
-def head_columns(tab) -> np.ndarray:
-    """``[n_bldg, CLPF_NA]`` the action column of every building's electrical / cooling / heating / DHW storage (-1: none), as the kernel reads them."""
-    return np.ascontiguousarray(tab.params).view(np.int32)[:, list(_HEAD_SLOTS)].astype(np.int64)
-
-
-class StoragePolicyTables:
-    """`StorageMLPPolicy.pack`'s result: the tables of `clpf_mlp` as float32 tensors on one device (the layouts of the header)."""
-
-    def __init__(self, pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, cols, low_bldg, high_bldg, sigma_bldg, n_device_cols, version):
-        self.pre, self.dep, self.out, self.net_reset = pre, dep, out, net_reset
-        self.act_low, self.act_high, self.sigma, self.set_of_block = act_low, act_high, sigma, set_of_block
-        # host side, int64 / float64 [n_bldg, CLPF_NA]: every head's action column (-1: none), that column's bounds and sigma -- what
-        # `StorageMLPPolicy.actions_host(..., tables=this)` evaluates the reference with
-        self.cols, self.low_bldg, self.high_bldg, self.sigma_bldg = cols, low_bldg, high_bldg, sigma_bldg
-        self.n_device_cols = int(n_device_cols)
-        self.version = version
-        self.n_sets, self.n_rows, self.n_bldg, self.n_hidden = (int(x) for x in pre.shape)
-
-    def struct(self, seed: int) -> _lib.PolicyFullMLP:
-        p = lambda t: None if t is None else t.data_ptr()
-        return _lib.PolicyFullMLP(self.n_hidden, self.n_sets, self.n_device_cols, 0, p(self.pre), p(self.dep), p(self.out), p(self.set_of_block),
-                                  p(self.net_reset), p(self.act_low), p(self.act_high), p(self.sigma), int(seed) & (2 ** 64 - 1))
-
-
-class StorageMLPPolicy:
-    """``act_a = clamp(mid_a + half_a tanh(w2[a] . tanh(W1 obs + b1) + b2[a]) + sigma_a z_a, low_a, high_a)`` per building and head a, the heads in
-    the fixed order electrical, cooling, heating, DHW storage (`HEAD_NAMES`); `obs` = the building's own observation vector as the env defines
-    it, (low_a, high_a) = the bounds of the building's action column of that storage.  The heads of columns a building lacks are ignored.  For
-    thermal districts without the LSTM stage and without device actions (the 2020 / 2021 schemas): `cl_rollout_full_policy_kernel`.
-
-    ``w1 [n_sets, n_bldg, H, n_obs]``, ``b1 [n_sets, n_bldg, H]``, ``w2 [n_sets, n_bldg, 4, H]``, ``b2 [n_sets, n_bldg, 4]`` (kept in float64); a
-    leading dimension of 1 broadcasts.  ``H``: 4, 8, .. 32.  ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
-
-    The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
-
-    def __init__(self, w1, b1, w2, b2, sigma=None):
-        self.w1, self.b1, self.w2, self.b2 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2))
-        if self.w1.ndim != 4 or self.b1.ndim != 3 or self.w2.ndim != 4 or self.b2.ndim != 3:
-            raise ValueError(f'w1 [n_sets, n_bldg, H, n_obs], b1 [n_sets, n_bldg, H], w2 [n_sets, n_bldg, {CLPF_NA}, H], b2 [n_sets, n_bldg, {CLPF_NA}]')
-        self.n_hidden, self.n_obs = int(self.w1.shape[2]), int(self.w1.shape[3])
-        if self.n_hidden % 4 or not 4 <= self.n_hidden <= CLPF_MAX_HIDDEN:
-            raise ValueError(f'H={self.n_hidden}: the policy kernel takes 4, 8, .. {CLPF_MAX_HIDDEN} hidden units')
-        if self.b1.shape[2] != self.n_hidden or self.w2.shape[3] != self.n_hidden or self.w2.shape[2] != CLPF_NA or self.b2.shape[2] != CLPF_NA:
-            raise ValueError(f'b1 / w2 / b2 disagree with w1 about H, or do not have {CLPF_NA} heads')
-        self.n_sets = max(x.shape[0] for x in (self.w1, self.b1, self.w2, self.b2))
-        self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
-        self.version = 0
-
-    invalidate = MLPPolicy.invalidate
-    update = MLPPolicy.update
-
-    def _full(self, n_bldg: int):
-        S, H = self.n_sets, self.n_hidden
-        try:
-            return (np.broadcast_to(self.w1, (S, n_bldg, H, self.n_obs)), np.broadcast_to(self.b1, (S, n_bldg, H)),
-                    np.broadcast_to(self.w2, (S, n_bldg, CLPF_NA, H)), np.broadcast_to(self.b2, (S, n_bldg, CLPF_NA)))
-        except ValueError as e:
-            raise ValueError(f'the weights do not broadcast to {S} sets x {n_bldg} buildings: {e}') from None
-
-    # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
-    def actions_host(self, obs_vectors, tables: StoragePolicyTables, noise=None, set_index: int = 0) -> np.ndarray:
-        """float64 numpy evaluation of the plain MLP: ``obs_vectors [..., n_bldg, n_obs]`` -> actions ``[..., n_bldg, 4]`` (0 for a head whose
-        column the building lacks).  ``noise``: the standard normals z (same shape as the result; `noise_host` replays the kernel's), scaled by
-        each head's sigma.  The heads' columns, bounds and sigmas come from ``tables`` (a `pack` result).  Nothing is remembered between calls."""
-        x = np.asarray(obs_vectors, dtype=np.float64)
-        w1, b1, w2, b2 = (v[set_index] for v in self._full(x.shape[-2]))
-        lo, hi = tables.low_bldg, tables.high_bldg
-        h = np.tanh(np.einsum('bjc,...bc->...bj', w1, x) + b1)
-        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('baj,...bj->...ba', w2, h) + b2)
-        if noise is not None:
-            a = a + tables.sigma_bldg * np.asarray(noise, dtype=np.float64)
-        return np.where(tables.cols >= 0, np.clip(a, lo, hi), 0.0)
-
-    def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
-        """The same MLP (no noise) written in torch over the env's observation TENSOR: returns ``f(obs [n_envs, n_obs_total], i=None) ->
-        actions [n_act_cols, n_envs]`` -- a `VectorCityLearnEnv.capture_rollout` policy; what `rollout_policy` replaces with one launch."""
-        cols = building_columns(layout)
-        n_bldg = len(cols)
-        w1, b1, w2, b2 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(n_bldg))
-        idx = torch.as_tensor(np.array([c + [c[0]] * (self.n_obs - len(c)) for c in cols]), device=device)
-        mask = torch.as_tensor(np.array([[1.0] * len(c) + [0.0] * (self.n_obs - len(c)) for c in cols]), dtype=dtype, device=device)
-        hc = head_columns(tab)
-        low, high = layout.spec.action_limits()
-        bsel, asel = np.nonzero(hc >= 0)
-        rows = torch.as_tensor(hc[bsel, asel], device=device)
-        lo = torch.as_tensor(np.asarray(low)[hc[bsel, asel]], dtype=dtype, device=device)
-        hi = torch.as_tensor(np.asarray(high)[hc[bsel, asel]], dtype=dtype, device=device)
-        flat = torch.as_tensor(bsel * CLPF_NA + asel, device=device)
-        n_act = len(low)
-
-        def f(obs, i=None):
-            x = obs.to(dtype)[:, idx] * mask                                     # [E, B, n_obs]
-            h = torch.tanh(torch.einsum('bjc,ebc->ebj', w1, x) + b1)
-            o = torch.tanh(torch.einsum('baj,ebj->eba', w2, h) + b2).reshape(obs.shape[0], -1)[:, flat]      # [E, present heads]
-            a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
-            out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
-            out[rows] = a.t().to(torch.float32)
-            return out
-        return f
-
-    # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
-    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None) -> StoragePolicyTables:
-        """Split the first layer along the observation tables of `layout` over the episode tables `tab`, as `MLPPolicy.pack` does, with FIVE
-        env-dependent inputs: the building's own ``electrical_storage_soc`` / ``cooling_storage_soc`` / ``heating_storage_soc`` /
-        ``dhw_storage_soc`` and ``net_electricity_consumption`` go into ``dep`` (rows `CLPF_D_*`; the row of a storage the building lacks stays
-        0), everything else into ``pre``.  A building observation fed by anything else on the device -- the indoor temperature of the LSTM stage
-        (``SRC_TEMP``), a detail plane, another building's plane -- and a building with a cooling / heating device ACTION raise ``ValueError``
-        naming the column."""
-        obs = layout.episode(tab, reset_table=True)
-        cols = building_columns(layout)
-        n_bldg, T = len(cols), int(obs.table.shape[0])
-        if any(len(c) > self.n_obs for c in cols) or not any(len(c) == self.n_obs for c in cols):
-            raise ValueError(f'w1 takes {self.n_obs} observations, the buildings have {sorted(set(len(c) for c in cols))}')
-        w1, b1, w2, b2 = self._full(n_bldg)
-        S, H = self.n_sets, self.n_hidden
-        params_i = np.ascontiguousarray(tab.params).view(np.int32)
-        bflags = np.ascontiguousarray(tab.params).view(np.uint32)[:, abi.CLP_FLAGS]
-        table = obs.table
-        x = np.zeros((T, n_bldg, self.n_obs))
-        scale = np.zeros((n_bldg, CLPF_ND, self.n_obs))                  # [b][term][position in the building's vector]
-        net_reset = np.zeros((T, n_bldg))
-        for i, bcols in enumerate(cols):
-            for j, c in enumerate(bcols):
-                name = f'{layout.columns[c][1]!r} of building {i} (column {c})'
-                src = int(obs.col_src[c])
-                if src < 0:
-                    if T > 1 and not np.array_equal(obs.reset_table[1:, c], table[1:, c]):
-                        raise ValueError(f'observation {name} is reset to a value its table row does not hold (observation_mode="reference"?): '
-                                         'the policy kernel reads the tables of observation_mode="current"')
-                    x[:, i, j] = table[:, c]
-                    continue
-                kind, plane, b = src >> 28, (src >> 20) & 0xFF, src & 0xFFFFF
-                which = _TERMS.get((kind, plane))
-                if which is None or b != i or layout.columns[c][0] != i:
-                    raise ValueError(f'observation {name} is fed by device plane (kind {kind}, plane {plane}, building {b}): the thermal policy kernel '
-                                     "only has the building's own storage socs (CLS_B_SOC, CLS_CS_SOC, CLS_HS_SOC, CLS_DS_SOC) and "
-                                     'net_electricity_consumption (CLO_NET)' + (' -- the indoor temperature comes from the LSTM stage' if kind == SRC_TEMP else ''))
-                offset = table[1:, c] if T > 1 else np.zeros(1)
-                if np.ptp(offset) != 0.0:
-                    raise ValueError(f'observation {name}: a table offset that changes with the row')
-                x[:, i, j] = offset[0]
-                flag = _TERM_FLAGS[which]
+                flag = kind.terms[which][1]
                 if flag is None or int(bflags[i]) & flag:                # (a storage the building lacks: its plane stays 0, the kernel skips the term)
                     scale[i, which, j] = float(obs.col_scale[c])
-                if which == CLPF_D_NET and scale[i, which, j] != 0.0:
+                if kind.terms[which][0] == (SRC_OUT, abi.CLO_NET) and scale[i, which, j] != 0.0:
                     net_reset[:, i] = (obs.reset_table[:, c] - offset[0]) / scale[i, which, j]
-        for i in range(n_bldg):
-            for dname, slot in _DEVICE_SLOTS:
-                if params_i[i, slot] >= 0:
-                    raise ValueError(f'action {dname!r} of building {i} (column {int(params_i[i, slot])}): the thermal policy kernel has storage heads '
-                                     f'only {HEAD_NAMES}; a district with device actions runs through capture_rollout')
+        if kind.refuse_device_actions:
+            for i in range(n_bldg):
+                for dname, slot in _DEVICE_SLOTS:
+                    if params_i[i, slot] >= 0:
+                        raise ValueError(f'action {dname!r} of building {i} (column {int(params_i[i, slot])}): the thermal policy kernel has storage heads '
+                                         f'only {HEAD_NAMES}; a district with device actions runs through capture_rollout')
         dev = torch.device(device)
         f64 = lambda v: torch.from_numpy(np.array(v, dtype=np.float64)).to(dev)
         pre = (torch.einsum('sbjc,tbc->stbj', f64(w1), f64(x)) + f64(b1)[:, None]) * ACT_SCALE
         dep = torch.einsum('sbjc,bkc->sbkj', f64(w1), f64(scale)) * ACT_SCALE
-        out = torch.cat([f64(w2), f64(b2)[:, :, :, None]], dim=3)
-        hc = head_columns(tab)
+        out = torch.cat([f64(w2), f64(b2)[..., None]], dim=-1)
+        hc = _head_columns(tab, kind)
         n_act = int(params_i[:, abi.CLP_ACT_COOL_STO:abi.CLP_ACT_COH_DEV + 1].max()) + 1
         low, high = layout.spec.action_limits()
         if len(low) != n_act:
@@ -482,9 +356,68 @@ class StorageMLPPolicy:
         sob = None
         if set_of_block is not None:
             sob = np.asarray(set_of_block, dtype=np.int64).reshape(-1)
-            if sob.min() < 0 or sob.max() >= S:
-                raise ValueError(f'set_of_block outside [0, {S})')
+            if sob.min() < 0 or sob.max() >= self.n_sets:
+                raise ValueError(f'set_of_block outside [0, {self.n_sets})')
             sob = torch.from_numpy(sob.astype(np.int32)).to(dev)
-        return StoragePolicyTables(pre.to(torch.float32).contiguous(), dep.to(torch.float32).contiguous(), out.to(torch.float32).contiguous(),
-                                   f32(net_reset), f32(low), f32(high), f32(sigma), sob, hc, at(low, -1.0), at(high, 1.0),
-                                   np.zeros(hc.shape) if sigma is None else at(sigma, 0.0), 0, self.version)      # (n_device_cols = 0: refused above)
+        host = (hc, at(low, -1.0), at(high, 1.0), np.zeros(hc.shape) if sigma is None else at(sigma, 0.0))
+        if kind.refuse_device_actions:
+            host += (0,)                                                 # (n_device_cols = 0: refused above)
+        return kind.tables(pre.to(torch.float32).contiguous(), dep.to(torch.float32).contiguous(), out.to(torch.float32).contiguous(),
+                           f32(net_reset), f32(low), f32(high), f32(sigma), sob, *host, self.version)
+
+
+class MLPPolicy(_MLPBase):
+    """``a = clamp(mid + half tanh(w2 . tanh(W1 obs + b1) + b2) + sigma z, low, high)`` per building, `obs` = the building's own observation
+    vector as the env defines it (``ObservationLayout.building_names[i]``: normalised or not, whatever the env was built with), (low, high) =
+    the bounds of the building's electrical-storage action, z ~ N(0, 1).  The env-dependent inputs are the building's own
+    ``electrical_storage_soc`` and ``net_electricity_consumption``.
+
+    ``w1 [n_sets, n_bldg, H, n_obs]``, ``b1 [n_sets, n_bldg, H]``, ``w2 [n_sets, n_bldg, H]``, ``b2 [n_sets, n_bldg]`` (anything array-like;
+    kept in float64); a leading dimension of 1 broadcasts -- shared weights over the buildings and / or one parameter set.  ``H``: 4, 8, .. 32.
+    ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
+
+    **The packed tables are a snapshot.**  `pack` reads the weights once; `VectorCityLearnEnv.rollout_policy` caches the packed tables per
+    (policy object, `version`, episode window).  Change the weights through :meth:`update` (or assign the arrays and call :meth:`invalidate`):
+    both bump `version`, so the next `rollout_policy` packs again.  Arrays edited in place without that keep driving the OLD policy."""
+    kind = _LEAN
+    _heads = staticmethod(lambda w2, h: np.einsum('bj,...bj->...b', w2, h))
+    _heads_torch = staticmethod(lambda w2, h: (w2 * h).sum(dim=-1))
+
+    def actions_host(self, obs_vectors, noise=None, tables: Optional[PolicyTables] = None, low=None, high=None, sigma_bldg=None,
+                     set_index: int = 0) -> np.ndarray:
+        """float64 numpy evaluation of the plain MLP: ``obs_vectors [..., n_bldg, n_obs]`` -> actions ``[..., n_bldg]``.  ``noise``: the
+        standard normals z (same shape as the result; `noise_host` replays the kernel's), scaled by each building's sigma.  The bounds of the
+        buildings' storage actions and their sigmas (``[n_bldg]`` each) come from ``tables`` (a `pack` result: `low_bldg`, `high_bldg`,
+        `sigma_bldg`) or from the arguments; without either: -1 / 1 and the policy's scalar sigma.  Nothing is remembered between calls."""
+        pick = lambda arg, attr, default: np.asarray(arg if arg is not None else getattr(tables, attr) if tables is not None else default, dtype=np.float64)
+
+        def sigma():
+            if sigma_bldg is None and tables is None and self.sigma is not None and self.sigma.ndim:
+                raise ValueError('a per-column sigma needs `tables` (or `sigma_bldg`): which column drives which building')
+            return pick(sigma_bldg, 'sigma_bldg', 0.0 if self.sigma is None or self.sigma.ndim else float(self.sigma))
+        return self._actions_host(obs_vectors, pick(low, 'low_bldg', -1.0), pick(high, 'high_bldg', 1.0), noise, sigma, set_index)
+
+
+class StorageMLPPolicy(_MLPBase):
+    """``act_a = clamp(mid_a + half_a tanh(w2[a] . tanh(W1 obs + b1) + b2[a]) + sigma_a z_a, low_a, high_a)`` per building and head a, the heads in
+    the fixed order electrical, cooling, heating, DHW storage (`HEAD_NAMES`); `obs` = the building's own observation vector as the env defines
+    it, (low_a, high_a) = the bounds of the building's action column of that storage.  The heads of columns a building lacks are ignored.  For
+    thermal districts without the LSTM stage and without device actions (the 2020 / 2021 schemas): `cl_rollout_full_policy_kernel`.  FIVE
+    env-dependent inputs: the building's own ``electrical_storage_soc`` / ``cooling_storage_soc`` / ``heating_storage_soc`` /
+    ``dhw_storage_soc`` and ``net_electricity_consumption`` (``dep`` rows `CLPF_D_*`).  `pack` also refuses the indoor temperature of the LSTM
+    stage (``SRC_TEMP``) and a building with a cooling / heating device ACTION.
+
+    ``w1 [n_sets, n_bldg, H, n_obs]``, ``b1 [n_sets, n_bldg, H]``, ``w2 [n_sets, n_bldg, 4, H]``, ``b2 [n_sets, n_bldg, 4]`` (kept in float64); a
+    leading dimension of 1 broadcasts.  ``H``: 4, 8, .. 32.  ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
+
+    The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
+    kind = _THERMAL
+    _heads = staticmethod(lambda w2, h: np.einsum('baj,...bj->...ba', w2, h))
+    _heads_torch = staticmethod(lambda w2, h: torch.einsum('baj,...bj->...ba', w2, h))
+
+    def actions_host(self, obs_vectors, tables: StoragePolicyTables, noise=None, set_index: int = 0) -> np.ndarray:
+        """float64 numpy evaluation of the plain MLP: ``obs_vectors [..., n_bldg, n_obs]`` -> actions ``[..., n_bldg, 4]`` (0 for a head whose
+        column the building lacks).  ``noise``: the standard normals z (same shape as the result; `noise_host` replays the kernel's), scaled by
+        each head's sigma.  The heads' columns, bounds and sigmas come from ``tables`` (a `pack` result).  Nothing is remembered between calls."""
+        a = self._actions_host(obs_vectors, tables.low_bldg, tables.high_bldg, noise, lambda: tables.sigma_bldg, set_index)
+        return np.where(tables.cols >= 0, a, 0.0)

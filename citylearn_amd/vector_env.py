@@ -431,9 +431,7 @@ class VectorCityLearnEnv:
         (`CLPF_T_ACTION` + head, `_REWARD`, `_NET`, `CLPF_T_SOC` + storage).  ``kpi=True`` on an env built with ``kpi=True`` keeps the streaming KPI
         accumulators in the same single launch (`cl_rollout_full_policy_kpi_kernel`), so `evaluate()` works afterwards without a record or a
         second env; on an env built without KPIs it raises `NotImplementedError`."""
-        from . import policy as _policy
-        storage = isinstance(policy, _policy.StorageMLPPolicy)
-        if storage and kpi and not self.kpi:
+        if kpi and not self.kpi and policy.kind.no_kpi_error is NotImplementedError:
             raise NotImplementedError('rollout_policy(kpi=True) with a StorageMLPPolicy: this env was built without the streaming KPI accumulators -- '
                                       'build it with VectorCityLearnEnv(..., kpi=True)')
         if kpi and not self.kpi:
@@ -458,7 +456,7 @@ class VectorCityLearnEnv:
             cache.clear()                                     # (one live entry: tables of another window or engine are stale)
             cache[key] = (policy, policy.pack(layout, self.tables, device=self.device, set_of_block=sob))
         ret = torch.zeros(self.n_envs, dtype=torch.float32, device=self.device)
-        traj = torch.empty((k_steps, _policy.CLPF_NT if storage else _policy.CLPOL_NT, e.n_bldg, self.n_envs), dtype=torch.float32, device=self.device) if record else None
+        traj = torch.empty((k_steps, policy.kind.n_planes, e.n_bldg, self.n_envs), dtype=torch.float32, device=self.device) if record else None
         e.rollout_policy(k_steps, cache[key][1], seed=seed, ret_env=ret, traj=traj, t0=self._t, kpi=kpi)
         self._t += k_steps
         return (ret, traj) if record else ret

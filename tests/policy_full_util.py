@@ -1,17 +1,17 @@
 """Shared by tests/test_policy_full_host.py and tests/test_gpu_policy_full_rollout.py: the test policies of thermal districts (ONE weight scale,
-fixed by the CPU conditioning test), the observation vectors of a batch rebuilt on the host from `ObservationTables` with FIVE env-dependent
-planes, and the closed loop on the CPU oracle with the four heads scattered into the action columns."""
+fixed by the CPU conditioning test), the FIVE env-dependent planes of the observation vectors rebuilt on the host (`policy_util.HostObservations`),
+the thermal districts, and the closed loop on the CPU oracle with the four heads scattered into the action columns."""
 import copy
 from dataclasses import replace
 from functools import lru_cache
 
 import numpy as np
-import torch
 
 from golden_util import golden
 from citylearn_amd import abi
 from citylearn_amd.observations import SRC_OUT, SRC_STATE, ObservationLayout
-from citylearn_amd.policy import CLPF_NA, StorageMLPPolicy, building_columns, noise_host
+from citylearn_amd.policy import CLPF_NA, StorageMLPPolicy, noise_host
+from policy_util import HostObservations
 
 # The weight scale of every test policy: first-layer rows uniform in +-W1_SCALE / sqrt(n_obs), output rows uniform in +-W2_SCALE / sqrt(H), output
 # biases in +-0.4 W2_SCALE (policy_util's 0.2 at its scale).  Chosen on the CPU, before any GPU run, by
@@ -26,8 +26,8 @@ from citylearn_amd.policy import CLPF_NA, StorageMLPPolicy, building_columns, no
 # action still goes through the unit's clipping, and the kernel has to agree that the plane stays 0).  Actions span about +-0.09 of the bounds.
 W1_SCALE, W2_SCALE = 0.25, 0.125
 
-# the planes of the state / output arrays the five terms read, in CLPF_D_* order
-_PLANES = ((SRC_STATE, abi.CLS_B_SOC), (SRC_STATE, abi.CLS_CS_SOC), (SRC_STATE, abi.CLS_HS_SOC), (SRC_STATE, abi.CLS_DS_SOC), (SRC_OUT, abi.CLO_NET))
+# the planes of the state / output arrays the five terms read, in CLPF_D_* order: soc, cs, hs, ds, previous net
+THERMAL_PLANES = ((SRC_STATE, abi.CLS_B_SOC), (SRC_STATE, abi.CLS_CS_SOC), (SRC_STATE, abi.CLS_HS_SOC), (SRC_STATE, abi.CLS_DS_SOC), (SRC_OUT, abi.CLO_NET))
 
 
 def make_storage_policy(layout: ObservationLayout, H: int, n_sets: int = 1, seed: int = 0, sigma=None, shared: bool = False) -> StorageMLPPolicy:
@@ -102,36 +102,6 @@ def outage_mask(tab, K: int):
     return tab.outage[:K] > 0
 
 
-class HostObservations5:
-    """Observation vectors [E, n_bldg, n_obs] of a batch at table row r from the five planes `x5` [5, n_bldg, E] (soc, cs, hs, ds, previous
-    net; float64): the arithmetic of `ObservationTables.host_row`, vectorised; a shorter building vector is zero-padded at the end."""
-
-    def __init__(self, layout: ObservationLayout, tab):
-        self.obs = layout.episode(tab, reset_table=True)
-        self.cols = building_columns(layout)
-        self.n_obs = max(len(c) for c in self.cols)
-        self.lengths = np.array([len(c) for c in self.cols])
-        self.idx = np.array([c + [c[0]] * (self.n_obs - len(c)) for c in self.cols])
-        self.mask = np.arange(self.n_obs)[None, :] < self.lengths[:, None]
-        src = self.obs.col_src[self.idx]
-        kind, plane = src >> 28, (src >> 20) & 0xFF
-        self.is_term = [self.mask & (src >= 0) & (kind == k) & (plane == p) for k, p in _PLANES]
-        assert np.array_equal(self.mask & (src >= 0), np.logical_or.reduce(self.is_term))
-        assert np.array_equal((src & 0xFFFFF)[self.mask & (src >= 0)], np.broadcast_to(np.arange(len(self.cols))[:, None], src.shape)[self.mask & (src >= 0)])
-        self.scale = self.obs.col_scale[self.idx].astype(np.float64)
-
-    def at(self, r: int, x5, reset: bool = False, E: int = None):
-        """`reset`: the observation `reset()` returns for an episode that starts at row r (x5 not read; pass E)."""
-        if reset:
-            row = (self.obs.reset_table[r] if r else self.obs.table[0])[self.idx] * self.mask
-            return np.broadcast_to(row[None], (E,) + self.idx.shape).copy()
-        E = np.shape(x5)[2]
-        x = np.broadcast_to((self.obs.table[r][self.idx] * self.mask)[None], (E,) + self.idx.shape).copy()
-        for d, is_d in enumerate(self.is_term):
-            x += np.where(is_d, np.asarray(x5[d], dtype=np.float64).T[:, :, None] * self.scale, 0.0)
-        return x
-
-
 def replay_noise(pt, seed, E, t, env_offset=0):
     """[E, n_bldg, 4] the kernel's standard normals of step t (0 where the head has no column or sigma 0)."""
     B = pt.cols.shape[0]
@@ -157,7 +127,7 @@ def host_closed_loop(spec, tab, layout, policy, pt, K, E, reward='RewardFunction
     ('action': [K, 4, n_bldg, E]; 'dnet': [K, E])."""
     from oracle.c_oracle import COracle, OS, OO
     ora = COracle(spec, tab, E, reward=reward)
-    hobs = HostObservations5(layout, tab)
+    hobs = HostObservations(layout, tab, THERMAL_PLANES)
     B = len(spec.buildings)
     out = {k: np.zeros((K, B, E)) for k in ('soc', 'cs', 'hs', 'ds', 'degcap', 'net', 'reward')}
     out['action'] = np.zeros((K, CLPF_NA, B, E))
@@ -168,7 +138,7 @@ def host_closed_loop(spec, tab, layout, policy, pt, K, E, reward='RewardFunction
         if t == 0:
             x = hobs.at(0, None, reset=True, E=E)
         else:
-            x = hobs.at(t, np.stack([ora.state[:, :, OS[k]].T for k in ('SOC', 'CS', 'HS', 'DS')] + [ora.out[:, :, OO['NET']].T]))
+            x = hobs.at(t, *[ora.state[:, :, OS[k]].T for k in ('SOC', 'CS', 'HS', 'DS')], ora.out[:, :, OO['NET']].T)
         a = policy.actions_host(x, pt, noise=replay_noise(pt, seed, E, t, env_offset) if noisy else None)          # [E, B, 4]
         if round_f32:
             a = a.astype(np.float32).astype(np.float64)
@@ -182,18 +152,3 @@ def host_closed_loop(spec, tab, layout, policy, pt, K, E, reward='RewardFunction
         out['reward'][t] = o[:, :, OO['REWARD']].T
         out['dnet'][t] = oe[:, 0]
     return out
-
-
-def f32_torch_deviation(pol, x, pt, device='cpu', noise=None):
-    """max |float32 torch evaluation of the unsplit MLP - float64| over the heads that exist, on observation vectors x [..., B, n_obs]
-    (`noise`: the standard normals [..., B, 4], handed to both evaluations)."""
-    ref = pol.actions_host(x, pt, noise=noise)
-    t = lambda v: torch.as_tensor(np.array(v), dtype=torch.float32, device=device)
-    w1, b1, w2, b2 = (t(v[0]) for v in pol._full(x.shape[-2]))
-    h = torch.tanh(torch.einsum('bjc,...bc->...bj', w1, t(x)) + b1)
-    lo, hi = t(pt.low_bldg), t(pt.high_bldg)
-    a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * torch.tanh(torch.einsum('baj,...bj->...ba', w2, h) + b2)
-    if noise is not None:
-        a = a + t(pt.sigma_bldg) * t(noise)
-    a = torch.clamp(a, lo, hi).cpu().numpy().astype(np.float64)
-    return float(np.abs(np.where(pt.cols >= 0, a - ref, 0.0)).max())

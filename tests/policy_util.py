@@ -1,5 +1,6 @@
-"""Shared by tests/test_policy_host.py and tests/test_gpu_policy_rollout.py: the test policies (ONE weight scale, fixed by the CPU conditioning
-test), the observation vectors of a batch rebuilt on the host from `ObservationTables`, and the closed loop on the CPU oracle."""
+"""Shared by the policy tests: the lean test policies (ONE weight scale, fixed by the CPU conditioning test of tests/test_policy_host.py) and their
+closed loop on the CPU oracle; for both policies (tests/policy_full_util.py has the thermal rest) the observation vectors of a batch rebuilt
+on the host from `ObservationTables` and the float32 torch evaluation's deviation."""
 import numpy as np
 import torch
 
@@ -26,13 +27,18 @@ def make_policy(layout: ObservationLayout, H: int, n_sets: int = 1, seed: int = 
     return MLPPolicy(w1, b1, w2, b2, sigma=sigma)
 
 
+# the planes of the state / output arrays the lean policy's two terms read: soc, previous net
+LEAN_PLANES = ((SRC_STATE, abi.CLS_B_SOC), (SRC_OUT, abi.CLO_NET))
+
+
 class HostObservations:
-    """Observation vectors [E, n_bldg, n_obs] of a batch at table row r from soc / previous-net planes [n_bldg, E], float64: the arithmetic of
+    """Observation vectors [E, n_bldg, n_obs] of a batch at table row r from the env-dependent planes [n_bldg, E] each (float64), in the order
+    of `planes` ((source kind, plane) pairs; by default the lean policy's soc and previous net): the arithmetic of
     `ObservationTables.host_row` (row + plane * col_scale for the env-dependent columns; row 0 / the reset table as they are), vectorised.
     A building whose own vector is shorter than `n_obs` (the longest one) is padded at the end, and the padding is multiplied by zero -- what
-    `MLPPolicy.pack` feeds the first layer's trailing weights of such a building (its `x` / `scale` rows stay 0 there)."""
+    `pack` feeds the first layer's trailing weights of such a building (its `x` / `scale` rows stay 0 there)."""
 
-    def __init__(self, layout: ObservationLayout, tab):
+    def __init__(self, layout: ObservationLayout, tab, planes=LEAN_PLANES):
         self.obs = layout.episode(tab, reset_table=True)
         self.cols = building_columns(layout)
         self.n_obs = max(len(c) for c in self.cols)
@@ -41,20 +47,21 @@ class HostObservations:
         self.mask = np.arange(self.n_obs)[None, :] < self.lengths[:, None]                    # [B, n_obs]
         src = self.obs.col_src[self.idx]
         kind, plane = src >> 28, (src >> 20) & 0xFF
-        self.is_soc = self.mask & (src >= 0) & (kind == SRC_STATE) & (plane == abi.CLS_B_SOC)
-        self.is_net = self.mask & (src >= 0) & (kind == SRC_OUT) & (plane == abi.CLO_NET)
-        assert np.array_equal(self.mask & (src >= 0), self.is_soc | self.is_net)
+        self.is_term = [self.mask & (src >= 0) & (kind == k) & (plane == p) for k, p in planes]
+        assert np.array_equal(self.mask & (src >= 0), np.logical_or.reduce(self.is_term))
+        assert np.array_equal((src & 0xFFFFF)[self.mask & (src >= 0)], np.broadcast_to(np.arange(len(self.cols))[:, None], src.shape)[self.mask & (src >= 0)])
         self.scale = self.obs.col_scale[self.idx].astype(np.float64)
 
-    def at(self, r: int, soc, net, reset: bool = False):
-        """`reset`: the observation `reset()` returns for an episode that starts at row r (soc / net not read)."""
-        E = np.shape(soc)[1]
+    def at(self, r: int, *planes, reset: bool = False, E: int = None):
+        """`planes`: one array per term.  `reset`: the observation `reset()` returns for an episode that starts at row r (the planes are not
+        read; E from the first one unless given)."""
+        E = np.shape(planes[0])[1] if E is None else E
         if reset:
             row = (self.obs.reset_table[r] if r else self.obs.table[0])[self.idx] * self.mask
             return np.broadcast_to(row[None], (E,) + self.idx.shape).copy()
         x = np.broadcast_to((self.obs.table[r][self.idx] * self.mask)[None], (E,) + self.idx.shape).copy()
-        soc, net = np.asarray(soc, dtype=np.float64).T[:, :, None], np.asarray(net, dtype=np.float64).T[:, :, None]
-        x += np.where(self.is_soc, soc * self.scale, 0.0) + np.where(self.is_net, net * self.scale, 0.0)
+        for is_d, v in zip(self.is_term, planes, strict=True):
+            x += np.where(is_d, np.asarray(v, dtype=np.float64).T[:, :, None] * self.scale, 0.0)
         return x
 
 
@@ -99,18 +106,19 @@ def host_closed_loop(spec, tab, layout, policy, pt, K, E, reward='RewardFunction
 
 
 def f32_torch_deviation(pol, x, pt, device='cpu', noise=None):
-    """max |float32 torch evaluation of the unsplit MLP - float64| on observation vectors x [..., B, n_obs] (`noise`: the standard normals
-    [..., B], handed to both evaluations; `pt`: the policy's `pack`, for the bounds and sigmas)."""
+    """max |float32 torch evaluation of the unsplit MLP - float64| on observation vectors x [..., B, n_obs], for either policy; with a head
+    axis, over the heads that exist (`noise`: the standard normals, shaped like the actions, handed to both evaluations; `pt`: the policy's
+    `pack`, for the bounds, sigmas and columns)."""
     ref = pol.actions_host(x, tables=pt, noise=noise)
     t = lambda v: torch.as_tensor(np.array(v), dtype=torch.float32, device=device)
     w1, b1, w2, b2 = (t(v[0]) for v in pol._full(x.shape[-2]))
     h = torch.tanh(torch.einsum('bjc,...bc->...bj', w1, t(x)) + b1)
     lo, hi = t(pt.low_bldg), t(pt.high_bldg)
-    a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * torch.tanh((w2 * h).sum(dim=-1) + b2)
+    a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * torch.tanh(pol._heads_torch(w2, h) + b2)
     if noise is not None:
         a = a + t(pt.sigma_bldg) * t(noise)
-    a = torch.clamp(a, lo, hi)
-    return float(np.abs(a.cpu().numpy().astype(np.float64) - ref).max())
+    d = np.abs(torch.clamp(a, lo, hi).cpu().numpy().astype(np.float64) - ref)
+    return float((np.where(pt.cols >= 0, d, 0.0) if pol.kind.head_shape else d).max())
 
 
 def exports(path):

@@ -15,7 +15,8 @@ from golden_util import check_worst, golden, record_worst
 from citylearn_amd import _lib, policy
 from citylearn_amd.engine import StepEngine
 from citylearn_amd.observations import ObservationLayout
-from policy_full_util import (HostObservations5, f32_torch_deviation, host_closed_loop, make_storage_policy, outage_mask, replay_noise, thermal_district)
+from policy_full_util import THERMAL_PLANES, host_closed_loop, make_storage_policy, outage_mask, replay_noise, thermal_district
+from policy_util import HostObservations, f32_torch_deviation
 
 pytestmark = pytest.mark.gpu
 
@@ -55,9 +56,9 @@ def _roll(eng, pt, K, seed=0):
 def _teacher_forced(tab, layout, pol, pt, traj, seed=0, row0=0, env_offset=0):
     """(kernel's worst |action - float64 MLP| over the heads that exist, a float32 torch evaluation's, on the recorded inputs of every step)."""
     K, E = traj.shape[0], traj.shape[3]
-    hobs = HostObservations5(layout, tab)
+    hobs = HostObservations(layout, tab, THERMAL_PLANES)
     tr = traj.cpu().numpy().astype(np.float64)
-    xs = [hobs.at(row0, None, reset=True, E=E)] + [hobs.at(row0 + k, np.concatenate([tr[k - 1, S:S + 4], tr[k - 1, N:N + 1]])) for k in range(1, K)]
+    xs = [hobs.at(row0, None, reset=True, E=E)] + [hobs.at(row0 + k, *tr[k - 1, S:S + 4], tr[k - 1, N]) for k in range(1, K)]
     x = np.stack(xs)
     z = None
     if np.any(pt.sigma_bldg > 0):
@@ -336,7 +337,7 @@ def test_g_env_level_equals_capture_rollout_with_the_torch_mlp(normalize):
     _, rewards, _ = cap.run()
     torch.cuda.synchronize()
     dev_kernel, dev_f32 = _teacher_forced(a.tables, a.layout, pol, pt_host, traj)
-    hobs = HostObservations5(a.layout, a.tables)
+    hobs = HostObservations(a.layout, a.tables, THERMAL_PLANES)
     w1, w2 = pol._full(a.n_bldg)[0][0], pol._full(a.n_bldg)[2][0]                  # [B, H, n_obs], [B, 4, H]
     tr = traj.cpu().numpy().astype(np.float64)
     tols = [2e-6 * (1 + np.abs(tr[:, S + d]).max()) for d in range(4)] + [2e-5 * (1 + np.abs(tr[:, N]).max())]

@@ -205,8 +205,8 @@ def test_g_env_level_equals_capture_rollout_with_the_torch_mlp(normalize):
     w1, w2 = pol._full(a.n_bldg)[0][0], pol._full(a.n_bldg)[2][0]                  # [B, H, n_obs], [B, H]
     tr = traj.cpu().numpy().astype(np.float64)
     tol_soc, tol_net = 2e-6 * (1 + np.abs(tr[:, S]).max()), 2e-5 * (1 + np.abs(tr[:, N]).max())
-    g_soc = np.abs(w1 * np.where(hobs.is_soc, hobs.scale, 0.0)[:, None, :]).sum(axis=2)      # [B, H]
-    g_net = np.abs(w1 * np.where(hobs.is_net, hobs.scale, 0.0)[:, None, :]).sum(axis=2)
+    g_soc = np.abs(w1 * np.where(hobs.is_term[0], hobs.scale, 0.0)[:, None, :]).sum(axis=2)      # [B, H]
+    g_net = np.abs(w1 * np.where(hobs.is_term[1], hobs.scale, 0.0)[:, None, :]).sum(axis=2)
     half = 0.5 * (pt_host.high_bldg - pt_host.low_bldg)
     widen = float((half * (np.abs(w2) * (g_soc * tol_soc + g_net * tol_net)).sum(axis=1)).max())
     tol = 4.0 * dev_f32 + dev_f32 + widen

@@ -12,9 +12,9 @@ import torch
 from golden_util import golden
 from citylearn_amd import _lib, abi, policy
 from citylearn_amd.observations import ObservationLayout
-from policy_full_util import (OUTAGE_NAMES, HostObservations5, f32_torch_deviation, host_closed_loop, make_storage_policy, outage_district, outage_mask,
-                              outage_rows, thermal_district)
-from policy_util import exports
+from policy_full_util import (OUTAGE_NAMES, THERMAL_PLANES, host_closed_loop, make_storage_policy, outage_district, outage_mask, outage_rows,
+                              thermal_district)
+from policy_util import HostObservations, exports, f32_torch_deviation
 from test_isa_guards import _asm
 
 
@@ -259,8 +259,8 @@ def _conditioning(spec, H, K=48, E=4):
     pol = make_storage_policy(layout, H, seed=H)
     pt = pol.pack(layout, tab)
     ref = host_closed_loop(spec, tab, layout, pol, pt, K, E)
-    hobs = HostObservations5(layout, tab)
-    x = np.stack([hobs.at(t, np.stack([ref[k][t - 1] for k in ('soc', 'cs', 'hs', 'ds', 'net')])) for t in range(1, K)])
+    hobs = HostObservations(layout, tab, THERMAL_PLANES)
+    x = np.stack([hobs.at(t, *[ref[k][t - 1] for k in ('soc', 'cs', 'hs', 'ds', 'net')]) for t in range(1, K)])
     tol = 4.0 * f32_torch_deviation(pol, x, pt)
     got = host_closed_loop(spec, tab, layout, pol, pt, K, E, perturb=tol, round_f32=True)
     return {k: float((np.abs(got[k] - ref[k]) / (1e-4 + 1e-4 * np.abs(ref[k]))).max()) for k in ('soc', 'cs', 'ds', 'net')}, tol, ref, pt

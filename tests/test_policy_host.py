@@ -201,6 +201,53 @@ def test_split_first_layer_equals_the_unsplit_one(normalize):
     assert np.array_equal(pt.out.numpy()[:, :, :16], pol.w2.astype(np.float32)) and np.array_equal(pt.out.numpy()[:, :, 16], pol.b2.astype(np.float32))
 
 
+@pytest.mark.parametrize('name, normalize', [('g2022_all', True), ('g2022_all', False), ('het17', True)])
+def test_lean_policy_is_the_electrical_storage_slice_of_the_thermal_one(name, normalize):
+    """`MLPPolicy` is the one-head, two-term case of `StorageMLPPolicy`: with the lean weights in head `CLPF_A_ES` (the other heads random: the
+    district has no column for them) both packers give bit-identical `pre`, `net_reset`, bounds, `sigma` and `set_of_block`, the thermal `dep` rows
+    `CLPF_D_SOC` / `CLPF_D_NET` are the lean rows 0 / 1, the rows of the three tanks are zero, head `CLPF_A_ES` of `out` is the lean `out`, and
+    `actions_host` agrees to the last bit on a random batch with noise.
+
+    het17 has the two places where the kinds differ by design, asserted as they are: (1) the lean soc term carries no flag gate, so the
+    building WITHOUT a battery (`HET_NO_BATTERY`) keeps w1 . col_scale in its lean soc row (its soc plane stays 0, so the term adds nothing),
+    where the thermal packer, which gates the term by `CLF_BATTERY`, writes 0; the building that keeps its battery but has no action
+    (`HET_IDLE_ACTION`) has equal rows.  (2) for a building without an action column the lean `actions_host` returns the MLP's value (the
+    kernel records 0 and the tests mask it), the thermal one 0."""
+    from district_util import HET_NO_BATTERY, HET_UNDRIVEN, district
+    spec = golden(name).spec() if name == 'g2022_all' else district(name)
+    tab = spec.episode_tables(0)
+    layout = ObservationLayout(spec, 'current', normalize)
+    H, ES = 8, policy.CLPF_A_ES
+    lean = make_policy(layout, H, n_sets=2, seed=5, sigma=0.1)
+    rng = np.random.RandomState(9)
+    w2, b2 = rng.uniform(-1, 1, lean.w2.shape[:2] + (policy.CLPF_NA, H)), rng.uniform(-1, 1, lean.b2.shape + (policy.CLPF_NA,))
+    w2[:, :, ES], b2[:, :, ES] = lean.w2, lean.b2
+    thermal = policy.StorageMLPPolicy(lean.w1, lean.b1, w2, b2, sigma=0.1)
+    a, b = lean.pack(layout, tab, set_of_block=[1, 0]), thermal.pack(layout, tab, set_of_block=[1, 0])
+    for k in ('pre', 'net_reset', 'act_low', 'act_high', 'sigma', 'set_of_block'):
+        assert torch.equal(getattr(a, k), getattr(b, k)), k
+    B = a.n_bldg
+    gated = [HET_NO_BATTERY] if name == 'het17' else []
+    same = [i for i in range(B) if i not in gated]
+    assert a.dep.shape == (2, B, 2, H) and b.dep.shape == (2, B, policy.CLPF_ND, H)
+    assert torch.equal(a.dep[:, same, 0], b.dep[:, same, policy.CLPF_D_SOC]) and torch.equal(a.dep[:, :, 1], b.dep[:, :, policy.CLPF_D_NET])
+    assert a.dep[:, same].abs().min() > 0
+    if gated:
+        assert not b.dep[:, gated, policy.CLPF_D_SOC].any() and a.dep[:, gated, 0].abs().min() > 0
+    assert not b.dep[:, :, [policy.CLPF_D_CS, policy.CLPF_D_HS, policy.CLPF_D_DS]].any()
+    assert torch.equal(a.out, b.out[:, :, ES])
+    assert np.array_equal(b.cols[:, ES], a.es_cols) and np.all(np.delete(b.cols, ES, axis=1) == -1)
+    for k in ('low_bldg', 'high_bldg', 'sigma_bldg'):
+        assert np.array_equal(getattr(b, k)[:, ES], getattr(a, k)), k
+    driven = a.es_cols >= 0
+    assert sorted(np.nonzero(~driven)[0]) == (sorted(HET_UNDRIVEN) if name == 'het17' else [])
+    x, z = rng.uniform(-1, 1, (5, B, lean.n_obs)), rng.normal(size=(5, B, policy.CLPF_NA))
+    for s in (0, 1):
+        got, want = thermal.actions_host(x, b, noise=z, set_index=s), lean.actions_host(x, noise=z[..., ES], tables=a, set_index=s)
+        assert np.array_equal(got[:, driven, ES], want[:, driven]) and np.abs(want).min() > 0
+        assert not got[:, ~driven].any() and not np.delete(got, ES, axis=2).any()
+
+
 def test_packer_refuses_observations_it_cannot_feed():
     spec = golden('g2022_all').spec()
     tab = spec.episode_tables(0)

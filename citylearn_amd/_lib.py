@@ -199,6 +199,10 @@ POLICY_FULL = _Extension('policy_full', 'clpf', 'thermal policy', [], 'rollout_m
 # ... and the thermal one that also keeps the streaming KPIs (cl_policy_full_kpi.hip, with SLP vectorisation like cl_policy_full.hip)
 POLICY_FULL_KPI = _Extension('policy_full_kpi', 'clpfk', 'thermal policy KPI', [], 'rollout_mlp_kpi_f32', PolicyFullMLP, n_kpi=2, headers=[POLICY_FULL.header])
 EXTENSIONS = (POLICY, POLICY_KPI, POLICY_FULL, POLICY_FULL_KPI)
+# ... and the thermal one of districts of MORE than 16 buildings, a building-chunked launch (cl_policy_full_chunk.hip, with SLP vectorisation like
+# cl_policy_full.hip; `clpf_mlp` again).  ALL_EXTENSIONS is what `__graft_entry__.build()` builds and checks; EXTENSIONS stays the four one-row ones.
+POLICY_FULL_CHUNK = _Extension('policy_full_chunk', 'clpfc', 'chunked thermal policy', [], 'rollout_mlp_f32', PolicyFullMLP, headers=[POLICY_FULL.header])
+ALL_EXTENSIONS = EXTENSIONS + (POLICY_FULL_CHUNK,)
 
 # The names other code and the tests use: read-only views of the descriptions above (build / load / check read the description, so rebinding one
 # of these changes nothing -- change the description's attribute instead)
@@ -213,6 +217,9 @@ build_policy_full, load_policy_full, check_policy_full = POLICY_FULL.build, POLI
 POLICY_FULL_KPI_LIB_PATH, POLICY_FULL_KPI_HEADER, POLICY_FULL_KPI_SOURCES, POLICY_FULL_KPI_ABI_VERSION, POLICY_FULL_KPI_SYMBOLS = \
     POLICY_FULL_KPI.path, POLICY_FULL_KPI.header, POLICY_FULL_KPI.sources, POLICY_FULL_KPI.abi_version, POLICY_FULL_KPI.symbols
 build_policy_full_kpi, load_policy_full_kpi, check_policy_full_kpi = POLICY_FULL_KPI.build, POLICY_FULL_KPI.load, POLICY_FULL_KPI.check
+POLICY_FULL_CHUNK_LIB_PATH, POLICY_FULL_CHUNK_HEADER, POLICY_FULL_CHUNK_SOURCES, POLICY_FULL_CHUNK_ABI_VERSION, POLICY_FULL_CHUNK_SYMBOLS = \
+    POLICY_FULL_CHUNK.path, POLICY_FULL_CHUNK.header, POLICY_FULL_CHUNK.sources, POLICY_FULL_CHUNK.abi_version, POLICY_FULL_CHUNK.symbols
+build_policy_full_chunk, load_policy_full_chunk, check_policy_full_chunk = POLICY_FULL_CHUNK.build, POLICY_FULL_CHUNK.load, POLICY_FULL_CHUNK.check
 
 
 def policy_kpi_lds_bytes(nw: int, vec: int) -> int:
@@ -226,6 +233,13 @@ def policy_kpi_lds_bytes(nw: int, vec: int) -> int:
 def policy_full_lds_bytes(nw: int, vec: int) -> int:
     """Dynamic LDS of one `cl_rollout_full_policy_kernel` workgroup of ``nw`` waves at ``vec`` envs per lane: csrc/cl_policy_full.h's
     `rollout_full_policy_lds_floats` -- the district reduction's rows [nw][4][tile], then the staged policy rows [nw][(5 + 4) x 32 + 4 x 8]."""
+    return 4 * (nw * 4 * 64 * vec + nw * ((5 + 4) * 32 + 4 * 8))
+
+
+def policy_full_chunk_lds_bytes(nw: int, vec: int) -> int:
+    """Dynamic LDS of one `cl_rollout_full_policy_chunk_kernel` workgroup of ``nw`` waves (= buildings of a chunk) at ``vec`` envs per lane:
+    csrc/cl_policy_full_chunk.h's `rollout_full_policy_chunk_lds_floats`, which is `policy_full_lds_bytes`'s formula (the chunk's reduction rows
+    [nw][4][tile], then the staged policy rows) -- 26 624 bytes at the default eight waves and two envs per lane."""
     return 4 * (nw * 4 * 64 * vec + nw * ((5 + 4) * 32 + 4 * 8))
 
 

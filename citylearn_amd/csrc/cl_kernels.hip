@@ -1249,7 +1249,9 @@ __global__ void __launch_bounds__(256 / VEC) cl_step_envmajor_kernel(const StepA
 //  LDS copy, 148 VGPRs = three waves per SIMD.  17 x 1 048 576, alternating runs on one box (profiles/r05g_*): 114.9 / 129.1 / 129.2 us against
 //  115.9 / 120.4 / 125.8 us for this kernel -- the same range; each PROCESS lands somewhere in it and stays there for thousands of launches (not a
 //  function of the planes' virtual addresses: profiles/r05i_placement.log).  17 x 262 144: 30.9 vs 26.0 us.  Wider accesses are not what this shape lacks.)
-#if !defined(CL_TU_NOSLP) && !defined(CL_TU_POLICY_FULL)      /* (cl_noslp_tu.hip compiles only what its two kernels need; cl_policy_full.hip keeps cl_full.h without these passes) */
+/* (cl_noslp_tu.hip compiles only what its two kernels need; cl_policy_full.hip keeps cl_full.h without these passes; CL_TU_FINISH: cl_policy_full_chunk.hip
+   keeps the first of them, the fold of the chunk partial sums) */
+#if (!defined(CL_TU_NOSLP) && !defined(CL_TU_POLICY_FULL)) || defined(CL_TU_FINISH)
 // Second pass for building-chunked launches: add the per-chunk partial district sums.  One workgroup = 64 envs x ONE district
 // quantity x 16 waves; wave w adds chunks w, w+16, ... (independent loads issued four at a time: one memory round trip for up
 // to 64 chunks), then the 16 wave partials are summed in a fixed order through LDS -- deterministic.  (The first version let one
@@ -1312,7 +1314,9 @@ __global__ void __launch_bounds__(1024) cl_finish_kernel(const StepArgs a, const
         else ret_env[e] += t;
     }
 }
+#endif  // cl_finish_kernel
 
+#if !defined(CL_TU_NOSLP) && !defined(CL_TU_POLICY_FULL)
 // ---- streaming KPI accumulators (CLD_KPI): two small passes over the detail planes the step kernel just wrote ----
 __global__ void cl_kpi_bldg_kernel(const StepArgs a) {
     const long long plane = (long long)a.n_bldg * a.n_env;

@@ -491,7 +491,7 @@ class StepEngine:
         self.t = t0 + k_steps
 
     def rollout_policy(self, k_steps: int, policy_tables, seed: int = 0, ret_env: Optional[torch.Tensor] = None,
-                       traj: Optional[torch.Tensor] = None, t0: Optional[int] = None, kpi: bool = False):
+                       traj: Optional[torch.Tensor] = None, t0: Optional[int] = None, kpi: bool = False, chunked: bool = False):
         """Fused K-step rollout driven by a CLOSED-LOOP policy in one launch (`clpol_rollout_mlp_f32`, ``libcitylearn_amd_policy.so``): every
         building's storage action of every step is a one-hidden-layer tanh MLP of its observation, evaluated inside the kernel from the soc and
         the previous net in its registers (`policy.MLPPolicy`; ``policy_tables`` = its `pack(...)` on this engine's device and tables).
@@ -511,8 +511,23 @@ class StepEngine:
         ``traj`` ``[k_steps, CLPF_NT, n_bldg, n_env]``.  With ``kpi=True`` on an engine built with ``kpi=True`` the same steps are ONE launch of
         `cl_rollout_full_policy_kpi_kernel` (`clpfk_rollout_mlp_kpi_f32`, ``libcitylearn_amd_policy_full_kpi.so``), which keeps every env's
         twelve per-building sums and both district series and, under the float64 chain, leaves the last step's `CLD_DETAIL_MIN` planes in
-        ``out_bldg``; on an engine built without KPIs it raises `NotImplementedError`."""
+        ``out_bldg``; on an engine built without KPIs it raises `NotImplementedError`.
+
+        ``chunked=True`` (with `StoragePolicyTables`; `ValueError` for a kind without a chunked library) sends a thermal district of MORE than 16
+        buildings to the building-chunked launch: `cl_rollout_full_policy_chunk_kernel` (`clpfc_rollout_mlp_f32`,
+        ``libcitylearn_amd_policy_full_chunk.so``) with one building per wave and chunks of ``tuning=dict(b_chunk=...)`` buildings along the grid's
+        second axis -- default: balanced chunks of at most eight, 17 -> 6 + 6 + 5, 1024 -> 128 x 8 -- followed by one `cl_finish_kernel` launch that
+        adds the chunks' district sums of the last step and their shares of the return.  Same steps, record and noise stream as the one-row kernel;
+        no MARL (the library's refusal), and ``kpi=True`` raises `NotImplementedError`: streaming KPIs in chunked launches are open.
+        ``chunked=False`` (the default) is the call above in every respect, its refusal of a district of more than 16 buildings included."""
         kind = policy_tables.kind           # (`policy._Kind`: the libraries, the trajectory's plane count and what a build without KPIs raises)
+        if chunked:
+            if kind.ext_chunk is None:
+                raise ValueError(f'rollout_policy(chunked=True) needs StoragePolicyTables: there is no building-chunked policy kernel for {type(policy_tables).__name__} '
+                                 '(battery + PV districts run up to 32 buildings in one workgroup row)')
+            if kpi:
+                raise NotImplementedError('rollout_policy(chunked=True, kpi=True): the building-chunked thermal policy kernel '
+                                          '(cl_rollout_full_policy_chunk_kernel) keeps no streaming KPI accumulators')
         if kpi and not self.kpi and kind.no_kpi_error is NotImplementedError:
             raise NotImplementedError('rollout_policy(kpi=True) with StoragePolicyTables: this engine was built without the streaming KPI accumulators -- '
                                       'build it with kpi=True (the thermal policy KPI kernel, cl_rollout_full_policy_kpi_kernel, needs them)')
@@ -522,7 +537,7 @@ class StepEngine:
             # (the library cannot see this: a battery + PV district with EV chargers / washing machines and a non-EV reward has CLD_LEAN set)
             raise NotImplementedError('rollout_policy: districts with flexible loads (EV chargers / washing machines) are not covered by the policy '
                                       'kernel -- it would leave their consumption out of net; use step() / capture_rollout')
-        ext = kind.ext_kpi if kpi else kind.ext
+        ext = kind.ext_chunk if chunked else kind.ext_kpi if kpi else kind.ext
         ext.load()          # (here, not only inside ext.rollout: a missing library is reported in front of the argument checks below)
         kpi_planes = (_ptr(self.kpi_bldg), _ptr(self.kpi_env)) if kpi else ()
         t0 = self.t if t0 is None else t0

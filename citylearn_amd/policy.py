@@ -42,7 +42,17 @@ streaming KPI accumulators, so `evaluate()` scores the controllers afterwards --
 
 (``kpi=True`` on an env built without KPIs raises `NotImplementedError`.)  `MLPPolicy` still refuses such a district.  A district with power
 outages goes through the same two kernels (their outage branch is tested on g2020_cz1 with chosen outage rows: tests/policy_full_util.py
-`outage_district`).  Open: thermal districts of more than 16 buildings (building-chunked) and heads for device actions.
+`outage_district`).
+
+A thermal district of MORE than 16 buildings -- BASELINE config 4's 1024 -- takes the same `StorageMLPPolicy` through a building-chunked launch:
+`cl_rollout_full_policy_chunk_kernel` (csrc/cl_policy_full_chunk.h, ``libcitylearn_amd_policy_full_chunk.so``,
+include/citylearn_amd_policy_full_chunk.h) with one building per wave and balanced chunks of at most eight buildings along the grid's second
+axis, then one `cl_finish_kernel` launch that adds the chunks' district sums and returns.  `VectorCityLearnEnv.rollout_policy` routes there by
+itself; on the engine it is ``rollout_policy(..., chunked=True)``, the chunk size from ``tuning=dict(b_chunk=...)``.  Same policy, same noise
+stream (keyed by global env, column and step: chunking does not change a draw), same record.  The packed tables are the same
+`StoragePolicyTables`; at 1024 buildings ``pre`` is ``[n_sets, rows, 1024, H]`` float32 -- 48 MB per parameter set at H = 16 over the 744-row
+fixture.  Open: device-action heads, and streaming KPIs and MARL in chunked launches (``kpi=True`` raises `NotImplementedError` there, MARL the
+library's refusal).
 """
 from __future__ import annotations
 
@@ -169,6 +179,7 @@ class _Kind:
     ext: '_lib._Extension'            # the rollout library, and the one that also keeps the streaming KPIs
     ext_kpi: '_lib._Extension'
     no_kpi_error: type                # what `rollout_policy(kpi=True)` raises on a build without KPIs
+    ext_chunk: Optional['_lib._Extension'] = None      # the building-chunked rollout library (`rollout_policy(chunked=True)`), where the kind has one
 
     def __post_init__(self):
         self.tables.kind = self
@@ -187,7 +198,7 @@ _THERMAL = _Kind(terms=(((SRC_STATE, abi.CLS_B_SOC), abi.CLF_BATTERY), ((SRC_STA
                  only="the thermal policy kernel only has the building's own storage socs (CLS_B_SOC, CLS_CS_SOC, CLS_HS_SOC, CLS_DS_SOC) and "
                       'net_electricity_consumption (CLO_NET)',
                  tables=StoragePolicyTables, struct=_lib.PolicyFullMLP, constants=FULL_CONSTANTS, max_hidden=CLPF_MAX_HIDDEN, n_planes=CLPF_NT,
-                 ext=_lib.POLICY_FULL, ext_kpi=_lib.POLICY_FULL_KPI, no_kpi_error=NotImplementedError)
+                 ext=_lib.POLICY_FULL, ext_kpi=_lib.POLICY_FULL_KPI, no_kpi_error=NotImplementedError, ext_chunk=_lib.POLICY_FULL_CHUNK)
 # (terms and heads above are written in the header's order)
 assert (CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET) == tuple(range(CLPF_ND)) and (CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS) == tuple(range(CLPF_NA))
 

@@ -430,7 +430,17 @@ class VectorCityLearnEnv:
         actions, up to 16 buildings) the same way through `cl_rollout_full_policy_kernel`: the trajectory then has `policy.CLPF_NT` planes
         (`CLPF_T_ACTION` + head, `_REWARD`, `_NET`, `CLPF_T_SOC` + storage).  ``kpi=True`` on an env built with ``kpi=True`` keeps the streaming KPI
         accumulators in the same single launch (`cl_rollout_full_policy_kpi_kernel`), so `evaluate()` works afterwards without a record or a
-        second env; on an env built without KPIs it raises `NotImplementedError`."""
+        second env; on an env built without KPIs it raises `NotImplementedError`.
+
+        A thermal district of MORE than 16 buildings (BASELINE config 4's 1024) is routed by itself to the building-chunked launch
+        (`StepEngine.rollout_policy(chunked=True)`: `cl_rollout_full_policy_chunk_kernel` + one `cl_finish_kernel`), same policy, record and
+        noise stream.  The packed ``pre`` table is ``[n_sets, rows, n_bldg, H]`` float32: 48 MB per parameter set at 1024 buildings, H = 16 and
+        the 744-row fixture (and a ``record=True`` trajectory ``k_steps x 10 x n_bldg x n_envs`` floats).  ``kpi=True`` there raises
+        `NotImplementedError` (streaming KPIs in chunked launches are open), a MARL reward the library's refusal."""
+        chunked = policy.kind.ext_chunk is not None and self.engine.n_bldg > 16
+        if chunked and kpi:
+            raise NotImplementedError(f'rollout_policy(kpi=True) on a thermal district of {self.engine.n_bldg} > 16 buildings: the building-chunked policy '
+                                      'kernel keeps no streaming KPI accumulators yet -- record the rollout and replay its actions through a kpi=True env')
         if kpi and not self.kpi and policy.kind.no_kpi_error is NotImplementedError:
             raise NotImplementedError('rollout_policy(kpi=True) with a StorageMLPPolicy: this env was built without the streaming KPI accumulators -- '
                                       'build it with VectorCityLearnEnv(..., kpi=True)')
@@ -457,7 +467,7 @@ class VectorCityLearnEnv:
             cache[key] = (policy, policy.pack(layout, self.tables, device=self.device, set_of_block=sob))
         ret = torch.zeros(self.n_envs, dtype=torch.float32, device=self.device)
         traj = torch.empty((k_steps, policy.kind.n_planes, e.n_bldg, self.n_envs), dtype=torch.float32, device=self.device) if record else None
-        e.rollout_policy(k_steps, cache[key][1], seed=seed, ret_env=ret, traj=traj, t0=self._t, kpi=kpi)
+        e.rollout_policy(k_steps, cache[key][1], seed=seed, ret_env=ret, traj=traj, t0=self._t, kpi=kpi, **({'chunked': True} if chunked else {}))
         self._t += k_steps
         return (ret, traj) if record else ret
 

@@ -145,10 +145,12 @@ class _Extension:
     """One closed-loop rollout library: a product library of its own per kernel family, so that the main library's symbol list, structs and
     translation units stay what they are (csrc/cl_<name>.hip, include/citylearn_amd_<name>.h, ``libcitylearn_amd_<name>.so``).  ``label`` names it
     in messages, ``flags`` are the translation unit's own compiler flags, ``entry`` is its rollout entry point taking ``mlp`` and ``n_kpi`` KPI
-    planes, ``headers`` the other extension headers its header includes."""
+    planes, ``headers`` the other extension headers its header includes.  ``extra``: the ctypes of further entry arguments behind the KPI planes;
+    ``functions``: ``(name, restype, argtypes)`` of further exported functions (``Dims`` pointer first) that `load` declares."""
 
-    def __init__(self, name, prefix, label, flags, entry, mlp, n_kpi=0, headers=()):
+    def __init__(self, name, prefix, label, flags, entry, mlp, n_kpi=0, headers=(), extra=(), functions=()):
         self.prefix, self.label, self.entry, self.mlp, self.n_kpi = prefix, label, entry, mlp, n_kpi
+        self.extra, self.functions = tuple(extra), tuple(functions)
         self.path = PKG / f'libcitylearn_amd_{name}.so'
         self.header = abi.HEADER.parent / f'citylearn_amd_{name}.h'
         self.sources = [(CSRC / f'cl_{name}.hip', flags)] if flags else [CSRC / f'cl_{name}.hip']
@@ -174,7 +176,10 @@ class _Extension:
         abi_version, core_abi_version, last_error, entry = (getattr(lib, f'{self.prefix}_{n}') for n in ('abi_version', 'core_abi_version', 'last_error', self.entry))
         abi_version.restype = core_abi_version.restype = entry.restype = ctypes.c_int
         last_error.restype = ctypes.c_char_p
-        entry.argtypes = [ctypes.POINTER(Dims), vp, vp, vp, ctypes.POINTER(self.mlp), vp, vp, vp, vp, *[vp] * self.n_kpi, i32, i32, vp]
+        entry.argtypes = [ctypes.POINTER(Dims), vp, vp, vp, ctypes.POINTER(self.mlp), vp, vp, vp, vp, *[vp] * self.n_kpi, *self.extra, i32, i32, vp]
+        for fname, restype, argtypes in self.functions:
+            fn = getattr(lib, f'{self.prefix}_{fname}')
+            fn.restype, fn.argtypes = restype, list(argtypes)
         got, core = abi_version(), core_abi_version()
         if got != self.abi_version or core != abi.CL_ABI_VERSION:
             raise EngineUnavailable(f'ABI mismatch: {self.label} library {got} (core {core}), headers {self.abi_version} (core {abi.CL_ABI_VERSION}); '
@@ -200,9 +205,16 @@ POLICY_FULL = _Extension('policy_full', 'clpf', 'thermal policy', [], 'rollout_m
 POLICY_FULL_KPI = _Extension('policy_full_kpi', 'clpfk', 'thermal policy KPI', [], 'rollout_mlp_kpi_f32', PolicyFullMLP, n_kpi=2, headers=[POLICY_FULL.header])
 EXTENSIONS = (POLICY, POLICY_KPI, POLICY_FULL, POLICY_FULL_KPI)
 # ... and the thermal one of districts of MORE than 16 buildings, a building-chunked launch (cl_policy_full_chunk.hip, with SLP vectorisation like
-# cl_policy_full.hip; `clpf_mlp` again).  ALL_EXTENSIONS is what `__graft_entry__.build()` builds and checks; EXTENSIONS stays the four one-row ones.
+# cl_policy_full.hip; `clpf_mlp` again).  EXTENSIONS stays the four one-row ones, ALL_EXTENSIONS these five.
 POLICY_FULL_CHUNK = _Extension('policy_full_chunk', 'clpfc', 'chunked thermal policy', [], 'rollout_mlp_f32', PolicyFullMLP, headers=[POLICY_FULL.header])
 ALL_EXTENSIONS = EXTENSIONS + (POLICY_FULL_CHUNK,)
+# ... and the chunked one that also keeps the streaming KPIs (cl_policy_full_chunk_kpi.hip, with SLP vectorisation; `clpf_mlp` again): behind the KPI
+# planes its entry takes the scratch of the district series' chunk samples and its size, which `series_scratch_floats` tells.  A tuple of its own:
+# EXTENSIONS and ALL_EXTENSIONS stay what they are; `__graft_entry__.build()` builds ALL_EXTENSIONS + CHUNK_KPI_EXTENSIONS.
+POLICY_FULL_CHUNK_KPI = _Extension('policy_full_chunk_kpi', 'clpfck', 'chunked thermal policy KPI', [], 'rollout_mlp_kpi_f32', PolicyFullMLP, n_kpi=2,
+                                   headers=[POLICY_FULL.header], extra=(ctypes.c_void_p, ctypes.c_int64),
+                                   functions=(('series_scratch_floats', ctypes.c_int64, (ctypes.POINTER(Dims), ctypes.c_int32)),))
+CHUNK_KPI_EXTENSIONS = (POLICY_FULL_CHUNK_KPI,)
 
 # The names other code and the tests use: read-only views of the descriptions above (build / load / check read the description, so rebinding one
 # of these changes nothing -- change the description's attribute instead)
@@ -220,6 +232,10 @@ build_policy_full_kpi, load_policy_full_kpi, check_policy_full_kpi = POLICY_FULL
 POLICY_FULL_CHUNK_LIB_PATH, POLICY_FULL_CHUNK_HEADER, POLICY_FULL_CHUNK_SOURCES, POLICY_FULL_CHUNK_ABI_VERSION, POLICY_FULL_CHUNK_SYMBOLS = \
     POLICY_FULL_CHUNK.path, POLICY_FULL_CHUNK.header, POLICY_FULL_CHUNK.sources, POLICY_FULL_CHUNK.abi_version, POLICY_FULL_CHUNK.symbols
 build_policy_full_chunk, load_policy_full_chunk, check_policy_full_chunk = POLICY_FULL_CHUNK.build, POLICY_FULL_CHUNK.load, POLICY_FULL_CHUNK.check
+POLICY_FULL_CHUNK_KPI_LIB_PATH, POLICY_FULL_CHUNK_KPI_HEADER, POLICY_FULL_CHUNK_KPI_SOURCES, POLICY_FULL_CHUNK_KPI_ABI_VERSION, POLICY_FULL_CHUNK_KPI_SYMBOLS = \
+    POLICY_FULL_CHUNK_KPI.path, POLICY_FULL_CHUNK_KPI.header, POLICY_FULL_CHUNK_KPI.sources, POLICY_FULL_CHUNK_KPI.abi_version, POLICY_FULL_CHUNK_KPI.symbols
+build_policy_full_chunk_kpi, load_policy_full_chunk_kpi, check_policy_full_chunk_kpi = \
+    POLICY_FULL_CHUNK_KPI.build, POLICY_FULL_CHUNK_KPI.load, POLICY_FULL_CHUNK_KPI.check
 
 
 def policy_kpi_lds_bytes(nw: int, vec: int) -> int:
@@ -248,6 +264,14 @@ def policy_full_kpi_lds_bytes(nw: int) -> int:
     `rollout_full_policy_kpi_lds_floats` -- the ring of both district series [8][2][nw][64], the two series [2][12][64], the staged policy rows
     [nw][(5 + 4) x 32 + 4 x 8], the units' twelve sums [nw][12][64] (tests/test_policy_full_kpi_host.py holds it against the header's formula)."""
     return 4 * (8 * 2 * nw * 64 + 2 * 12 * 64 + nw * ((5 + 4) * 32 + 4 * 8) + nw * 12 * 64)
+
+
+def policy_full_chunk_kpi_lds_bytes(nw: int) -> int:
+    """Dynamic LDS of one `cl_rollout_full_policy_chunk_kpi_kernel` workgroup of ``nw`` waves (= buildings of a chunk; one env per lane):
+    csrc/cl_policy_full_chunk_kpi.h's `rollout_full_policy_chunk_kpi_lds_floats` -- the ring of both district series [8][2][nw][64], then the staged
+    policy rows [nw][(5 + 4) x 32 + 4 x 8] (the units' twelve sums live in registers) -- 43 008 bytes at the default eight waves, 86 016 at sixteen
+    (tests/test_policy_full_chunk_kpi_host.py holds it against the header's formula)."""
+    return 4 * (8 * 2 * nw * 64 + nw * ((5 + 4) * 32 + 4 * 8))
 
 
 _lib = None

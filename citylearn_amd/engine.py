@@ -216,6 +216,10 @@ class StepEngine:
         self.act_low = self.act_high = None         # bounds of the on-device rollout policy (set_action_limits)
         self._policy_actions = None                 # scratch planes of cl_rollout_seq_f32 (four steps of policy draws)
         self._dims_fused = None                     # `dims` with CLD_ROLLOUT_FUSED (rollout(fused=True) on a kpi=True engine)
+        # rollout_policy(chunked=True, kpi=True): steps per call -- bounds the scratch of the district series' chunk samples, which the engine owns
+        # (window x 2 x n_chunks x n_env floats, allocated at the first such call and reused)
+        self.policy_kpi_window = 64
+        self._series_scratch = None
         self.t = 0
         self.reset()
 
@@ -518,16 +522,21 @@ class StepEngine:
         ``libcitylearn_amd_policy_full_chunk.so``) with one building per wave and chunks of ``tuning=dict(b_chunk=...)`` buildings along the grid's
         second axis -- default: balanced chunks of at most eight, 17 -> 6 + 6 + 5, 1024 -> 128 x 8 -- followed by one `cl_finish_kernel` launch that
         adds the chunks' district sums of the last step and their shares of the return.  Same steps, record and noise stream as the one-row kernel;
-        no MARL (the library's refusal), and ``kpi=True`` raises `NotImplementedError`: streaming KPIs in chunked launches are open.
-        ``chunked=False`` (the default) is the call above in every respect, its refusal of a district of more than 16 buildings included."""
+        no MARL (the library's refusal).  ``chunked=False`` (the default) is the call above in every respect, its refusal of a district of more
+        than 16 buildings included.
+
+        ``chunked=True, kpi=True`` on an engine built with ``kpi=True`` (otherwise `NotImplementedError`) keeps the streaming KPI accumulators in
+        the chunked launch too (`clpfck_rollout_mlp_kpi_f32`, ``libcitylearn_amd_policy_full_chunk_kpi.so``): per call
+        `cl_rollout_full_policy_chunk_kpi_kernel` (the units' twelve sums, and every chunk's partial samples of the two district series into a
+        scratch tensor the engine owns), `cl_kpi_series_chunk_kernel` (both series of every env from those samples) and `cl_finish_kernel`.  The K
+        steps are cut into windows of at most ``self.policy_kpi_window`` (64) steps, one call each -- ``traj`` and the step index advance,
+        ``ret_env`` accumulates -- so that the scratch stays ``window x 2 x n_chunks x n_env`` floats: 64 MB at 1024 buildings x 1024 envs instead
+        of 755 MB for a 720-step launch.  The windows do not show in the result: state, outputs, record and every KPI plane are bit for bit what
+        one call leaves.  ``chunked=True, kpi=False`` on a ``kpi=True`` engine stays `clpfc_rollout_mlp_f32`'s refusal."""
         kind = policy_tables.kind           # (`policy._Kind`: the libraries, the trajectory's plane count and what a build without KPIs raises)
-        if chunked:
-            if kind.ext_chunk is None:
-                raise ValueError(f'rollout_policy(chunked=True) needs StoragePolicyTables: there is no building-chunked policy kernel for {type(policy_tables).__name__} '
-                                 '(battery + PV districts run up to 32 buildings in one workgroup row)')
-            if kpi:
-                raise NotImplementedError('rollout_policy(chunked=True, kpi=True): the building-chunked thermal policy kernel '
-                                          '(cl_rollout_full_policy_chunk_kernel) keeps no streaming KPI accumulators')
+        if chunked and kind.ext_chunk is None:
+            raise ValueError(f'rollout_policy(chunked=True) needs StoragePolicyTables: there is no building-chunked policy kernel for {type(policy_tables).__name__} '
+                             '(battery + PV districts run up to 32 buildings in one workgroup row)')
         if kpi and not self.kpi and kind.no_kpi_error is NotImplementedError:
             raise NotImplementedError('rollout_policy(kpi=True) with StoragePolicyTables: this engine was built without the streaming KPI accumulators -- '
                                       'build it with kpi=True (the thermal policy KPI kernel, cl_rollout_full_policy_kpi_kernel, needs them)')
@@ -537,7 +546,7 @@ class StepEngine:
             # (the library cannot see this: a battery + PV district with EV chargers / washing machines and a non-EV reward has CLD_LEAN set)
             raise NotImplementedError('rollout_policy: districts with flexible loads (EV chargers / washing machines) are not covered by the policy '
                                       'kernel -- it would leave their consumption out of net; use step() / capture_rollout')
-        ext = kind.ext_chunk if chunked else kind.ext_kpi if kpi else kind.ext
+        ext = (kind.ext_chunk_kpi if kpi else kind.ext_chunk) if chunked else kind.ext_kpi if kpi else kind.ext
         ext.load()          # (here, not only inside ext.rollout: a missing library is reported in front of the argument checks below)
         kpi_planes = (_ptr(self.kpi_bldg), _ptr(self.kpi_env)) if kpi else ()
         t0 = self.t if t0 is None else t0
@@ -553,11 +562,37 @@ class StepEngine:
             if x is not None and (x.dtype != torch.float32 or x.device != self.device or tuple(x.shape) != shape or not x.is_contiguous()):
                 raise ValueError(f'{name} must be a contiguous float32 tensor {shape} on {self.device}')
         mlp = pt.struct(seed)
-        with torch.cuda.device(self.device):
-            ext.rollout(ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), ctypes.byref(mlp), _ptr(self.out_bldg),
-                        _ptr(self._out_env), _ptr(ret_env), _ptr(traj), *kpi_planes, int(t0), int(k_steps), self._stream())
+        t0, k_steps = int(t0), int(k_steps)
+        if chunked and kpi:
+            self._rollout_policy_chunk_kpi(ext, mlp, kpi_planes, ret_env, traj, t0, k_steps)
+        else:
+            with torch.cuda.device(self.device):
+                ext.rollout(ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), ctypes.byref(mlp), _ptr(self.out_bldg),
+                            _ptr(self._out_env), _ptr(ret_env), _ptr(traj), *kpi_planes, t0, k_steps, self._stream())
         self._pending_t = None
         self.t = t0 + k_steps
+
+    def _rollout_policy_chunk_kpi(self, ext, mlp, kpi_planes, ret_env, traj, t0: int, k_steps: int):
+        """`rollout_policy(chunked=True, kpi=True)`: the K steps as calls of at most `policy_kpi_window` steps, all through one scratch tensor."""
+        window = max(1, int(self.policy_kpi_window))
+        if k_steps < 0 or t0 < 0 or t0 + k_steps > self.dims.n_steps:
+            window = max(1, k_steps)        # (one call, which the library refuses by its step range before anything moves -- not a later window)
+        need = int(getattr(ext.load(), f'{ext.prefix}_series_scratch_floats')(ctypes.byref(self.dims), max(1, min(window, k_steps))))
+        if need < 0:
+            ext.check(-need)
+        if self._series_scratch is None or self._series_scratch.numel() < need:
+            self._series_scratch = torch.empty(need, dtype=torch.float32, device=self.device)
+        scratch = self._series_scratch
+        with torch.cuda.device(self.device):
+            done = 0
+            while True:
+                k = min(window, k_steps - done)
+                ext.rollout(ctypes.byref(self.dims), _ptr(self.params), _ptr(self.ts), _ptr(self.state), ctypes.byref(mlp), _ptr(self.out_bldg),
+                            _ptr(self._out_env), _ptr(ret_env), _ptr(None if traj is None else traj[done:done + k]), *kpi_planes,
+                            _ptr(scratch), scratch.numel(), t0 + done, k, self._stream())
+                done += k
+                if done >= k_steps:
+                    break
 
     def step_many(self, actions: torch.Tensor, t0: Optional[int] = None):
         """``actions.shape[0]`` consecutive env steps enqueued by ONE C call (`cl_rollout_seq_f32` with an open-loop action tensor

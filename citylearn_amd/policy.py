@@ -51,8 +51,18 @@ axis, then one `cl_finish_kernel` launch that adds the chunks' district sums and
 itself; on the engine it is ``rollout_policy(..., chunked=True)``, the chunk size from ``tuning=dict(b_chunk=...)``.  Same policy, same noise
 stream (keyed by global env, column and step: chunking does not change a draw), same record.  The packed tables are the same
 `StoragePolicyTables`; at 1024 buildings ``pre`` is ``[n_sets, rows, 1024, H]`` float32 -- 48 MB per parameter set at H = 16 over the 744-row
-fixture.  Open: device-action heads, and streaming KPIs and MARL in chunked launches (``kpi=True`` raises `NotImplementedError` there, MARL the
-library's refusal).
+fixture.
+
+On an env built with ``kpi=True`` the chunked call takes ``kpi=True`` as well: `cl_rollout_full_policy_chunk_kpi_kernel`
+(csrc/cl_policy_full_chunk_kpi.h, ``libcitylearn_amd_policy_full_chunk_kpi.so``, include/citylearn_amd_policy_full_chunk_kpi.h) keeps every unit's
+twelve sums inside the launch and hands the chunks' partial samples of the two district series to `cl_kpi_series_chunk_kernel`; `cl_finish_kernel`
+follows as before.  `evaluate()` then scores the 1024-building district's controllers without a record, a second env or a replay:
+
+    kenv = VectorCityLearnEnv(schema_1024, n_envs, kpi=True)
+    ret = kenv.rollout_policy(spolicy, 720, seed=3, kpi=True)      # windows of StepEngine.policy_kpi_window = 64 steps, one call each
+    building_kpis, district_kpis = kenv.evaluate()
+
+Open: device-action heads, and MARL in chunked launches (the library's refusal).
 """
 from __future__ import annotations
 
@@ -180,6 +190,7 @@ class _Kind:
     ext_kpi: '_lib._Extension'
     no_kpi_error: type                # what `rollout_policy(kpi=True)` raises on a build without KPIs
     ext_chunk: Optional['_lib._Extension'] = None      # the building-chunked rollout library (`rollout_policy(chunked=True)`), where the kind has one
+    ext_chunk_kpi: Optional['_lib._Extension'] = None  # ... and the one that also keeps the streaming KPIs (`rollout_policy(chunked=True, kpi=True)`)
 
     def __post_init__(self):
         self.tables.kind = self
@@ -198,7 +209,8 @@ _THERMAL = _Kind(terms=(((SRC_STATE, abi.CLS_B_SOC), abi.CLF_BATTERY), ((SRC_STA
                  only="the thermal policy kernel only has the building's own storage socs (CLS_B_SOC, CLS_CS_SOC, CLS_HS_SOC, CLS_DS_SOC) and "
                       'net_electricity_consumption (CLO_NET)',
                  tables=StoragePolicyTables, struct=_lib.PolicyFullMLP, constants=FULL_CONSTANTS, max_hidden=CLPF_MAX_HIDDEN, n_planes=CLPF_NT,
-                 ext=_lib.POLICY_FULL, ext_kpi=_lib.POLICY_FULL_KPI, no_kpi_error=NotImplementedError, ext_chunk=_lib.POLICY_FULL_CHUNK)
+                 ext=_lib.POLICY_FULL, ext_kpi=_lib.POLICY_FULL_KPI, no_kpi_error=NotImplementedError, ext_chunk=_lib.POLICY_FULL_CHUNK,
+                 ext_chunk_kpi=_lib.POLICY_FULL_CHUNK_KPI)
 # (terms and heads above are written in the header's order)
 assert (CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET) == tuple(range(CLPF_ND)) and (CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS) == tuple(range(CLPF_NA))
 

@@ -435,12 +435,12 @@ class VectorCityLearnEnv:
         A thermal district of MORE than 16 buildings (BASELINE config 4's 1024) is routed by itself to the building-chunked launch
         (`StepEngine.rollout_policy(chunked=True)`: `cl_rollout_full_policy_chunk_kernel` + one `cl_finish_kernel`), same policy, record and
         noise stream.  The packed ``pre`` table is ``[n_sets, rows, n_bldg, H]`` float32: 48 MB per parameter set at 1024 buildings, H = 16 and
-        the 744-row fixture (and a ``record=True`` trajectory ``k_steps x 10 x n_bldg x n_envs`` floats).  ``kpi=True`` there raises
-        `NotImplementedError` (streaming KPIs in chunked launches are open), a MARL reward the library's refusal."""
+        the 744-row fixture (and a ``record=True`` trajectory ``k_steps x 10 x n_bldg x n_envs`` floats).  ``kpi=True`` on an env built with
+        ``kpi=True`` keeps the streaming KPI accumulators there too (`StepEngine.rollout_policy(chunked=True, kpi=True)`:
+        `cl_rollout_full_policy_chunk_kpi_kernel` + `cl_kpi_series_chunk_kernel` + `cl_finish_kernel` per window of
+        ``engine.policy_kpi_window`` steps), so `evaluate()` works afterwards without a record or a second env; on an env built without KPIs it
+        raises `NotImplementedError`.  A MARL reward is the library's refusal."""
         chunked = policy.kind.ext_chunk is not None and self.engine.n_bldg > 16
-        if chunked and kpi:
-            raise NotImplementedError(f'rollout_policy(kpi=True) on a thermal district of {self.engine.n_bldg} > 16 buildings: the building-chunked policy '
-                                      'kernel keeps no streaming KPI accumulators yet -- record the rollout and replay its actions through a kpi=True env')
         if kpi and not self.kpi and policy.kind.no_kpi_error is NotImplementedError:
             raise NotImplementedError('rollout_policy(kpi=True) with a StorageMLPPolicy: this env was built without the streaming KPI accumulators -- '
                                       'build it with VectorCityLearnEnv(..., kpi=True)')

@@ -215,6 +215,11 @@ POLICY_FULL_CHUNK_KPI = _Extension('policy_full_chunk_kpi', 'clpfck', 'chunked t
                                    headers=[POLICY_FULL.header], extra=(ctypes.c_void_p, ctypes.c_int64),
                                    functions=(('series_scratch_floats', ctypes.c_int64, (ctypes.POINTER(Dims), ctypes.c_int32)),))
 CHUNK_KPI_EXTENSIONS = (POLICY_FULL_CHUNK_KPI,)
+# ... and the battery + PV one of districts of MORE than 32 buildings, a building-chunked launch with two buildings per wave (cl_policy_chunk.hip,
+# without SLP vectorisation like cl_policy.hip; `clpol_mlp` again).  A tuple of its own once more: the tuples above stay what they are;
+# `__graft_entry__.build()` builds ALL_EXTENSIONS + CHUNK_KPI_EXTENSIONS + LEAN_CHUNK_EXTENSIONS.
+POLICY_CHUNK = _Extension('policy_chunk', 'clpc', 'chunked policy', ['-fno-slp-vectorize'], 'rollout_mlp_f32', PolicyMLP, headers=[POLICY.header])
+LEAN_CHUNK_EXTENSIONS = (POLICY_CHUNK,)
 
 # The names other code and the tests use: read-only views of the descriptions above (build / load / check read the description, so rebinding one
 # of these changes nothing -- change the description's attribute instead)
@@ -236,6 +241,9 @@ POLICY_FULL_CHUNK_KPI_LIB_PATH, POLICY_FULL_CHUNK_KPI_HEADER, POLICY_FULL_CHUNK_
     POLICY_FULL_CHUNK_KPI.path, POLICY_FULL_CHUNK_KPI.header, POLICY_FULL_CHUNK_KPI.sources, POLICY_FULL_CHUNK_KPI.abi_version, POLICY_FULL_CHUNK_KPI.symbols
 build_policy_full_chunk_kpi, load_policy_full_chunk_kpi, check_policy_full_chunk_kpi = \
     POLICY_FULL_CHUNK_KPI.build, POLICY_FULL_CHUNK_KPI.load, POLICY_FULL_CHUNK_KPI.check
+POLICY_CHUNK_LIB_PATH, POLICY_CHUNK_HEADER, POLICY_CHUNK_SOURCES, POLICY_CHUNK_ABI_VERSION, POLICY_CHUNK_SYMBOLS = \
+    POLICY_CHUNK.path, POLICY_CHUNK.header, POLICY_CHUNK.sources, POLICY_CHUNK.abi_version, POLICY_CHUNK.symbols
+build_policy_chunk, load_policy_chunk, check_policy_chunk = POLICY_CHUNK.build, POLICY_CHUNK.load, POLICY_CHUNK.check
 
 
 def policy_kpi_lds_bytes(nw: int, vec: int) -> int:
@@ -244,6 +252,14 @@ def policy_kpi_lds_bytes(nw: int, vec: int) -> int:
     policy's staged rows [nw][2][3 x 32 + 8] (tests/test_policy_kpi_host.py holds it against the header's formula)."""
     tile = 64 * vec
     return 4 * (8 * nw * tile + 12 * tile + 16 + 8 * 4 * 32 + 5 * 32 + nw * 2 * (3 * 32 + 8))
+
+
+def policy_chunk_lds_bytes(nw: int, vec: int) -> int:
+    """Dynamic LDS of one `cl_rollout_policy_chunk_kernel` workgroup of ``nw`` waves (two buildings each) at ``vec`` envs per lane:
+    csrc/cl_policy_chunk.h's `rollout_policy_chunk_lds_floats`, which is `cl_rollout_policy_kernel`'s formula -- the chunk's reduction rows
+    [nw][4][tile], then the staged policy rows [nw][2][3 x 32 + 8] -- 29 696 bytes at sixteen waves and one env per lane, 46 080 at two
+    (tests/test_policy_chunk_host.py holds it against the header's formula)."""
+    return 4 * (nw * 4 * 64 * vec + nw * 2 * (3 * 32 + 8))
 
 
 def policy_full_lds_bytes(nw: int, vec: int) -> int:

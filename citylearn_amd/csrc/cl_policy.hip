@@ -40,7 +40,8 @@ int clpol_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const flo
     if (!(dims->flags & CLD_LEAN))
         return fail(CL_EINVAL, "clpol_rollout_mlp_f32: only battery + PV districts (CLD_LEAN); a thermal / outage district has no closed-loop rollout kernel");
     if (dims->n_bldg > 32)
-        return fail(CL_EINVAL, "clpol_rollout_mlp_f32: n_bldg=%d > 32 would be a building-chunked launch, which the policy kernel is not", dims->n_bldg);
+        return fail(CL_EINVAL, "clpol_rollout_mlp_f32: n_bldg=%d > 32 would be a building-chunked launch, which the policy kernel is not: "
+                               "clpc_rollout_mlp_f32 (libcitylearn_amd_policy_chunk.so)", dims->n_bldg);
     if (dims->flags & CLD_F64_MAPS)
         return fail(CL_EINVAL, "clpol_rollout_mlp_f32: the battery map in fp32 or as the float64 chain (CLD_F64_CHAIN), not CLD_F64_MAPS");
     if (dims->flags & CLD_KPI)

@@ -525,7 +525,16 @@ class StepEngine:
         no MARL (the library's refusal).  ``chunked=False`` (the default) is the call above in every respect, its refusal of a district of more
         than 16 buildings included.
 
-        ``chunked=True, kpi=True`` on an engine built with ``kpi=True`` (otherwise `NotImplementedError`) keeps the streaming KPI accumulators in
+        ``chunked=True`` with `PolicyTables` (a `policy.MLPPolicy`'s) sends a BATTERY + PV district of MORE than 32 buildings to its own
+        building-chunked launch: `cl_rollout_policy_chunk_kernel` (`clpc_rollout_mlp_f32`, ``libcitylearn_amd_policy_chunk.so``) with two buildings
+        per wave and chunks of ``tuning=dict(b_chunk=...)`` <= 32 buildings -- default: the blind chunked rollout's 32-building workgroups, balanced,
+        33 -> 17 + 16, 1024 -> 32 x 32; ``tuning=dict(b_chunk=16, nw=16)`` runs one building per wave -- followed by one `cl_finish_kernel` launch.
+        Same steps, record ``[k_steps, CLPOL_NT, n_bldg, n_env]`` and noise stream as `cl_rollout_policy_kernel`; no MARL and no ``kpi=True``
+        engine (the library's refusals); on a thermal district it is a `ValueError`.  ``chunked=True, kpi=True`` with `PolicyTables` raises
+        `NotImplementedError`: there is no chunked lean KPI kernel -- record ``traj`` and replay its action plane through `step_many` on a second
+        engine built with ``kpi=True``.
+
+        With `StoragePolicyTables`, ``chunked=True, kpi=True`` on an engine built with ``kpi=True`` (otherwise `NotImplementedError`) keeps the streaming KPI accumulators in
         the chunked launch too (`clpfck_rollout_mlp_kpi_f32`, ``libcitylearn_amd_policy_full_chunk_kpi.so``): per call
         `cl_rollout_full_policy_chunk_kpi_kernel` (the units' twelve sums, and every chunk's partial samples of the two district series into a
         scratch tensor the engine owns), `cl_kpi_series_chunk_kernel` (both series of every env from those samples) and `cl_finish_kernel`.  The K
@@ -534,9 +543,15 @@ class StepEngine:
         of 755 MB for a 720-step launch.  The windows do not show in the result: state, outputs, record and every KPI plane are bit for bit what
         one call leaves.  ``chunked=True, kpi=False`` on a ``kpi=True`` engine stays `clpfc_rollout_mlp_f32`'s refusal."""
         kind = policy_tables.kind           # (`policy._Kind`: the libraries, the trajectory's plane count and what a build without KPIs raises)
-        if chunked and kind.ext_chunk is None:
-            raise ValueError(f'rollout_policy(chunked=True) needs StoragePolicyTables: there is no building-chunked policy kernel for {type(policy_tables).__name__} '
-                             '(battery + PV districts run up to 32 buildings in one workgroup row)')
+        ext_chunk = kind.ext_chunk or kind.ext_chunk_pair
+        if chunked and (ext_chunk is None or (kind.ext_chunk is None and not self.dims.flags & abi.CLD_LEAN)):
+            raise ValueError(f'rollout_policy(chunked=True) needs StoragePolicyTables here: there is no building-chunked policy kernel for '
+                             f'{type(policy_tables).__name__}' + (' at all' if ext_chunk is None else ' on a thermal district (its chunked kernel takes '
+                                                                  'battery + PV districts, CLD_LEAN, only)'))
+        if chunked and kpi and kind.ext_chunk_kpi is None:
+            raise NotImplementedError(f'rollout_policy(chunked=True, kpi=True) with {type(policy_tables).__name__}: there is no chunked lean KPI kernel -- the '
+                                      'building-chunked battery + PV policy launch keeps no streaming KPI accumulators.  Record the rollout (traj) and feed '
+                                      'its action plane through step_many() on a second engine built with kpi=True')
         if kpi and not self.kpi and kind.no_kpi_error is NotImplementedError:
             raise NotImplementedError('rollout_policy(kpi=True) with StoragePolicyTables: this engine was built without the streaming KPI accumulators -- '
                                       'build it with kpi=True (the thermal policy KPI kernel, cl_rollout_full_policy_kpi_kernel, needs them)')
@@ -546,7 +561,7 @@ class StepEngine:
             # (the library cannot see this: a battery + PV district with EV chargers / washing machines and a non-EV reward has CLD_LEAN set)
             raise NotImplementedError('rollout_policy: districts with flexible loads (EV chargers / washing machines) are not covered by the policy '
                                       'kernel -- it would leave their consumption out of net; use step() / capture_rollout')
-        ext = (kind.ext_chunk_kpi if kpi else kind.ext_chunk) if chunked else kind.ext_kpi if kpi else kind.ext
+        ext = (kind.ext_chunk_kpi if kpi else ext_chunk) if chunked else kind.ext_kpi if kpi else kind.ext
         ext.load()          # (here, not only inside ext.rollout: a missing library is reported in front of the argument checks below)
         kpi_planes = (_ptr(self.kpi_bldg), _ptr(self.kpi_env)) if kpi else ()
         t0 = self.t if t0 is None else t0

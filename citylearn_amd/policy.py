@@ -62,7 +62,16 @@ follows as before.  `evaluate()` then scores the 1024-building district's contro
     ret = kenv.rollout_policy(spolicy, 720, seed=3, kpi=True)      # windows of StepEngine.policy_kpi_window = 64 steps, one call each
     building_kpis, district_kpis = kenv.evaluate()
 
-Open: device-action heads, and MARL in chunked launches (the library's refusal).
+A battery + PV district of MORE than 32 buildings -- the 1024-building tiling of the 2022 schema -- takes the `MLPPolicy` through a
+building-chunked launch as well: `cl_rollout_policy_chunk_kernel` (csrc/cl_policy_chunk.h, ``libcitylearn_amd_policy_chunk.so``,
+include/citylearn_amd_policy_chunk.h) with two buildings per wave and the blind chunked rollout's 32-building workgroups, balanced (33 -> 17 + 16,
+1024 -> 32 x 32), then one `cl_finish_kernel` launch.  `VectorCityLearnEnv.rollout_policy` routes there by itself (`_Kind.one_row_max`); on the
+engine it is ``rollout_policy(..., chunked=True)`` with `PolicyTables`, chunk size and waves from ``tuning=dict(b_chunk=..., nw=...)``.  Same
+policy, same noise stream, same record ``[k_steps, CLPOL_NT, n_bldg, n_envs]``.  This launch keeps NO streaming KPIs (``chunked=True, kpi=True``
+with `PolicyTables` raises `NotImplementedError`): score such a district by the replay above -- record, then `StepEngine.step_many` of the action
+plane on a second, ``kpi=True`` engine.
+
+Open: device-action heads, streaming KPIs in the chunked battery + PV launch, and MARL in chunked launches (the libraries' refusal).
 """
 from __future__ import annotations
 
@@ -191,6 +200,8 @@ class _Kind:
     no_kpi_error: type                # what `rollout_policy(kpi=True)` raises on a build without KPIs
     ext_chunk: Optional['_lib._Extension'] = None      # the building-chunked rollout library (`rollout_policy(chunked=True)`), where the kind has one
     ext_chunk_kpi: Optional['_lib._Extension'] = None  # ... and the one that also keeps the streaming KPIs (`rollout_policy(chunked=True, kpi=True)`)
+    ext_chunk_pair: Optional['_lib._Extension'] = None  # the chunked library of a kind that runs TWO buildings per wave (no KPI twin yet)
+    one_row_max: int = 16             # buildings one workgroup row holds: beyond it `VectorCityLearnEnv.rollout_policy` asks for the chunked launch
 
     def __post_init__(self):
         self.tables.kind = self
@@ -201,7 +212,7 @@ _LEAN = _Kind(terms=(((SRC_STATE, abi.CLS_B_SOC), None), ((SRC_OUT, abi.CLO_NET)
               refuse_device_actions=False,
               only="the policy kernel only has the building's own electrical_storage_soc (CLS_B_SOC) and net_electricity_consumption (CLO_NET)",
               tables=PolicyTables, struct=_lib.PolicyMLP, constants=CONSTANTS, max_hidden=CLPOL_MAX_HIDDEN, n_planes=CLPOL_NT,
-              ext=_lib.POLICY, ext_kpi=_lib.POLICY_KPI, no_kpi_error=ValueError)
+              ext=_lib.POLICY, ext_kpi=_lib.POLICY_KPI, no_kpi_error=ValueError, ext_chunk_pair=_lib.POLICY_CHUNK, one_row_max=32)
 _THERMAL = _Kind(terms=(((SRC_STATE, abi.CLS_B_SOC), abi.CLF_BATTERY), ((SRC_STATE, abi.CLS_CS_SOC), abi.CLF_COOL_STO), ((SRC_STATE, abi.CLS_HS_SOC), abi.CLF_HEAT_STO),
                         ((SRC_STATE, abi.CLS_DS_SOC), abi.CLF_DHW_STO), ((SRC_OUT, abi.CLO_NET), None)),           # rows CLPF_D_SOC, _CS, _HS, _DS, _NET
                  head_slots=(abi.CLP_ACT_ELEC_STO, abi.CLP_ACT_COOL_STO, abi.CLP_ACT_HEAT_STO, abi.CLP_ACT_DHW_STO), head_shape=(CLPF_NA,),    # CLPF_A_*
@@ -210,7 +221,7 @@ _THERMAL = _Kind(terms=(((SRC_STATE, abi.CLS_B_SOC), abi.CLF_BATTERY), ((SRC_STA
                       'net_electricity_consumption (CLO_NET)',
                  tables=StoragePolicyTables, struct=_lib.PolicyFullMLP, constants=FULL_CONSTANTS, max_hidden=CLPF_MAX_HIDDEN, n_planes=CLPF_NT,
                  ext=_lib.POLICY_FULL, ext_kpi=_lib.POLICY_FULL_KPI, no_kpi_error=NotImplementedError, ext_chunk=_lib.POLICY_FULL_CHUNK,
-                 ext_chunk_kpi=_lib.POLICY_FULL_CHUNK_KPI)
+                 ext_chunk_kpi=_lib.POLICY_FULL_CHUNK_KPI, one_row_max=16)
 # (terms and heads above are written in the header's order)
 assert (CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET) == tuple(range(CLPF_ND)) and (CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS) == tuple(range(CLPF_NA))
 

@@ -439,8 +439,13 @@ class VectorCityLearnEnv:
         ``kpi=True`` keeps the streaming KPI accumulators there too (`StepEngine.rollout_policy(chunked=True, kpi=True)`:
         `cl_rollout_full_policy_chunk_kpi_kernel` + `cl_kpi_series_chunk_kernel` + `cl_finish_kernel` per window of
         ``engine.policy_kpi_window`` steps), so `evaluate()` works afterwards without a record or a second env; on an env built without KPIs it
-        raises `NotImplementedError`.  A MARL reward is the library's refusal."""
-        chunked = policy.kind.ext_chunk is not None and self.engine.n_bldg > 16
+        raises `NotImplementedError`.  A MARL reward is the library's refusal.
+
+        A BATTERY + PV district of MORE than 32 buildings (the 1024-building tiling of the 2022 schema) with an `MLPPolicy` is routed by itself
+        too: `cl_rollout_policy_chunk_kernel` + one `cl_finish_kernel` (`StepEngine.rollout_policy(chunked=True)` with `PolicyTables`), same
+        policy, record and noise stream.  That launch keeps no streaming KPIs: ``kpi=True`` there raises `NotImplementedError` (record, then replay
+        the action plane on a ``kpi=True`` env), and MARL is the library's refusal."""
+        chunked = (policy.kind.ext_chunk or policy.kind.ext_chunk_pair) is not None and self.engine.n_bldg > policy.kind.one_row_max
         if kpi and not self.kpi and policy.kind.no_kpi_error is NotImplementedError:
             raise NotImplementedError('rollout_policy(kpi=True) with a StorageMLPPolicy: this env was built without the streaming KPI accumulators -- '
                                       'build it with VectorCityLearnEnv(..., kpi=True)')

@@ -49,6 +49,12 @@ CONSTANTS = dict(_C)
 # (CL_ABI_VERSION comes from the header like everything else: 9 since CLD_ROLLOUT_FUSED -- `cl_rollout_seq_f32` as one fused launch that keeps
 #  the streaming KPI accumulators; `_lib.load()` refuses a library built from another version)
 
+# The one constant mirrored by hand: the `CLD_LEAN_UNIFORM` hint (a cast expression in the header, which the parser above skips, so that
+# CONSTANTS stays the table of mode bits other code enumerates) -- held against the header's own line
+CLD_LEAN_UNIFORM = 1 << 17
+assert re.search(r'#define\s+CLD_LEAN_UNIFORM\s+\(\(uint32_t\)1 << 17\)', HEADER.read_text()) and 'CLD_LEAN_UNIFORM' not in _C
+assert not any(v & CLD_LEAN_UNIFORM for k, v in _C.items() if k.startswith('CLD_') and k != 'CLD_REWARD_SHIFT'), 'CLD_LEAN_UNIFORM collides'
+
 # every function the header declares (used by the "library exports every symbol" test)
 EXPORTED_SYMBOLS = sorted(set(re.findall(r'\b(cl_\w+)\s*\(', _strip_comments(HEADER.read_text()))))
 

@@ -80,10 +80,17 @@ struct Bp {         // what stays live for the whole unit
     int a_cs, a_hs, a_ds, a_cd, a_hd, a_coh;
 };
 
-#ifdef CL_TU_CONST_TABLES
-// (cl_policy_full_kpi.hip: every read of the READ-ONLY tables through the constant address space -- a scalar load whatever surrounds it, where a
-//  K loop that holds a barrier turns a plain global read into a vector load per lane: cl_rollout.h's note on as_const.  Never on an LDS copy.)
+#ifndef CL_HOST_SHIM
+// A READ-ONLY table through the constant address space: a uniform read is a scalar load whatever surrounds it, where stores the compiler cannot
+// tell apart from the table (the plane stores are vector-typed: they may alias anything) turn a plain global read behind them into a vector load
+// per lane.  Never on an LDS copy.  A caller that holds such a pointer passes it to the loaders below in place of the plain one
+// (lean_step_body's uniform path, cl_kernels.hip); CL_TU_CONST_TABLES does it for every read of a translation unit.
 typedef const uint32_t __attribute__((address_space(4)))* cl_ctab;
+CL_DEV cl_ctab as_ctab(const void* p) { return (cl_ctab)(const uint32_t*)p; }
+CL_DEV float pw(cl_ctab p, int slot) { return __uint_as_float(p[slot]); }
+#endif
+#ifdef CL_TU_CONST_TABLES
+// (cl_policy_full_kpi.hip: a K loop that holds a barrier is such a surrounding -- cl_rollout.h's note on as_const)
 #define CL_TAB(p) ((::cl::cl_ctab)(const uint32_t*)(p))
 #else
 #define CL_TAB(p) (p)
@@ -394,19 +401,32 @@ CL_DEV double pc(const uint32_t* __restrict__ p, int k) {           // k-th doub
     return d;
 }
 
-// the float64 part, from the CLP_C_* block at p + CLP_C_FIRST
-CL_DEV void load_battc64(BattC& C, const uint32_t* __restrict__ p) {
+#ifndef CL_HOST_SHIM
+CL_DEV double pc(cl_ctab p, int k) {
+    const uint64_t bits = (uint64_t)p[CLP_C_FIRST + 2 * k] | ((uint64_t)p[CLP_C_FIRST + 2 * k + 1] << 32);
+    double d;
+    __builtin_memcpy(&d, &bits, 8);
+    return d;
+}
+#endif
+
+// the float64 part, from the CLP_C_* block at p + CLP_C_FIRST (P: a plain pointer or a cl_ctab)
+template <class P>
+CL_DEV void load_battc64_from(BattC& C, P p) {
     C.cap = pc(p, CLPC_CAP); C.oml = pc(p, CLPC_OML); C.rcap = pc(p, CLPC_RCAP); C.pdt = pc(p, CLPC_PDT); C.pow = pc(p, CLPC_POW);
     C.rpow = pc(p, CLPC_RPOW); C.r = pc(p, CLPC_TSR);
     C.ca0 = pc(p, CLPC_CPC_A0); C.cb0 = pc(p, CLPC_CPC_B0); C.cx1 = pc(p, CLPC_CPC_X1); C.cdb1 = pc(p, CLPC_CPC_DB1);
     C.ea0 = pc(p, CLPC_PEC_A0); C.eb0 = pc(p, CLPC_PEC_B0); C.ex1 = pc(p, CLPC_PEC_X1); C.edb1 = pc(p, CLPC_PEC_DB1);
     C.ex2 = pc(p, CLPC_PEC_X2); C.edb2 = pc(p, CLPC_PEC_DB2); C.ex3 = pc(p, CLPC_PEC_X3); C.edb3 = pc(p, CLPC_PEC_DB3);
 }
+CL_DEV void load_battc64(BattC& C, const uint32_t* __restrict__ p) { load_battc64_from(C, p); }
 
-CL_DEV void load_battc(BattC& C, const uint32_t* __restrict__ p) {
-    load_battc64(C, p);
+template <class P>
+CL_DEV void load_battc_from(BattC& C, P p) {
+    load_battc64_from(C, p);
     C.cap32 = pw(p, CLP_L_CAP); C.omd32 = pw(p, CLP_L_OMD); C.degk = pw(p, CLP_L_DEGK);
 }
+CL_DEV void load_battc(BattC& C, const uint32_t* __restrict__ p) { load_battc_from(C, p); }
 
 // 1 / sqrt(x) to ~2^-45: the fp32 seed (v_rsq_f32, 1 ulp) and one Newton step whose residual is a single fused multiply-add
 CL_DEV double rsq64(double x) {

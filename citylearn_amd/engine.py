@@ -25,6 +25,26 @@ REWARD_KINDS = {
 }
 
 
+def lean_district(tables: EpisodeTables) -> bool:
+    """`CLD_LEAN`: no building has a thermal device / tank, outage or dynamics flag, and no thermal demand anywhere in the tables."""
+    heavy = abi.CLF_THERMAL | abi.CLF_OUTAGE | abi.CLF_DYNAMICS
+    return not bool(np.any(tables.params[:, abi.CLP_FLAGS] & heavy)) and \
+        not bool(np.any(tables.ts[:, :, [abi.CLT_COOL_DEM, abi.CLT_HEAT_DEM, abi.CLT_DHW_DEM]]))
+
+
+def lean_uniform(tables: EpisodeTables, reward: str = 'RewardFunction') -> bool:
+    """`CLD_LEAN_UNIFORM` (include/citylearn_amd.h), from the host tables alone: a battery + PV district without flexible loads in which EVERY
+    building has a battery driven by action column = building index, under the default reward with exponent 1."""
+    if tables.flex is not None or REWARD_KINDS.get(reward) != abi.CLR_DEFAULT or not lean_district(tables):
+        return False
+    params = np.ascontiguousarray(tables.params)
+    n_bldg = params.shape[0]
+    all_batteries = bool(np.all(params.view(np.uint32)[:, abi.CLP_FLAGS] & abi.CLF_BATTERY))
+    in_order = np.array_equal(params.view(np.int32)[:, abi.CLP_ACT_ELEC_STO], np.arange(n_bldg))
+    exponent_one = bool(np.all(params.view(np.float32)[:, abi.CLP_L_RW_EXPONENT] == 1.0))
+    return all_batteries and in_order and exponent_one
+
+
 class _NullContext:
     def __enter__(self):
         return self
@@ -133,9 +153,7 @@ class StepEngine:
                 raise NotImplementedError("f64_maps='chain' needs battery curves with ascending breakpoints that end at 1 and power fractions <= 1 "
                                           "(the ramp form of the float64 chain); use f64_maps=True for this district")
         self.kpi = kpi
-        bflags = tables.params[:, abi.CLP_FLAGS]
-        heavy = abi.CLF_THERMAL | abi.CLF_OUTAGE | abi.CLF_DYNAMICS
-        self.lean = not bool(np.any(bflags & heavy)) and not bool(np.any(tables.ts[:, :, [abi.CLT_COOL_DEM, abi.CLT_HEAT_DEM, abi.CLT_DHW_DEM]]))
+        self.lean = lean_district(tables)
         flags |= abi.CLD_LEAN if self.lean else 0
         # the streaming KPI passes read the detail planes -- except for battery + PV districts of up to 32 buildings, whose step kernel
         # updates the per-building accumulators itself (cl_step_lean_kpi_kernel): no detail planes, no second pass
@@ -168,6 +186,8 @@ class StepEngine:
         es_cols = tables.params.view(np.int32)[:, abi.CLP_ACT_ELEC_STO]
         if np.array_equal(es_cols, np.arange(self.n_bldg)):          # one battery action per building, building order
             flags |= abi.CLD_ES_COL_IS_BLDG
+        if lean_uniform(tables, reward):                             # ... every one with a battery, default reward: the straight-line lean body
+            flags |= abi.CLD_LEAN_UNIFORM
         with torch.cuda.device(self.device):
             if env_row0 is not None:
                 self.env_row0 = torch.from_numpy(self.env_row0_host).to(self.device)

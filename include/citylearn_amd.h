@@ -326,6 +326,16 @@ enum cl_kpi_env {             /* kpi_env[cond*12 + k][env], cond 0 = control dis
                                          CLD_F64_CHAIN, every reward kind but CLR_EV, both action sources, env_row0 / env_offset.  Refused with the flag:
                                          flex != NULL, CLD_F64_MAPS; and with CLD_KPI also a district without CLD_LEAN, n_bldg > 32 (a building-chunked
                                          launch), CLD_WRITE_DETAIL, env_pitch != n_env.  `policy_actions` is not read on this path and may be NULL. */
+#define CLD_LEAN_UNIFORM   ((uint32_t)1 << 17) /* hint, cl_step_f32 (read by the plain battery + PV launch under CLD_F64_CHAIN, cl_step_lean_chain_kernel;
+                                         every other kernel and entry point ignores it).  Caller asserts ALL of: the district is CLD_LEAN; EVERY building has
+                                         CLF_BATTERY and an electrical_storage action column, and CLD_ES_COL_IS_BLDG holds (column of building b is b);
+                                         the reward kind is CLR_DEFAULT with RewardFunction.exponent == 1 for every building (CLP_L_RW_EXPONENT);
+                                         no flexible loads.  The launch then runs a straight-line body in which those district properties are
+                                         compile-time facts -- no battery-flag / action-column / reward-kind branches, no pow() -- with the same
+                                         arithmetic: identical bits.  Taken when the actions are env-contiguous (act_stride_env == 1); any other
+                                         action layout runs the generic body with the hint set.  (StepEngine derives it from the host tables:
+                                         engine.lean_uniform.  A hint next to the twelve mode bits above, not one of them: citylearn_amd/abi.py keeps
+                                         its parsed table of those as it is and mirrors this bit by hand, held against this line.) */
 enum cl_violation {
     CLV_FLEXIBILITY = 1,   /* downward_electrical_flexibility < 0 beyond TOLERANCE during a power outage (building.py:665) */
     CLV_COOLING     = 2,   /* ___electricity_consumption_polarity_check('cooling', ..): negative device consumption (building.py:1660, 1831-1835) */

@@ -47,6 +47,28 @@ hipError_t ensure_dynamic_lds(const void* fn, size_t bytes) {
     return hipSuccess;
 }
 
+// Two envs per lane of a fused rollout where its 128-env workgroups come in (nearly) full rounds of one per CU: 17 x 32 768 (the C5 per-GPU shard)
+// 2.60 -> 2.31 us per step, 65 536 4.99 -> 4.19, 98 304 7.24 -> 6.19, 131 072 9.54 -> 8.21; 49 152 = 1.5 rounds: 4.20 vs 3.89 at one env per lane
+// (scripts/rollout_vec_probe.py).  A building-chunked launch has env tiles x chunks workgroups; one workgroup row is n_chunks = 1, where
+// n_env >= 32 768 makes the last term true.  The ONE copy: cl_rollout_f32, the fused KPI rollout and the lean policy rollouts (cl_policy.h,
+// cl_policy_chunk.hip) all pick their envs per lane by it.
+inline bool full_rounds(int n_env, int n_chunks) {
+    const long long wg2 = (long long)((n_env + 127) / 128) * n_chunks, rounds2 = (wg2 + 255) / 256;
+    return (long long)n_env * n_chunks >= 32768 && wg2 * 100 >= rounds2 * 256 * 85 && n_env >= 128;
+}
+
+// out_bldg's reserved plane has room for what a building-chunked fused rollout parks there: n_chunks x NQ partial sums, one return row per chunk
+// and, at its tail, the marker words (and, in front of those, the ticket words of the one-step launches' in-launch fold: they stay zero between
+// launches).  cl_rollout_f32 and the three chunked policy entries refuse a geometry that does not fit -- in the same words, so the refusal is here too.
+inline bool chunk_partials_fit(int n_chunks, const cl_dims* dims) {
+    return ((long long)n_chunks * (CL_NQ + 1)) * dims->n_env + (dims->n_env + 63) / 64 + 4 <= (long long)dims->n_bldg * dims->n_env;
+}
+inline int check_chunk_partials(int b_chunk, int n_chunks, const cl_dims* dims) {
+    if (!chunk_partials_fit(n_chunks, dims))
+        return fail(CL_EINVAL, "b_chunk=%d leaves no room for the %d chunk partial sums of the fused rollout", b_chunk, n_chunks);
+    return CL_OK;
+}
+
 struct StepArgs {
     const uint32_t* __restrict__ params;
     const float* __restrict__ ts;
@@ -1366,6 +1388,18 @@ __global__ void __launch_bounds__(1024) cl_finish_kernel(const StepArgs a, const
         else ret_env[e] += t;
     }
 }
+
+// (host) The fold behind a building-chunked K-step launch -- the last step's district sums and, with `ret_env`, the K-step return: one launch of
+// NQ (+ 1) workgroup rows at step t_last.  cl_rollout_f32 and the three chunked policy entries each spelled this as `StepArgs f = a;
+// f.t = t0 + k_steps - 1; ...`; this is the one copy.
+inline int launch_rollout_finish(const cl_tuning& tun, const StepArgs& a, int t_last, float* ret_env, hipStream_t stream) {
+    StepArgs f = a;
+    f.t = t_last;
+    name_add(tun, "cl_finish_kernel");
+    hipLaunchKernelGGL(cl_finish_kernel, dim3((a.n_env + 63) / 64, NQ + (ret_env ? 1 : 0)), dim3(1024), 0, stream, f, 0, ret_env);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "cl_finish_kernel launch");
+    return CL_OK;
+}
 #endif  // cl_finish_kernel
 
 #if !defined(CL_TU_NOSLP) && !defined(CL_TU_POLICY_FULL)
@@ -2024,9 +2058,7 @@ static int rollout_fused(const cl_dims* dims, const uint32_t* params, const floa
     a.nw = tun.nw ? tun.nw : (dims->n_bldg + 1) / 2;
     // (nw > n_bldg: a wave without any building would read its parameter row -- row `w` -- past the end of the table)
     if (a.nw * 2 < dims->n_bldg || a.nw < 1 || a.nw > 16 || a.nw > dims->n_bldg) return fail(CL_EINVAL, "bad nw %d", a.nw);
-    const long long wg2 = (dims->n_env + 127) / 128, rounds2 = (wg2 + 255) / 256;
-    const bool full_rounds = dims->n_env >= 32768 && wg2 * 100 >= rounds2 * 256 * 85;
-    const int vec = tun.vec ? tun.vec : (((actions == nullptr || act_stride_env == 1) && full_rounds) ? 2 : 1);
+    const int vec = tun.vec ? tun.vec : (((actions == nullptr || act_stride_env == 1) && full_rounds(dims->n_env, 1)) ? 2 : 1);
     if (vec != 1 && vec != 2) return fail(CL_EINVAL, "no fused KPI rollout kernel at %d envs per lane", vec);
     const int tile = 64 * vec;
     const size_t lds = rollout_kpi_lds_floats(a.nw, tile) * sizeof(float);
@@ -2143,20 +2175,13 @@ int cl_rollout_f32(const cl_dims* dims, const uint32_t* params, const float* ts,
         if (a.b_chunk > 16 * mb_max) return fail(CL_EINVAL, "b_chunk=%d: a fused-rollout workgroup holds at most %d buildings of this district", a.b_chunk, 16 * mb_max);
         mb = mb_max;                      // (battery + PV: always two buildings per wave -- the one-building chunked instantiations spill)
         a.n_chunks = (dims->n_bldg + a.b_chunk - 1) / a.b_chunk;
-        // the reserved plane holds n_chunks x NQ partial sums, one return row per chunk and the marker words
-        // (and, in front of those, the ticket words of the one-step launches' in-launch fold: they stay zero between launches)
-        if (((long long)a.n_chunks * (NQ + 1)) * dims->n_env + (dims->n_env + 63) / 64 + 4 > (long long)dims->n_bldg * dims->n_env)
-            return fail(CL_EINVAL, "b_chunk=%d leaves no room for the %d chunk partial sums of the fused rollout", a.b_chunk, a.n_chunks);
+        if (int rc = check_chunk_partials(a.b_chunk, a.n_chunks, dims)) return rc;
     }
     a.nw = tun.nw ? tun.nw : ((chunked ? a.b_chunk : dims->n_bldg) + mb - 1) / mb;
     if (a.nw * mb < (chunked ? a.b_chunk : dims->n_bldg) || a.nw > 16) return fail(CL_EINVAL, "bad nw %d", a.nw);
-    // two envs per lane where its 128-env workgroups come in (nearly) full rounds of one per CU: 17 x 32 768 (the C5 per-GPU shard) 2.60 ->
-    // 2.31 us per step, 65 536 4.99 -> 4.19, 98 304 7.24 -> 6.19, 131 072 9.54 -> 8.21; 49 152 = 1.5 rounds: 4.20 vs 3.89 at one env per lane
-    // (scripts/rollout_vec_probe.py); chunked districts: the workgroup count is env tiles x chunks
-    const long long wg2 = (long long)((dims->n_env + 127) / 128) * a.n_chunks, rounds2 = (wg2 + 255) / 256;
-    const bool full_rounds = (long long)dims->n_env * a.n_chunks >= 32768 && wg2 * 100 >= rounds2 * 256 * 85 && dims->n_env >= 128;
+    // two envs per lane where the 128-env workgroups come in (nearly) full rounds of one per CU (full_rounds)
     const bool chain = dims->flags & CLD_F64_CHAIN;          // (the float64 soc chain: two envs per lane only where one workgroup row holds the district)
-    int vec = tun.vec ? tun.vec : ((!full && (actions == nullptr || act_stride_env == 1) && full_rounds) ? 2 : 1);
+    int vec = tun.vec ? tun.vec : ((!full && (actions == nullptr || act_stride_env == 1) && full_rounds(dims->n_env, a.n_chunks)) ? 2 : 1);
     if (chain && (full || vec > 2)) vec = 1;                 // (chunked battery + PV districts keep the two-env pack under the chain too: 1024 x 1024 / x 8192 127.6 -> 107.9 / 932.9 -> 798.9 us per 24 steps, profiles/r06z_*)
     const int tile = 64 * vec;
     const unsigned grid = (unsigned)((dims->n_env + tile - 1) / tile);
@@ -2196,14 +2221,8 @@ int cl_rollout_f32(const cl_dims* dims, const uint32_t* params, const float* ts,
     const int rc = cl_tu_launch_rollout(key + (chunked ? 1000 : 0) + (chain ? 2000 : 0), pin, grid, (unsigned)a.n_chunks, block.x, lds, stream, &r);
     if (rc) return hip_fail((hipError_t)rc, "cl_rollout_kernel launch");
     }
-    if (chunked && k_steps > 0) {
-        // the last step's district sums (and the K-step return): one fold per launch
-        StepArgs f = a;
-        f.t = t0 + k_steps - 1;
-        name_add(tun, "cl_finish_kernel");
-        hipLaunchKernelGGL(cl_finish_kernel, dim3((dims->n_env + 63) / 64, NQ + (ret_env ? 1 : 0)), dim3(1024), 0, (hipStream_t)stream, f, 0, ret_env);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "cl_finish_kernel launch");
-    }
+    // the last step's district sums (and the K-step return): one fold per launch
+    if (chunked && k_steps > 0) return launch_rollout_finish(tun, a, t0 + k_steps - 1, ret_env, (hipStream_t)stream);
     return CL_OK;
 }
 

@@ -289,22 +289,13 @@ __global__ void __launch_bounds__(1024) cl_rollout_policy_kernel(const PolicyArg
 }
 
 // ---- host: what clpol_rollout_mlp_f32 and clpk_rollout_mlp_kpi_f32 share beyond cl_policy_common.h ----
-int check_lean_policy_mlp(const clpol_mlp* mlp) {
-    if (!mlp) return fail(CL_ENULL, "mlp is NULL");
-    if (int rc = check_policy_sizes(*mlp, CLPOL_MAX_HIDDEN)) return rc;
-    if (mlp->flags || mlp->reserved) return fail(CL_EINVAL, "clpol_mlp.flags / .reserved must be 0");
-    return CL_OK;
-}
-
-// The lean rollout's geometry: two buildings per wave, two envs per lane where the 128-env workgroups come in (nearly) full rounds of one per CU
-// (`what`: "policy" or "policy KPI", for the refusal)
+// The one-row lean rollout's geometry: two buildings per wave, two envs per lane where the 128-env workgroups come in (nearly) full rounds of one
+// per CU (full_rounds, cl_kernels.hip).  `what`: "policy" or "policy KPI", for the refusal
 int lean_policy_geometry(const cl_dims* dims, const cl_tuning& tun, const char* what, int& nw, int& vec) {
     nw = tun.nw ? tun.nw : (dims->n_bldg + 1) / 2;
     // (nw > n_bldg: a wave without any building would read its parameter row -- row `w` -- past the end of the table)
     if (nw * 2 < dims->n_bldg || nw < 1 || nw > 16 || nw > dims->n_bldg) return fail(CL_EINVAL, "bad nw %d", nw);
-    const long long wg2 = (dims->n_env + 127) / 128, rounds2 = (wg2 + 255) / 256;
-    const bool full_rounds = dims->n_env >= 32768 && wg2 * 100 >= rounds2 * 256 * 85;
-    vec = tun.vec ? tun.vec : (full_rounds ? 2 : 1);
+    vec = tun.vec ? tun.vec : (full_rounds(dims->n_env, 1) ? 2 : 1);
     if (vec != 1 && vec != 2) return fail(CL_EINVAL, "no %s rollout kernel at %d envs per lane", what, vec);
     return CL_OK;
 }

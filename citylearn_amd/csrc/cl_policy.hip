@@ -28,27 +28,24 @@ int launch_policy(int vec, int prec, unsigned grid, unsigned block, size_t lds, 
 
 extern "C" {
 
-int clpol_abi_version(void) { return CLPOL_ABI_VERSION; }
-int clpol_core_abi_version(void) { return CL_ABI_VERSION; }
-const char* clpol_last_error(void) { return g_err; }
+CL_POLICY_ABI(clpol, CLPOL_ABI_VERSION)
 
 int clpol_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const float* ts, float* state, const clpol_mlp* mlp,
                           float* out_bldg, float* out_env, float* ret_env, float* traj, int32_t t0, int32_t k_steps, void* stream) {
+    const char* const entry = "clpol_rollout_mlp_f32";
     if (int rc = check_dims(dims, false)) return rc;
-    const uint32_t rk = (dims->flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT;
     // ---- what the kernel covers ----
     if (!(dims->flags & CLD_LEAN))
         return fail(CL_EINVAL, "clpol_rollout_mlp_f32: only battery + PV districts (CLD_LEAN); a thermal / outage district has no closed-loop rollout kernel");
     if (dims->n_bldg > 32)
         return fail(CL_EINVAL, "clpol_rollout_mlp_f32: n_bldg=%d > 32 would be a building-chunked launch, which the policy kernel is not: "
                                "clpc_rollout_mlp_f32 (libcitylearn_amd_policy_chunk.so)", dims->n_bldg);
-    if (dims->flags & CLD_F64_MAPS)
-        return fail(CL_EINVAL, "clpol_rollout_mlp_f32: the battery map in fp32 or as the float64 chain (CLD_F64_CHAIN), not CLD_F64_MAPS");
+    if (int rc = no_f64_maps(dims, entry)) return rc;
     if (dims->flags & CLD_KPI)
         return fail(CL_EINVAL, "clpol_rollout_mlp_f32: no streaming KPIs (CLD_KPI) inside this kernel -- record traj and replay CLPOL_T_ACTION through cl_rollout_seq_f32");
-    if (dims->flags & CLD_WRITE_DETAIL) return fail(CL_EINVAL, "clpol_rollout_mlp_f32: not with the detail planes (CLD_WRITE_DETAIL)");
-    if (rk == CLR_EV) return fail(CL_EINVAL, "clpol_rollout_mlp_f32: reward kind CLR_EV needs the flexible-load tables");
-    if (int rc = no_pitch(dims, "clpol_rollout_mlp_f32")) return rc;
+    if (int rc = no_detail_planes(dims, entry)) return rc;
+    if (int rc = no_reward_ev(dims, entry)) return rc;
+    if (int rc = no_pitch(dims, entry)) return rc;
     if (int rc = check_lean_policy_mlp(mlp)) return rc;
     const PolicyCall call = {params, ts, state, out_bldg, out_env, ret_env, traj, nullptr, nullptr, t0, k_steps};
     if (int rc = check_policy_buffers(dims, *mlp, call, false)) return rc;

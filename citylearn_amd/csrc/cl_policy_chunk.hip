@@ -1,7 +1,7 @@
 // cl_policy_chunk.hip -- the translation unit of libcitylearn_amd_policy_chunk.so (include/citylearn_amd_policy_chunk.h): cl_kernels.hip reduced as
 // for cl_policy.hip (CL_TU_NOSLP, CL_TU_POLICY) but WITH cl_finish_kernel (CL_TU_FINISH: the fold of the chunk partial sums, which a
-// building-chunked launch needs behind it), cl_policy.h for the staged-row layout and the lean policy's host checks (its kernel template is never
-// instantiated here), cl_policy_chunk.h's kernel, its launcher and the `clpc_*` entry points.  Compiled with -fno-slp-vectorize like cl_policy.hip.
+// building-chunked launch needs behind it), cl_policy.h for the staged-row layout (its kernel template is never instantiated here),
+// cl_policy_chunk.h's kernel, its launcher and the `clpc_*` entry points.  Compiled with -fno-slp-vectorize like cl_policy.hip.
 #define CL_TU_NOSLP
 #define CL_TU_POLICY
 #define CL_TU_FINISH
@@ -29,26 +29,22 @@ int launch_policy_chunk(int vec, int prec, dim3 grid, unsigned block, size_t lds
 
 extern "C" {
 
-int clpc_abi_version(void) { return CLPC_ABI_VERSION; }
-int clpc_core_abi_version(void) { return CL_ABI_VERSION; }
-const char* clpc_last_error(void) { return g_err; }
+CL_POLICY_ABI(clpc, CLPC_ABI_VERSION)
 
 int clpc_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const float* ts, float* state, const clpol_mlp* mlp,
                          float* out_bldg, float* out_env, float* ret_env, float* traj, int32_t t0, int32_t k_steps, void* stream) {
+    const char* const entry = "clpc_rollout_mlp_f32";
     if (int rc = check_dims(dims, false)) return rc;
-    const uint32_t rk = (dims->flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT;
     // ---- what the kernel covers ----
     if (!(dims->flags & CLD_LEAN))
         return fail(CL_EINVAL, "clpc_rollout_mlp_f32: only battery + PV districts (CLD_LEAN); a thermal / outage district of more than one workgroup row goes to "
                                "clpfc_rollout_mlp_f32 (libcitylearn_amd_policy_full_chunk.so)");
-    if (rk == CLR_MARL)
-        return fail(CL_EINVAL, "clpc_rollout_mlp_f32: reward kind CLR_MARL: a building-chunked launch cannot couple the buildings inside a step");
-    if (rk == CLR_EV) return fail(CL_EINVAL, "clpc_rollout_mlp_f32: reward kind CLR_EV needs the flexible-load tables");
-    if (dims->flags & CLD_F64_MAPS)
-        return fail(CL_EINVAL, "clpc_rollout_mlp_f32: the battery map in fp32 or as the float64 chain (CLD_F64_CHAIN), not CLD_F64_MAPS");
+    if (int rc = no_chunked_marl(dims, entry)) return rc;
+    if (int rc = no_reward_ev(dims, entry)) return rc;
+    if (int rc = no_f64_maps(dims, entry)) return rc;
     if (dims->flags & CLD_KPI) return fail(CL_EINVAL, "clpc_rollout_mlp_f32: no streaming KPIs (CLD_KPI) inside a building-chunked policy launch");
-    if (dims->flags & CLD_WRITE_DETAIL) return fail(CL_EINVAL, "clpc_rollout_mlp_f32: not with the detail planes (CLD_WRITE_DETAIL)");
-    if (int rc = no_pitch(dims, "clpc_rollout_mlp_f32")) return rc;
+    if (int rc = no_detail_planes(dims, entry)) return rc;
+    if (int rc = no_pitch(dims, entry)) return rc;
     if (int rc = check_lean_policy_mlp(mlp)) return rc;
     const PolicyCall call = {params, ts, state, out_bldg, out_env, ret_env, traj, nullptr, nullptr, t0, k_steps};
     if (int rc = check_policy_buffers(dims, *mlp, call, false)) return rc;
@@ -57,22 +53,9 @@ int clpc_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const floa
     PolicyArgs p;
     fill_policy_args(p, dims, *mlp, CLPOL_NOISE_KEY, call);
     StepArgs& a = p.r.s;
-    // ---- the chunk geometry: TWO buildings per wave, b_chunk buildings per workgroup row, n_chunks rows along gridDim.y.  Default: the blind
-    // chunked lean rollout's 32-building workgroups (cl_rollout_f32), balanced over the chunks
-    if (tun.b_chunk < 0) return fail(CL_EINVAL, "b_chunk=%d", tun.b_chunk);
-    if (tun.b_chunk > 32) return fail(CL_EINVAL, "b_chunk=%d: a policy rollout workgroup holds at most 32 buildings (two per wave)", tun.b_chunk);
-    if (tun.b_chunk == 0 && dims->n_bldg <= 32)
-        return fail(CL_EINVAL, "clpc_rollout_mlp_f32: n_bldg=%d fits one workgroup row, which is clpol_rollout_mlp_f32's launch (libcitylearn_amd_policy.so); "
-                               "a chunked launch of it takes an explicit cl_tuning.b_chunk < n_bldg", dims->n_bldg);
-    if (tun.b_chunk >= dims->n_bldg)
-        return fail(CL_EINVAL, "b_chunk=%d >= n_bldg=%d: one workgroup row is clpol_rollout_mlp_f32's launch (libcitylearn_amd_policy.so)", tun.b_chunk, dims->n_bldg);
-    if (tun.b_chunk > 0) {
-        a.b_chunk = tun.b_chunk;
-    } else {
-        const int nc = (dims->n_bldg + 31) / 32;
-        a.b_chunk = (dims->n_bldg + nc - 1) / nc;
-    }
-    a.n_chunks = (dims->n_bldg + a.b_chunk - 1) / a.b_chunk;
+    // ---- the chunk geometry: TWO buildings per wave
+    const ChunkRule rule = {2, entry, "clpol_rollout_mlp_f32", "libcitylearn_amd_policy.so"};
+    if (int rc = policy_chunk_geometry(dims, tun, rule, a.b_chunk, a.n_chunks)) return rc;
     a.nw = tun.nw ? tun.nw : (a.b_chunk + 1) / 2;
     // (nw > b_chunk: waves that no chunk ever fills)
     if (a.nw * 2 < a.b_chunk || a.nw < 1 || a.nw > 16 || a.nw > a.b_chunk)
@@ -80,13 +63,9 @@ int clpc_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const floa
                     (a.b_chunk + 1) / 2, a.b_chunk < 16 ? a.b_chunk : 16);
     // envs per lane: the blind chunked rollout's rule (cl_rollout_f32) -- two where the 128-env workgroups come in (nearly) full rounds of one per
     // CU over env tiles x chunks; under the float64 chain too (the blind chunked lean kernel keeps the two-env pack there)
-    const long long wg2 = (long long)((dims->n_env + 127) / 128) * a.n_chunks, rounds2 = (wg2 + 255) / 256;
-    const bool full_rounds = (long long)dims->n_env * a.n_chunks >= 32768 && wg2 * 100 >= rounds2 * 256 * 85 && dims->n_env >= 128;
     if (tun.vec != 0 && tun.vec != 1 && tun.vec != 2) return fail(CL_EINVAL, "no chunked policy rollout kernel at %d envs per lane", tun.vec);
-    const int vec = tun.vec ? tun.vec : (full_rounds ? 2 : 1);
-    // the reserved plane holds n_chunks x NQ partial sums, one return row per chunk and, at its tail, the ticket and marker words of the step launches
-    if (((long long)a.n_chunks * (NQ + 1)) * dims->n_env + (dims->n_env + 63) / 64 + 4 > (long long)dims->n_bldg * dims->n_env)
-        return fail(CL_EINVAL, "b_chunk=%d leaves no room for the %d chunk partial sums of the fused rollout", a.b_chunk, a.n_chunks);
+    const int vec = tun.vec ? tun.vec : (full_rounds(dims->n_env, a.n_chunks) ? 2 : 1);
+    if (int rc = check_chunk_partials(a.b_chunk, a.n_chunks, dims)) return rc;
     const int tile = 64 * vec;
     const size_t lds = rollout_policy_chunk_lds_floats(a.nw, tile) * sizeof(float);
     if (int rc = check_policy_lds(lds, "chunked policy", a.nw, vec)) return rc;
@@ -96,14 +75,8 @@ int clpc_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const floa
     const dim3 grid((unsigned)((dims->n_env + tile - 1) / tile), (unsigned)a.n_chunks);
     const int rc = launch_policy_chunk(vec, prec, grid, 64u * a.nw, lds, (hipStream_t)stream, p);
     if (rc) return hip_fail((hipError_t)rc, "cl_rollout_policy_chunk_kernel launch");
-    if (k_steps > 0) {
-        // the last step's district sums (and the K-step return): one fold per launch, as behind a chunked cl_rollout_f32
-        StepArgs f = a;
-        f.t = t0 + k_steps - 1;
-        name_add(tun, "cl_finish_kernel");
-        hipLaunchKernelGGL(cl_finish_kernel, dim3((dims->n_env + 63) / 64, NQ + (ret_env ? 1 : 0)), dim3(1024), 0, (hipStream_t)stream, f, 0, ret_env);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "cl_finish_kernel launch");
-    }
+    // the last step's district sums (and the K-step return): one fold per launch, as behind a chunked cl_rollout_f32
+    if (k_steps > 0) return launch_rollout_finish(tun, a, t0 + k_steps - 1, ret_env, (hipStream_t)stream);
     return CL_OK;
 }
 

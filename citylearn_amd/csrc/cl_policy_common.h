@@ -1,8 +1,19 @@
-// cl_policy_common.h -- what the three closed-loop policy units share (cl_policy.hip, cl_policy_kpi.hip, cl_policy_full.hip; each behind
-// cl_kernels.hip's helpers and cl_rollout.h): the kernels' argument struct, the hidden unit's activation and the Box-Muller draw on the device; the
-// argument checks, the argument fill and the launch macro on the host.  The ONE copy of each.  The larger pieces of a step that the kernels have in
-// common (row staging, the action, the record, the write-back, the return reduction) stay written out in each kernel: as functions they change the
-// generated code of the instantiations that call them (profiles/policy_refactor_isa.md).
+// cl_policy_common.h -- what the seven closed-loop policy units share (cl_policy.hip, cl_policy_kpi.hip, cl_policy_chunk.hip for battery + PV
+// districts; cl_policy_full.hip, cl_policy_full_kpi.hip, cl_policy_full_chunk.hip, cl_policy_full_chunk_kpi.hip for thermal ones; each behind
+// cl_kernels.hip's helpers and cl_rollout.h).  The ONE copy of each:
+//   device  PolicyArgs, the hidden unit's activation (clpol_unit), the Box-Muller draw (clpol_gauss);
+//   host    the three entry points every library exports besides its rollout (CL_POLICY_ABI);
+//           the coverage refusals whose text is the same up to the entry's name (no_f64_maps, no_reward_ev, no_chunked_marl, no_detail_planes,
+//           detail_min_only) -- an entry calls them in ITS order, which is behaviour (tests/test_policy_refusals_host.py pins which one wins);
+//           the mlp struct's checks (check_policy_sizes, check_lean_policy_mlp, check_thermal_policy_mlp) and the buffers' (check_policy_buffers);
+//           the argument fill (fill_policy_args);
+//           the geometry rules: policy_chunk_geometry (b_chunk / n_chunks of a building-chunked launch), thermal_one_row_geometry,
+//           one_env_per_lane_only, check_policy_lds -- cl_kernels.hip holds the ones the blind rollouts use too: full_rounds,
+//           chunk_partials_fit / check_chunk_partials, launch_rollout_finish;
+//           the launch macro (CL_POLICY_LAUNCH).
+// What is an entry's own stays written out in it: the CLD_LEAN and CLD_KPI redirects, n_bldg > 16 / 32, its nw and envs-per-lane lines, its launcher.
+// The larger pieces of a step that the kernels have in common (row staging, the action, the record, the write-back, the return reduction) stay
+// written out in each kernel: as functions they change the generated code of the instantiations that call them (profiles/policy_refactor_isa.md).
 #pragma once
 
 #ifdef __HIPCC__
@@ -41,7 +52,32 @@ CL_DEV float clpol_gauss(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, int
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
-// The buffers of one call, as the three entry points receive them (kpi_bldg / kpi_env: NULL except for the KPI kernel)
+// <prefix>_abi_version, <prefix>_core_abi_version, <prefix>_last_error (inside the unit's extern "C" block)
+#define CL_POLICY_ABI(prefix, version) \
+    int prefix##_abi_version(void) { return version; } \
+    int prefix##_core_abi_version(void) { return CL_ABI_VERSION; } \
+    const char* prefix##_last_error(void) { return g_err; }
+
+// ---- what a kernel covers: the refusals that read the same in every entry (`entry`: its name) ----
+inline uint32_t reward_kind(const cl_dims* dims) { return (dims->flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT; }
+inline int no_f64_maps(const cl_dims* dims, const char* entry) {
+    return (dims->flags & CLD_F64_MAPS) ? fail(CL_EINVAL, "%s: the battery map in fp32 or as the float64 chain (CLD_F64_CHAIN), not CLD_F64_MAPS", entry) : CL_OK;
+}
+inline int no_reward_ev(const cl_dims* dims, const char* entry) {
+    return reward_kind(dims) == CLR_EV ? fail(CL_EINVAL, "%s: reward kind CLR_EV needs the flexible-load tables", entry) : CL_OK;
+}
+inline int no_chunked_marl(const cl_dims* dims, const char* entry) {
+    return reward_kind(dims) == CLR_MARL ? fail(CL_EINVAL, "%s: reward kind CLR_MARL: a building-chunked launch cannot couple the buildings inside a step", entry) : CL_OK;
+}
+inline int no_detail_planes(const cl_dims* dims, const char* entry) {
+    return (dims->flags & CLD_WRITE_DETAIL) ? fail(CL_EINVAL, "%s: not with the detail planes (CLD_WRITE_DETAIL)", entry) : CL_OK;
+}
+inline int detail_min_only(const cl_dims* dims, const char* entry) {
+    const bool all = (dims->flags & CLD_WRITE_DETAIL) && !(dims->flags & CLD_DETAIL_MIN);
+    return all ? fail(CL_EINVAL, "%s: of the detail planes (CLD_WRITE_DETAIL) only the subset of CLD_DETAIL_MIN is written", entry) : CL_OK;
+}
+
+// The buffers of one call, as the entry points receive them (kpi_bldg / kpi_env: NULL except for the KPI kernels)
 struct PolicyCall {
     const uint32_t* params; const float* ts; float* state; float* out_bldg; float* out_env; float* ret_env; float* traj;
     float* kpi_bldg; float* kpi_env;
@@ -56,6 +92,29 @@ int check_policy_sizes(const MLP& mlp, int max_hidden) {
     if (mlp.n_sets < 1) return fail(CL_EINVAL, "n_sets=%d: at least one parameter set", mlp.n_sets);
     return CL_OK;
 }
+
+// the struct of a battery + PV policy (the three lean units) and of a thermal one (the four thermal units, with the action-column count that the
+// kernels' 16-bit column ids admit); each where the unit has included the public header that declares the struct
+#ifdef CITYLEARN_AMD_POLICY_H
+inline int check_lean_policy_mlp(const clpol_mlp* mlp) {
+    if (!mlp) return fail(CL_ENULL, "mlp is NULL");
+    if (int rc = check_policy_sizes(*mlp, CLPOL_MAX_HIDDEN)) return rc;
+    if (mlp->flags || mlp->reserved) return fail(CL_EINVAL, "clpol_mlp.flags / .reserved must be 0");
+    return CL_OK;
+}
+#endif
+#ifdef CITYLEARN_AMD_POLICY_FULL_H
+inline int check_thermal_policy_mlp(const char* entry, const cl_dims* dims, const clpf_mlp* mlp) {
+    if (dims->n_act_cols > 65536) return fail(CL_EINVAL, "%s: n_act_cols=%d > 65536", entry, dims->n_act_cols);
+    if (!mlp) return fail(CL_ENULL, "mlp is NULL");
+    if (mlp->n_device_cols != 0)
+        return fail(CL_EINVAL, "%s: n_device_cols=%d: a building with a cooling / heating / combined device action column is not covered "
+                               "(the policy has storage heads only)", entry, mlp->n_device_cols);
+    if (int rc = check_policy_sizes(*mlp, CLPF_MAX_HIDDEN)) return rc;
+    if (mlp->reserved) return fail(CL_EINVAL, "clpf_mlp.reserved must be 0");
+    return CL_OK;
+}
+#endif
 
 // every pointer of the call and of the policy's tables, then the step range (`kpi`: the call takes the KPI planes)
 template <class MLP>
@@ -102,7 +161,52 @@ void fill_policy_args(PolicyArgs& p, const cl_dims* dims, const MLP& mlp, uint64
     p.traj = c.traj; p.n_rows = dims->n_ts_rows ? dims->n_ts_rows : dims->n_steps; p.n_hidden = mlp.n_hidden;
 }
 
-// the workgroup's dynamic LDS against what a CU has (`what`: "policy", "policy KPI", "thermal policy")
+// ---- geometry ----
+// A building-chunked launch: b_chunk buildings per workgroup row, n_chunks rows along gridDim.y.  `per_wave` buildings a wave (2: battery + PV,
+// 1: thermal), so a row holds at most 16 x per_wave; the default is the blind chunked rollout's (cl_rollout_f32) -- 32-building rows for battery +
+// PV, EIGHT for the packed thermal kernel (two or three workgroups per CU instead of one of sixteen waves) -- BALANCED over the chunks.  A district
+// that fits one row is `one_row`'s launch (in `one_row_lib`) unless the caller asks for chunks.  The waves per row and the room in the reserved
+// plane (check_chunk_partials) are the entry's own lines: the entries check them at different points.
+struct ChunkRule { int per_wave; const char* entry; const char* one_row; const char* one_row_lib; };
+inline int policy_chunk_geometry(const cl_dims* dims, const cl_tuning& tun, const ChunkRule& rule, int& b_chunk, int& n_chunks) {
+    const bool pair = rule.per_wave == 2;
+    const int b_max = 16 * rule.per_wave, b_default = pair ? 32 : 8;
+    if (tun.b_chunk < 0) return fail(CL_EINVAL, "b_chunk=%d", tun.b_chunk);
+    if (tun.b_chunk > b_max)
+        return fail(CL_EINVAL, "b_chunk=%d: a %spolicy rollout workgroup holds at most %d buildings (%s per wave)", tun.b_chunk, pair ? "" : "thermal ", b_max,
+                    pair ? "two" : "one");
+    if (tun.b_chunk == 0 && dims->n_bldg <= b_max)
+        return fail(CL_EINVAL, "%s: n_bldg=%d fits one workgroup row, which is %s's launch (%s); a chunked launch of it takes an explicit cl_tuning.b_chunk < n_bldg",
+                    rule.entry, dims->n_bldg, rule.one_row, rule.one_row_lib);
+    if (tun.b_chunk >= dims->n_bldg)
+        return fail(CL_EINVAL, "b_chunk=%d >= n_bldg=%d: one workgroup row is %s's launch (%s)", tun.b_chunk, dims->n_bldg, rule.one_row, rule.one_row_lib);
+    if (tun.b_chunk > 0) {
+        b_chunk = tun.b_chunk;
+    } else {
+        const int nc = (dims->n_bldg + b_default - 1) / b_default;
+        b_chunk = (dims->n_bldg + nc - 1) / nc;
+    }
+    n_chunks = (dims->n_bldg + b_chunk - 1) / b_chunk;
+    return CL_OK;
+}
+
+// The one-row thermal rollouts: ONE building per wave, the whole district in one workgroup row -- so nw is n_bldg and nothing else (nw > n_bldg: a
+// wave without a building would read parameter row `w` past the end of the table; nw < n_bldg would leave buildings out).  `what` as below.
+inline int thermal_one_row_geometry(const cl_dims* dims, const cl_tuning& tun, const char* what, int& nw) {
+    nw = tun.nw ? tun.nw : dims->n_bldg;
+    if (nw > 16 || nw > dims->n_bldg || nw < dims->n_bldg)
+        return fail(CL_EINVAL, "bad nw %d: the %s rollout runs one building per wave (nw = n_bldg = %d, at most 16)", nw, what, dims->n_bldg);
+    return CL_OK;
+}
+
+// the thermal KPI kernels have no instantiation at two envs per lane (`what`: "thermal policy KPI", "chunked thermal policy KPI")
+inline int one_env_per_lane_only(const cl_tuning& tun, const char* what) {
+    if (tun.vec == 2) return fail(CL_EINVAL, "no %s rollout kernel at 2 envs per lane: it runs at one env per lane", what);
+    if (tun.vec != 0 && tun.vec != 1) return fail(CL_EINVAL, "no %s rollout kernel at %d envs per lane", what, tun.vec);
+    return CL_OK;
+}
+
+// the workgroup's dynamic LDS against what a CU has (`what`: "policy", "policy KPI", "thermal policy", ...)
 int check_policy_lds(size_t lds, const char* what, int nw, int vec) {
     if (lds > CL_LDS_PER_CU) return fail(CL_EINVAL, "the %s rollout would need %zu bytes of LDS per workgroup (nw=%d, %d envs per lane): a CU has %d", what, lds, nw, vec, CL_LDS_PER_CU);
     return CL_OK;

@@ -29,32 +29,23 @@ int launch_policy_full(int vec, int prec, bool marl, unsigned grid, unsigned blo
 
 extern "C" {
 
-int clpf_abi_version(void) { return CLPF_ABI_VERSION; }
-int clpf_core_abi_version(void) { return CL_ABI_VERSION; }
-const char* clpf_last_error(void) { return g_err; }
+CL_POLICY_ABI(clpf, CLPF_ABI_VERSION)
 
 int clpf_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const float* ts, float* state, const clpf_mlp* mlp,
                          float* out_bldg, float* out_env, float* ret_env, float* traj, int32_t t0, int32_t k_steps, void* stream) {
+    const char* const entry = "clpf_rollout_mlp_f32";
     if (int rc = check_dims(dims, false)) return rc;
-    const uint32_t rk = (dims->flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT;
     // ---- what the kernel covers ----
     if (dims->flags & CLD_LEAN)
         return fail(CL_EINVAL, "clpf_rollout_mlp_f32: thermal / outage districts only; a battery + PV district (CLD_LEAN) goes to clpol_rollout_mlp_f32 (libcitylearn_amd_policy.so)");
     if (dims->n_bldg > 16)
         return fail(CL_EINVAL, "clpf_rollout_mlp_f32: n_bldg=%d > 16 would be a building-chunked launch, which the policy kernel is not", dims->n_bldg);
-    if (dims->flags & CLD_F64_MAPS)
-        return fail(CL_EINVAL, "clpf_rollout_mlp_f32: the battery map in fp32 or as the float64 chain (CLD_F64_CHAIN), not CLD_F64_MAPS");
+    if (int rc = no_f64_maps(dims, entry)) return rc;
     if (dims->flags & CLD_KPI) return fail(CL_EINVAL, "clpf_rollout_mlp_f32: no streaming KPIs (CLD_KPI) inside this kernel");
-    if (dims->flags & CLD_WRITE_DETAIL) return fail(CL_EINVAL, "clpf_rollout_mlp_f32: not with the detail planes (CLD_WRITE_DETAIL)");
-    if (rk == CLR_EV) return fail(CL_EINVAL, "clpf_rollout_mlp_f32: reward kind CLR_EV needs the flexible-load tables");
-    if (int rc = no_pitch(dims, "clpf_rollout_mlp_f32")) return rc;
-    if (dims->n_act_cols > 65536) return fail(CL_EINVAL, "clpf_rollout_mlp_f32: n_act_cols=%d > 65536", dims->n_act_cols);
-    if (!mlp) return fail(CL_ENULL, "mlp is NULL");
-    if (mlp->n_device_cols != 0)
-        return fail(CL_EINVAL, "clpf_rollout_mlp_f32: n_device_cols=%d: a building with a cooling / heating / combined device action column is not covered "
-                               "(the policy has storage heads only)", mlp->n_device_cols);
-    if (int rc = check_policy_sizes(*mlp, CLPF_MAX_HIDDEN)) return rc;
-    if (mlp->reserved) return fail(CL_EINVAL, "clpf_mlp.reserved must be 0");
+    if (int rc = no_detail_planes(dims, entry)) return rc;
+    if (int rc = no_reward_ev(dims, entry)) return rc;
+    if (int rc = no_pitch(dims, entry)) return rc;
+    if (int rc = check_thermal_policy_mlp(entry, dims, mlp)) return rc;
     const PolicyCall call = {params, ts, state, out_bldg, out_env, ret_env, traj, nullptr, nullptr, t0, k_steps};
     if (int rc = check_policy_buffers(dims, *mlp, call, false)) return rc;
 
@@ -62,12 +53,8 @@ int clpf_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const floa
     PolicyArgs p;
     fill_policy_args(p, dims, *mlp, CLPF_NOISE_KEY, call);
     StepArgs& a = p.r.s;
-    // the packed thermal rollout's geometry: ONE building per wave, the whole district in one workgroup row -- so nw is n_bldg and nothing else
-    // (nw > n_bldg: a wave without a building would read parameter row `w` past the end of the table; nw < n_bldg would leave buildings out)
-    a.nw = tun.nw ? tun.nw : dims->n_bldg;
-    if (a.nw > 16 || a.nw > dims->n_bldg || a.nw < dims->n_bldg)
-        return fail(CL_EINVAL, "bad nw %d: the thermal policy rollout runs one building per wave (nw = n_bldg = %d, at most 16)", a.nw, dims->n_bldg);
-    const bool chain = dims->flags & CLD_F64_CHAIN, marl = rk == CLR_MARL;
+    if (int rc = thermal_one_row_geometry(dims, tun, "thermal policy", a.nw)) return rc;
+    const bool chain = dims->flags & CLD_F64_CHAIN, marl = reward_kind(dims) == CLR_MARL;
     if (tun.vec != 0 && tun.vec != 1 && tun.vec != 2) return fail(CL_EINVAL, "no thermal policy rollout kernel at %d envs per lane", tun.vec);
     if (tun.vec == 2 && (chain || marl))
         return fail(CL_EINVAL, "no thermal policy rollout kernel at 2 envs per lane under %s: it runs at one env per lane", chain ? "CLD_F64_CHAIN" : "CLR_MARL");

@@ -29,32 +29,22 @@ int launch_policy_full_chunk(int vec, int prec, dim3 grid, unsigned block, size_
 
 extern "C" {
 
-int clpfc_abi_version(void) { return CLPFC_ABI_VERSION; }
-int clpfc_core_abi_version(void) { return CL_ABI_VERSION; }
-const char* clpfc_last_error(void) { return g_err; }
+CL_POLICY_ABI(clpfc, CLPFC_ABI_VERSION)
 
 int clpfc_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const float* ts, float* state, const clpf_mlp* mlp,
                           float* out_bldg, float* out_env, float* ret_env, float* traj, int32_t t0, int32_t k_steps, void* stream) {
+    const char* const entry = "clpfc_rollout_mlp_f32";
     if (int rc = check_dims(dims, false)) return rc;
-    const uint32_t rk = (dims->flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT;
     // ---- what the kernel covers ----
     if (dims->flags & CLD_LEAN)
         return fail(CL_EINVAL, "clpfc_rollout_mlp_f32: thermal / outage districts only; a battery + PV district (CLD_LEAN) goes to clpol_rollout_mlp_f32 (libcitylearn_amd_policy.so)");
-    if (rk == CLR_MARL)
-        return fail(CL_EINVAL, "clpfc_rollout_mlp_f32: reward kind CLR_MARL: a building-chunked launch cannot couple the buildings inside a step");
-    if (rk == CLR_EV) return fail(CL_EINVAL, "clpfc_rollout_mlp_f32: reward kind CLR_EV needs the flexible-load tables");
-    if (dims->flags & CLD_F64_MAPS)
-        return fail(CL_EINVAL, "clpfc_rollout_mlp_f32: the battery map in fp32 or as the float64 chain (CLD_F64_CHAIN), not CLD_F64_MAPS");
+    if (int rc = no_chunked_marl(dims, entry)) return rc;
+    if (int rc = no_reward_ev(dims, entry)) return rc;
+    if (int rc = no_f64_maps(dims, entry)) return rc;
     if (dims->flags & CLD_KPI) return fail(CL_EINVAL, "clpfc_rollout_mlp_f32: no streaming KPIs (CLD_KPI) inside a building-chunked policy launch");
-    if (dims->flags & CLD_WRITE_DETAIL) return fail(CL_EINVAL, "clpfc_rollout_mlp_f32: not with the detail planes (CLD_WRITE_DETAIL)");
-    if (int rc = no_pitch(dims, "clpfc_rollout_mlp_f32")) return rc;
-    if (dims->n_act_cols > 65536) return fail(CL_EINVAL, "clpfc_rollout_mlp_f32: n_act_cols=%d > 65536", dims->n_act_cols);
-    if (!mlp) return fail(CL_ENULL, "mlp is NULL");
-    if (mlp->n_device_cols != 0)
-        return fail(CL_EINVAL, "clpfc_rollout_mlp_f32: n_device_cols=%d: a building with a cooling / heating / combined device action column is not covered "
-                               "(the policy has storage heads only)", mlp->n_device_cols);
-    if (int rc = check_policy_sizes(*mlp, CLPF_MAX_HIDDEN)) return rc;
-    if (mlp->reserved) return fail(CL_EINVAL, "clpf_mlp.reserved must be 0");
+    if (int rc = no_detail_planes(dims, entry)) return rc;
+    if (int rc = no_pitch(dims, entry)) return rc;
+    if (int rc = check_thermal_policy_mlp(entry, dims, mlp)) return rc;
     const PolicyCall call = {params, ts, state, out_bldg, out_env, ret_env, traj, nullptr, nullptr, t0, k_steps};
     if (int rc = check_policy_buffers(dims, *mlp, call, false)) return rc;
 
@@ -62,28 +52,13 @@ int clpfc_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const flo
     PolicyArgs p;
     fill_policy_args(p, dims, *mlp, CLPF_NOISE_KEY, call);
     StepArgs& a = p.r.s;
-    // ---- the chunk geometry: ONE building per wave, b_chunk buildings = waves per workgroup row, n_chunks rows along gridDim.y.  Default: balanced
-    // chunks of at most EIGHT (what the blind packed kernel runs its chunked launches at: two or three workgroups per CU instead of one of sixteen waves)
-    if (tun.b_chunk < 0) return fail(CL_EINVAL, "b_chunk=%d", tun.b_chunk);
-    if (tun.b_chunk > 16) return fail(CL_EINVAL, "b_chunk=%d: a thermal policy rollout workgroup holds at most 16 buildings (one per wave)", tun.b_chunk);
-    if (tun.b_chunk == 0 && dims->n_bldg <= 16)
-        return fail(CL_EINVAL, "clpfc_rollout_mlp_f32: n_bldg=%d fits one workgroup row, which is clpf_rollout_mlp_f32's launch (libcitylearn_amd_policy_full.so); "
-                               "a chunked launch of it takes an explicit cl_tuning.b_chunk < n_bldg", dims->n_bldg);
-    if (tun.b_chunk >= dims->n_bldg)
-        return fail(CL_EINVAL, "b_chunk=%d >= n_bldg=%d: one workgroup row is clpf_rollout_mlp_f32's launch (libcitylearn_amd_policy_full.so)", tun.b_chunk, dims->n_bldg);
-    if (tun.b_chunk > 0) {
-        a.b_chunk = tun.b_chunk;
-    } else {
-        const int nc = (dims->n_bldg + 7) / 8;
-        a.b_chunk = (dims->n_bldg + nc - 1) / nc;
-    }
-    a.n_chunks = (dims->n_bldg + a.b_chunk - 1) / a.b_chunk;
+    // ---- the chunk geometry: ONE building per wave, so b_chunk buildings = waves per workgroup row
+    const ChunkRule rule = {1, entry, "clpf_rollout_mlp_f32", "libcitylearn_amd_policy_full.so"};
+    if (int rc = policy_chunk_geometry(dims, tun, rule, a.b_chunk, a.n_chunks)) return rc;
     if (tun.nw != 0 && tun.nw != a.b_chunk)
         return fail(CL_EINVAL, "bad nw %d: the chunked thermal policy rollout runs one building per wave (nw = b_chunk = %d)", tun.nw, a.b_chunk);
     a.nw = a.b_chunk;
-    // the reserved plane holds n_chunks x NQ partial sums, one return row per chunk and, at its tail, the ticket and marker words of the step launches
-    if (((long long)a.n_chunks * (NQ + 1)) * dims->n_env + (dims->n_env + 63) / 64 + 4 > (long long)dims->n_bldg * dims->n_env)
-        return fail(CL_EINVAL, "b_chunk=%d leaves no room for the %d chunk partial sums of the fused rollout", a.b_chunk, a.n_chunks);
+    if (int rc = check_chunk_partials(a.b_chunk, a.n_chunks, dims)) return rc;
     const bool chain = dims->flags & CLD_F64_CHAIN;
     if (tun.vec != 0 && tun.vec != 1 && tun.vec != 2) return fail(CL_EINVAL, "no chunked thermal policy rollout kernel at %d envs per lane", tun.vec);
     if (tun.vec == 2 && chain)
@@ -98,14 +73,8 @@ int clpfc_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const flo
     const dim3 grid((unsigned)((dims->n_env + tile - 1) / tile), (unsigned)a.n_chunks);
     const int rc = launch_policy_full_chunk(vec, prec, grid, 64u * a.nw, lds, (hipStream_t)stream, p);
     if (rc) return hip_fail((hipError_t)rc, "cl_rollout_full_policy_chunk_kernel launch");
-    if (k_steps > 0) {
-        // the last step's district sums (and the K-step return): one fold per launch, as behind a chunked cl_rollout_f32
-        StepArgs f = a;
-        f.t = t0 + k_steps - 1;
-        name_add(tun, "cl_finish_kernel");
-        hipLaunchKernelGGL(cl_finish_kernel, dim3((dims->n_env + 63) / 64, NQ + (ret_env ? 1 : 0)), dim3(1024), 0, (hipStream_t)stream, f, 0, ret_env);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "cl_finish_kernel launch");
-    }
+    // the last step's district sums (and the K-step return): one fold per launch, as behind a chunked cl_rollout_f32
+    if (k_steps > 0) return launch_rollout_finish(tun, a, t0 + k_steps - 1, ret_env, (hipStream_t)stream);
     return CL_OK;
 }
 

@@ -30,15 +30,13 @@ int launch_policy_full_kpi(int prec, bool marl, unsigned grid, unsigned block, s
 
 extern "C" {
 
-int clpfk_abi_version(void) { return CLPFK_ABI_VERSION; }
-int clpfk_core_abi_version(void) { return CL_ABI_VERSION; }
-const char* clpfk_last_error(void) { return g_err; }
+CL_POLICY_ABI(clpfk, CLPFK_ABI_VERSION)
 
 int clpfk_rollout_mlp_kpi_f32(const cl_dims* dims, const uint32_t* params, const float* ts, float* state, const clpf_mlp* mlp,
                               float* out_bldg, float* out_env, float* ret_env, float* traj, float* kpi_bldg, float* kpi_env,
                               int32_t t0, int32_t k_steps, void* stream) {
+    const char* const entry = "clpfk_rollout_mlp_kpi_f32";
     if (int rc = check_dims(dims, false)) return rc;
-    const uint32_t rk = (dims->flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT;
     // ---- what the kernel covers ----
     if (dims->flags & CLD_LEAN)
         return fail(CL_EINVAL, "clpfk_rollout_mlp_kpi_f32: thermal / outage districts only; a battery + PV district (CLD_LEAN) goes to clpk_rollout_mlp_kpi_f32 (libcitylearn_amd_policy_kpi.so)");
@@ -46,19 +44,11 @@ int clpfk_rollout_mlp_kpi_f32(const cl_dims* dims, const uint32_t* params, const
         return fail(CL_EINVAL, "clpfk_rollout_mlp_kpi_f32: the district must keep the streaming KPIs (CLD_KPI); without them the call is clpf_rollout_mlp_f32");
     if (dims->n_bldg > 16)
         return fail(CL_EINVAL, "clpfk_rollout_mlp_kpi_f32: n_bldg=%d > 16 would be a building-chunked launch, which the policy KPI kernel is not", dims->n_bldg);
-    if (dims->flags & CLD_F64_MAPS)
-        return fail(CL_EINVAL, "clpfk_rollout_mlp_kpi_f32: the battery map in fp32 or as the float64 chain (CLD_F64_CHAIN), not CLD_F64_MAPS");
-    if ((dims->flags & CLD_WRITE_DETAIL) && !(dims->flags & CLD_DETAIL_MIN))
-        return fail(CL_EINVAL, "clpfk_rollout_mlp_kpi_f32: of the detail planes (CLD_WRITE_DETAIL) only the subset of CLD_DETAIL_MIN is written");
-    if (rk == CLR_EV) return fail(CL_EINVAL, "clpfk_rollout_mlp_kpi_f32: reward kind CLR_EV needs the flexible-load tables");
-    if (int rc = no_pitch(dims, "clpfk_rollout_mlp_kpi_f32")) return rc;
-    if (dims->n_act_cols > 65536) return fail(CL_EINVAL, "clpfk_rollout_mlp_kpi_f32: n_act_cols=%d > 65536", dims->n_act_cols);
-    if (!mlp) return fail(CL_ENULL, "mlp is NULL");
-    if (mlp->n_device_cols != 0)
-        return fail(CL_EINVAL, "clpfk_rollout_mlp_kpi_f32: n_device_cols=%d: a building with a cooling / heating / combined device action column is not covered "
-                               "(the policy has storage heads only)", mlp->n_device_cols);
-    if (int rc = check_policy_sizes(*mlp, CLPF_MAX_HIDDEN)) return rc;
-    if (mlp->reserved) return fail(CL_EINVAL, "clpf_mlp.reserved must be 0");
+    if (int rc = no_f64_maps(dims, entry)) return rc;
+    if (int rc = detail_min_only(dims, entry)) return rc;
+    if (int rc = no_reward_ev(dims, entry)) return rc;
+    if (int rc = no_pitch(dims, entry)) return rc;
+    if (int rc = check_thermal_policy_mlp(entry, dims, mlp)) return rc;
     const PolicyCall call = {params, ts, state, out_bldg, out_env, ret_env, traj, kpi_bldg, kpi_env, t0, k_steps};
     if (int rc = check_policy_buffers(dims, *mlp, call, true)) return rc;
 
@@ -66,13 +56,10 @@ int clpfk_rollout_mlp_kpi_f32(const cl_dims* dims, const uint32_t* params, const
     PolicyArgs p;
     fill_policy_args(p, dims, *mlp, CLPF_NOISE_KEY, call);
     StepArgs& a = p.r.s;
-    // cl_rollout_full_policy_kernel's geometry: ONE building per wave, the whole district in one workgroup row -- so nw is n_bldg and nothing else
-    a.nw = tun.nw ? tun.nw : dims->n_bldg;
-    if (a.nw > 16 || a.nw > dims->n_bldg || a.nw < dims->n_bldg)
-        return fail(CL_EINVAL, "bad nw %d: the thermal policy KPI rollout runs one building per wave (nw = n_bldg = %d, at most 16)", a.nw, dims->n_bldg);
-    if (tun.vec == 2) return fail(CL_EINVAL, "no thermal policy KPI rollout kernel at 2 envs per lane: it runs at one env per lane");
-    if (tun.vec != 0 && tun.vec != 1) return fail(CL_EINVAL, "no thermal policy KPI rollout kernel at %d envs per lane", tun.vec);
-    const bool chain = dims->flags & CLD_F64_CHAIN, marl = rk == CLR_MARL;
+    // cl_rollout_full_policy_kernel's geometry
+    if (int rc = thermal_one_row_geometry(dims, tun, "thermal policy KPI", a.nw)) return rc;
+    if (int rc = one_env_per_lane_only(tun, "thermal policy KPI")) return rc;
+    const bool chain = dims->flags & CLD_F64_CHAIN, marl = reward_kind(dims) == CLR_MARL;
     const size_t lds = rollout_full_policy_kpi_lds_floats(a.nw) * sizeof(float);
     if (int rc = check_policy_lds(lds, "thermal policy KPI", a.nw, 1)) return rc;
     const int prec = chain ? 2 : 0;

@@ -121,6 +121,62 @@ def f32_torch_deviation(pol, x, pt, device='cpu', noise=None):
     return float((np.where(pt.cols >= 0, d, 0.0) if pol.kind.head_shape else d).max())
 
 
+class HostEntry:
+    """The entry point of one policy extension (a `_lib._Extension`) called on 256 bytes of HOST memory, for the refusals that come back before
+    any HIP call: a call that got as far as a launch would not return one of the argument codes.  `n_bldg`, `flags`, `n_act_cols` are the
+    defaults of `dims()`; `call()` returns the code, `error()` the library's message."""
+    BUFFERS = ('params', 'ts', 'state', 'out_bldg', 'out_env', 'ret_env', 'traj', 'kpi_bldg', 'kpi_env', 'series_scratch')
+    ODD, ODD1 = 'odd', 'odd1'              # a pointer value of `call`'s mlp fields: the buffer + 4 bytes / + 5 bytes
+
+    def __init__(self, ext, n_bldg, flags=0, n_act_cols=None):
+        import ctypes
+        from citylearn_amd import _lib
+        self.ext, self.defaults = ext, dict(n_bldg=n_bldg, flags=flags, n_act_cols=n_act_cols)
+        ext.build()
+        self.lib = lib = ctypes.CDLL(str(ext.path))
+        vp, i32 = ctypes.c_void_p, ctypes.c_int32
+        getattr(lib, f'{ext.prefix}_last_error').restype = ctypes.c_char_p
+        self.entry = getattr(lib, f'{ext.prefix}_{ext.entry}')
+        self.entry.argtypes = [ctypes.POINTER(_lib.Dims), vp, vp, vp, ctypes.POINTER(ext.mlp), vp, vp, vp, vp, *[vp] * ext.n_kpi, *ext.extra, i32, i32, vp]
+        for fname, restype, argtypes in ext.functions:
+            fn = getattr(lib, f'{ext.prefix}_{fname}')
+            fn.restype, fn.argtypes = restype, list(argtypes)
+
+    def error(self):
+        return getattr(self.lib, f'{self.ext.prefix}_last_error')().decode()
+
+    def dims(self, n_env=64, tun=None, **kw):
+        """`cl_dims` of 100 steps; `tun`: the fields of a `cl_tuning` to hang on it; any other field by name."""
+        import ctypes
+        from citylearn_amd import _lib
+        f = {**self.defaults, **kw}
+        d = _lib.Dims(n_env, f.pop('n_bldg'), 100, 0, f.pop('flags'))
+        n_act_cols = f.pop('n_act_cols')
+        d.n_act_cols = d.n_bldg if n_act_cols is None else n_act_cols
+        for k, v in f.items():
+            setattr(d, k, v)
+        if tun is not None:
+            d.tuning = ctypes.pointer(_lib.Tuning(**tun))
+        return d
+
+    def call(self, d, *, t0=0, k_steps=8, null=(), odd=(), scratch_floats=1 << 40, **mlp_kw):
+        """`null` / `odd`: names of BUFFERS to pass as NULL / 4 bytes off (ret_env and traj are NULL unless `odd`); `mlp_kw`: fields of the mlp
+        struct, pointers as None, ODD or ODD1."""
+        import ctypes
+        buf = np.zeros(64, dtype=np.float32)
+        p = buf.ctypes.data
+        null, odd = ((v,) if isinstance(v, str) else tuple(v) for v in (null, odd))
+        assert set(null + odd) <= set(self.BUFFERS)
+        a = {k: (p + 4 if k in odd else None if k in null or k in ('ret_env', 'traj') else p) for k in self.BUFFERS}
+        m = dict(n_hidden=16, n_sets=1, reserved=0, pre=p, dep=p, out=p, set_of_block=None, net_reset=None, act_low=p, act_high=p, sigma=None, seed=1)
+        m.update({k: {self.ODD: p + 4, self.ODD1: p + 5}.get(v, v) if isinstance(v, str) else v for k, v in mlp_kw.items()})
+        mlp = self.ext.mlp(**m)
+        kpi = [a['kpi_bldg'], a['kpi_env']][:self.ext.n_kpi]
+        extra = [a['series_scratch'], scratch_floats] if self.ext.extra else []
+        return self.entry(ctypes.byref(d) if d is not None else None, a['params'], a['ts'], a['state'], ctypes.byref(mlp), a['out_bldg'], a['out_env'],
+                          a['ret_env'], a['traj'], *kpi, *extra, t0, k_steps, None)
+
+
 def exports(path):
     """The dynamic symbols a shared library defines (`nm -D --defined-only`), sorted."""
     import subprocess

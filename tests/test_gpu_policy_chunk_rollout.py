@@ -166,6 +166,22 @@ def test_2_config_4_size_replayed(b_chunk, f64):
     _replay('b1024', tab, pt, eng, ret, traj, 'RewardFunction', f64, f'b1024 b_chunk={b_chunk} RewardFunction E=64 f64_maps={f64}')
 
 
+def test_2_without_a_return_buffer():
+    """(2) `ret_env=None`: the fold behind the chunk kernel launches NQ workgroup rows instead of NQ + 1.  The smallest shape that chunks -- 17
+    buildings cut 9 + 8 (an explicit b_chunk: they fit one row), 64 envs, K = 4: every plane bit for bit what a twin engine that keeps the
+    return leaves, and against single steps at `_replay`'s tolerances (the return it checks is the twin's)."""
+    E, K = 64, 4
+    spec, tab, layout, pol, pt, eng = _setup('het17', E, sigma=0.1, b_chunk=9)
+    twin = _setup('het17', E, sigma=0.1, b_chunk=9)[5]
+    ret, traj_twin = _roll(twin, pt, K, seed=5)
+    traj = torch.full_like(traj_twin, float('nan'))
+    eng.rollout_policy(K, pt, seed=5, traj=traj, chunked=True)
+    assert eng.last_kernels == twin.last_kernels == _names('chain'), eng.last_kernels
+    for got, want in ((traj, traj_twin), (eng.state, twin.state), (eng.out_bldg[:2], twin.out_bldg[:2]), (eng.out_env, twin.out_env)):
+        assert torch.equal(got, want)
+    _replay('het17', tab, pt, eng, ret, traj, 'RewardFunction', 'chain', 'het17 b_chunk=9 RewardFunction E=64 f64_maps=chain ret_env=None')
+
+
 # ---- 3. teacher-forced actions ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('H', [4, 16, 32])
 @pytest.mark.parametrize('f64,vec', PRECISIONS)

@@ -115,6 +115,24 @@ def test_2_kpis_equal_single_steps(district, b_chunk, kind, E, f64):
     assert bool((eng.kpi_bldg[abi.CLK_B_NET] != 0).all())
 
 
+def test_2_without_a_return_buffer():
+    """(2) `ret_env=None`: the fold behind the two kernels launches NQ workgroup rows instead of NQ + 1.  The smallest shape that chunks -- 17
+    buildings cut 6 + 6 + 5 (the default), 64 envs, K = 4: every plane a caller reads bit for bit what a twin engine that keeps the return leaves,
+    and against single steps at `_replay`'s tolerances (the return it checks is the twin's)."""
+    E, K = 64, 4
+    spec, tab, layout, pol, pt, eng = _setup('t17', E, sigma=0.1)
+    twin = _setup('t17', E, sigma=0.1)[5]
+    ret, traj_twin = _roll(twin, pt, K, seed=5)
+    traj = torch.full_like(traj_twin, float('nan'))
+    eng.rollout_policy(K, pt, seed=5, traj=traj, kpi=True, chunked=True)
+    assert eng.last_kernels == twin.last_kernels == _names('chain'), eng.last_kernels
+    assert torch.equal(traj, traj_twin)
+    for got, want in zip(_planes(eng), _planes(twin)):
+        assert torch.equal(got, want)
+    ref = StepEngine(tab, E, kpi=True, f64_maps='chain')
+    _replay(ref, pt, traj, eng, ret, 'chunked thermal policy kpi rollout vs single steps t17 E=64 f64_maps=chain ret_env=None', tab=tab)
+
+
 # ---- 3. config 4's district -------------------------------------------------------------------------------------------------------------
 def _series_f64(init, samples, t0=0):
     """`kpi_series_advance` (csrc/cl_rollout.h) restated in float64: `init` [12, E] the accumulators, `samples` [K, E] the district samples."""

@@ -115,6 +115,22 @@ def test_2_config_4_district_replayed(f64):
     _replay(tab, pt, eng, ret, traj, 'RewardFunction', f64)
 
 
+def test_2_without_a_return_buffer():
+    """(2) `ret_env=None`: the fold behind the chunk kernel launches NQ workgroup rows instead of NQ + 1.  The smallest shape that chunks -- 17
+    buildings cut 6 + 6 + 5 (the default), 64 envs, K = 4: every plane bit for bit what a twin engine that keeps the return leaves, and against
+    single steps at `_replay`'s tolerances (the return it checks is the twin's)."""
+    E, K = 64, 4
+    spec, tab, layout, pol, pt, eng = _setup('t17', E, sigma=0.1)
+    twin = _setup('t17', E, sigma=0.1)[5]
+    ret, traj_twin = _roll(twin, pt, K, seed=5)
+    traj = torch.full_like(traj_twin, float('nan'))
+    eng.rollout_policy(K, pt, seed=5, traj=traj, chunked=True)
+    assert eng.last_kernels == twin.last_kernels == _names('chain'), eng.last_kernels
+    for got, want in ((traj, traj_twin), (eng.state[:6], twin.state[:6]), (eng.out_bldg[:2], twin.out_bldg[:2]), (eng.out_env, twin.out_env)):
+        assert torch.equal(got, want)
+    _replay(tab, pt, eng, ret, traj, 'RewardFunction', 'chain')
+
+
 # ---- 3. teacher-forced actions ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('H', [4, 16, 32])
 @pytest.mark.parametrize('f64,vec', PRECISIONS)

@@ -796,6 +796,21 @@ struct ObsFusedArgs {
 // and its two inlined __powf are not in the code a wave fetches, and a building's scalar loads (parameter words, chain constants, table row) form
 // ONE group behind the plane loads instead of two dependent ones around the battery-flag test.  Same expressions on the same operands: same bits.
 // The plain float64-chain launch only (no FLEX / OBS / KPI epilogue; lean_step_dispatch's note on the fp32 map).
+// STORE ACKNOWLEDGEMENTS.  On gfx9 a store counts in vmcnt like a load, so a vmcnt wait behind a wave's plane stores sits out their
+// acknowledgement (0.3 - 0.8 us) whatever it was placed for.  The compiler placed three that nothing needed: in front of wave 0's second
+// building, in front of the partial sums' LDS writes, behind the reduction's barrier.  The cause is how its wait-count pass joins paths: a
+// register holds a "pending load" mark until a wait on the path clears it, and at a join the mark of ANY predecessor survives.  The plane
+// loads used to sit in an `if (live)` of their own and each building behind an `if (!own[m])` / `if (!live)` skip: a path "loads requested,
+// arithmetic (and its wait) skipped" exists in the flow graph though no wave takes it, the marks reached the join behind the stores, and
+// the first instruction there that re-used one of those registers got a vmcnt wait that now counted the stores.  (A wait written out in
+// front of the arithmetic does not help: it sits on the side of the skip that was clean already.)  So:
+//  - loads, both buildings and their stores form ONE region under `live && own[0]`, and the second building hangs on own[1] alone -- its
+//    loads' marks are cleared by the first building's wait on the only path that reaches it;
+//  - what the generic body reads behind the first building's stores -- parameter block, table row, chain constants, the reward's capacity
+//    word -- comes through the constant address space (scalar loads; as plain reads they were vector loads, real waits behind stores);
+//  - actions whose column is a parameter word are requested for both buildings in front of the first one's arithmetic;
+//  - the no-battery path, which truly leaves its state rows unread, waits for them itself.
+// Left as it was: two waits INSIDE the first building's store burst of the generic body (behind its first and third store; cause not found).
 template <int VEC, bool FLEX, bool NT, bool OBS, bool KPI = false, int PREC = 0, bool UNI = false>
 CL_DEV void lean_step_body(const StepArgs& a, float* lds, const ObsFusedArgs* of) {     // lds: [nw][NQ][64*VEC] (, then [64*VEC][pitch])
     static_assert(!UNI || (!FLEX && !OBS && !KPI && PREC == 2), "the uniform body is the plain float64-chain launch's");
@@ -838,10 +853,10 @@ CL_DEV void lean_step_body(const StepArgs& a, float* lds, const ObsFusedArgs* of
     CL_TRACE_DECL;
     CL_TRACE_ENTRY(0);
     CL_TRACE_CYCLES_ENTRY(4);
-    if (live) {
+    if (live && own[0]) {
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
-            if (!own[m]) continue;
+            if (m && !own[1]) continue;
             const long long off = (long long)bb[m] * a.ld + env0;          // every building has its state rows: no flag test
             pload<VEC, NTL>(s_soc[m], a.state + CLS_B_SOC * plane + off);
             pload<VEC, NTL>(s_eff[m], a.state + CLS_B_EFF * plane + off);
@@ -852,117 +867,142 @@ CL_DEV void lean_step_body(const StepArgs& a, float* lds, const ObsFusedArgs* of
             }
             if (act_by_bldg) pload<VEC, NTL>(a_es[m], a.actions + (long long)bb[m] * a.act_stride_col + env0);
         }
-    }
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        if (!own[m]) continue;
-        const int b = bb[m];
-        cl::Bp B;
-        cl::Row R;
-        [[maybe_unused]] cl::BattC bc_uni;
-        if constexpr (UNI) {
-            // every scalar of the building as ONE group: parameter words, the chain constants (not behind a battery-flag test that needs
-            // the words first) and the table row -- through the constant address space (cl_unit.h: the tables are read-only, and the kernel
-            // holds the generic body's plane stores, behind which a plain read would be a vector load per lane)
+        for (int m = 0; m < 2; ++m) {
+            if (m && !own[1]) continue;
+            const int b = bb[m];
+            cl::Bp B;
+            cl::Row R;
+            [[maybe_unused]] cl::BattC bc_uni;
+            // The building's parameter block and table row through the constant address space (cl_unit.h: the tables are read-only): behind the
+            // first building's plane stores a plain read of them is a vector load per lane -- and the wait for it sits out the acknowledgement of
+            // those stores as well, since loads and stores count in one counter (STORE ACKNOWLEDGEMENTS, above)
             const cl::cl_ctab pb = cl::as_ctab(a.params + (long long)b * CL_NP);
             const cl::cl_ctab qb = cl::as_ctab(a.ts + ((long long)ts_row * a.n_bldg + b) * CL_NF);
-            B.p = a.params + (long long)b * CL_NP; B.flags = CLF_BATTERY; B.a_es = b; B.rw_exponent = 1.0f;
-            B.r = cl::pw(pb, CLP_L_TSR);
-            cl::load_battc_from(bc_uni, pb);
+            if constexpr (UNI) {
+                // every scalar of the building as ONE group: parameter words, the chain constants (not behind a battery-flag test that needs
+                // the words first) and the table row
+                B.p = a.params + (long long)b * CL_NP; B.flags = CLF_BATTERY; B.a_es = b; B.rw_exponent = 1.0f;
+                B.r = cl::pw(pb, CLP_L_TSR);
+                cl::load_battc_from(bc_uni, pb);
+            } else cl::load_bp_from<false>(B, a.params + (long long)b * CL_NP, pb);
             R.nsl = cl::pw(qb, CLT_NSL); R.sol = cl::pw(qb, CLT_SOLAR); R.price = cl::pw(qb, CLT_PRICE); R.carbon = cl::pw(qb, CLT_CARBON);
             R.outage = false;
-        } else {
-            cl::load_bp<false>(B, a.params + (long long)b * CL_NP);
-            cl::load_row<false>(R, a.ts + ((long long)ts_row * a.n_bldg + b) * CL_NF, B.flags);
-        }
-        // (OBS) the building's column descriptors and the offsets of their affine maps, fetched with the parameters: nothing is left to
-        // wait for between the arithmetic and the tile writes
-        [[maybe_unused]] int od_n = 0, od_col[CL_OBS_FUSED_PER_BLDG], od_src[CL_OBS_FUSED_PER_BLDG];
-        [[maybe_unused]] float od_scale[CL_OBS_FUSED_PER_BLDG], od_base[CL_OBS_FUSED_PER_BLDG];
-        if constexpr (OBS) {
-            const float* __restrict__ trow = of->table + (size_t)(of->row + (ts_row - a.t)) * of->n_cols;
-            const int d0 = of->start[b];
-            od_n = of->start[b + 1] - d0;
+            // (OBS) the building's column descriptors and the offsets of their affine maps, fetched with the parameters: nothing is left to
+            // wait for between the arithmetic and the tile writes
+            [[maybe_unused]] int od_n = 0, od_col[CL_OBS_FUSED_PER_BLDG], od_src[CL_OBS_FUSED_PER_BLDG];
+            [[maybe_unused]] float od_scale[CL_OBS_FUSED_PER_BLDG], od_base[CL_OBS_FUSED_PER_BLDG];
+            if constexpr (OBS) {
+                const float* __restrict__ trow = of->table + (size_t)(of->row + (ts_row - a.t)) * of->n_cols;
+                const int d0 = of->start[b];
+                od_n = of->start[b + 1] - d0;
 #pragma unroll
-            for (int k = 0; k < CL_OBS_FUSED_PER_BLDG; ++k) {
-                const int d = min(d0 + min(k, max(od_n - 1, 0)), CLOB_MAX_DEPS - 1);      // (a building without columns reads a valid, unused entry)
-                od_col[k] = of->deps[d].col; od_src[k] = of->deps[d].src; od_scale[k] = of->deps[d].scale;
-                od_base[k] = trow[od_col[k]];
-            }
-        }
-        if (!live) continue;
-        const long long off = (long long)b * a.ld + env0;
-        const bool batt = UNI || (B.flags & CLF_BATTERY);
-        const bool no_es = !UNI && B.a_es < 0;                       // no electrical_storage action: the battery idles
-        if (!act_by_bldg) load_action<VEC>(a_es[m], a, B.a_es, env0);
-        CL_TRACE_WAITV(1 + 4 * m, s_deg[m][0]);
-        float o_net[VEC], o_rw[VEC];
-        [[maybe_unused]] float o_cb[VEC];
-        // chargers / washing machines of this building (cl_flex_kernel ran just before this launch)
-        const int fbi = (FLEX && (B.flags & CLF_FLEX)) ? (int)B.p[CLP_FLEX_INDEX] : -1;
-        float x_load[VEC];
-        if (FLEX && fbi >= 0) vload<VEC>(x_load, a.flex_out + (long long)CLX_LOAD * a.n_flex_bldg * a.n_env + (long long)fbi * a.n_env + env0);
-        if constexpr (FLEX) {
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                cl::State S;
-                S.soc = batt ? s_soc[m][i] : 0.0f; S.eff = batt ? s_eff[m][i] : 1.0f; S.degcap = batt ? s_deg[m][i] : 0.0f;
-                S.cs = S.hs = S.ds = 0.0f;
-                const cl::Act act = {0.0f, 0.0f, 0.0f, B.a_es >= 0 ? a_es[m][i] : 0.0f, 0.0f, 0.0f};
-                cl::Out O;
-                cl::unit_step<false>(B, R, a.t, quirk, act, S, O);
-                if (FLEX && fbi >= 0) cl::apply_flex(false, R.price, R.carbon, x_load[i], 0.0f, O);
-                const float rw = cl::unit_reward<false>(rkind, B, S, O.net);
-                s_soc[m][i] = S.soc; s_eff[m][i] = S.eff; s_deg[m][i] = S.degcap;
-                o_net[i] = O.net; o_rw[i] = rw;
-                q_net[i] += O.net; q_cost[i] += O.cost; q_em[i] += O.emission;
-                q_rw[i] += (FLEX && rkind == CLR_EV) ? cl::marl_reward(O.net, 1.0f) : rw;
-            }
-        } else {
-            // The lean unit (cl::unit_step<false> + cl::unit_reward<false>, restated with the same expressions) with everything that
-            // does not depend on the env taken out of the env loop: the t = 0 booking of the load, the battery's curve parameters
-            // (in VGPRs once per building instead of one v_mov per select per env), the has-battery and reward-kind tests.
-            // 111 -> 90 VALU instructions per unit (SQ_INSTS_VALU).
-            const bool first = quirk && a.t == 0;
-            float c_ns = first ? 3.0f * R.nsl : R.nsl;           // booked at reset, by the step and by update_variables
-            float sol = R.sol;
-            const float cbk = first ? 2.0f : 1.0f;               // c_b = first ? 2 eb : eb
-            CL_PIN_V(c_ns); CL_PIN_V(sol);
-            if constexpr (UNI) {
-                // The scalar group is complete HERE, at the row's first use, and nothing moves across: left alone, the scheduler sinks the row's
-                // loads behind the battery map (a fresh scalar round trip in the middle of the wave), and the optimiser lifts the actions'
-                // float -> double conversions into the plane-load block (a vector wait between the two buildings' loads, in front of the
-                // scalar group) -- the action stays opaque until this point.  No instruction either way.
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) CL_PIN_V(a_es[m][i]);
-            }
-            float soc_rw[VEC];
-            if (F64 && batt) {
-                // the battery map in float64 on the unrounded parameters (CLD_F64_MAPS, cl_unit.h)
-                if constexpr (F64) {
-                    cl::BattP64 B64;
-                    cl::load_batt64(B64, B.p);
-                    if (B.a_es < 0) {
-#pragma unroll
-                        for (int i = 0; i < VEC; ++i) a_es[m][i] = 0.0f;
-                    }
-#pragma unroll
-                    for (int i = 0; i < VEC; ++i) {
-                        cl::State S = {s_soc[m][i], s_eff[m][i], s_deg[m][i], 0.0f, 0.0f, 0.0f, s_efl[m][i], s_dgl[m][i]};
-                        const float eb = cl::battery_charge_ref(B64, (double)a_es[m][i] * B64.pow * B64.dt / B64.r, a.t == 0, S);     // (flexibility = +inf)
-                        s_soc[m][i] = S.soc; s_eff[m][i] = S.eff; s_deg[m][i] = S.degcap; s_efl[m][i] = S.eff_lo; s_dgl[m][i] = S.deg_lo;
-                        soc_rw[i] = S.soc;
-                        o_cb[i] = cbk * eb;
-                        o_net[i] = fmaf(c_ns + o_cb[i], B.r, sol);
-                    }
+                for (int k = 0; k < CL_OBS_FUSED_PER_BLDG; ++k) {
+                    const int d = min(d0 + min(k, max(od_n - 1, 0)), CLOB_MAX_DEPS - 1);      // (a building without columns reads a valid, unused entry)
+                    od_col[k] = of->deps[d].col; od_src[k] = of->deps[d].src; od_scale[k] = of->deps[d].scale;
+                    od_base[k] = trow[od_col[k]];
                 }
-            } else if (PREC == 2 && batt) {
-                // the soc chain in float64, the degraded capacity as the capacity loss (CLD_F64_CHAIN, cl_unit.h)
-                if constexpr (PREC == 2) {
-                    cl::BattC bc;
-                    if constexpr (UNI) bc = bc_uni;
-                    else cl::load_battc(bc, B.p);
+            }
+            const long long off = (long long)b * a.ld + env0;
+            const bool batt = UNI || (B.flags & CLF_BATTERY);
+            const bool no_es = !UNI && B.a_es < 0;                       // no electrical_storage action: the battery idles
+            if constexpr (!UNI) {
+                // Actions the top of the kernel could not request (their column is a parameter word): BOTH buildings' here, in front of the
+                // first one's arithmetic -- the second one's column word rides in the first one's scalar group.  Requested by the second
+                // building itself they would be loads behind the first one's stores.
+                if (!act_by_bldg && m == 0) {
+                    load_action<VEC>(a_es[0], a, B.a_es, env0);
+                    const int col1 = (int)cl::as_ctab(a.params + (long long)bb[own[1] ? 1 : 0] * CL_NP)[CLP_L_ACT_ES];
+                    if (own[1]) load_action<VEC>(a_es[1], a, col1, env0);
+                }
+            }
+            CL_TRACE_WAITV(1 + 4 * m, s_deg[m][0]);
+            float o_net[VEC], o_rw[VEC];
+            [[maybe_unused]] float o_cb[VEC];
+            // chargers / washing machines of this building (cl_flex_kernel ran just before this launch)
+            const int fbi = (FLEX && (B.flags & CLF_FLEX)) ? (int)B.p[CLP_FLEX_INDEX] : -1;
+            float x_load[VEC];
+            if (FLEX && fbi >= 0) vload<VEC>(x_load, a.flex_out + (long long)CLX_LOAD * a.n_flex_bldg * a.n_env + (long long)fbi * a.n_env + env0);
+            if constexpr (FLEX) {
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    cl::State S;
+                    S.soc = batt ? s_soc[m][i] : 0.0f; S.eff = batt ? s_eff[m][i] : 1.0f; S.degcap = batt ? s_deg[m][i] : 0.0f;
+                    S.cs = S.hs = S.ds = 0.0f;
+                    const cl::Act act = {0.0f, 0.0f, 0.0f, B.a_es >= 0 ? a_es[m][i] : 0.0f, 0.0f, 0.0f};
+                    cl::Out O;
+                    cl::unit_step<false>(B, R, a.t, quirk, act, S, O);
+                    if (FLEX && fbi >= 0) cl::apply_flex(false, R.price, R.carbon, x_load[i], 0.0f, O);
+                    const float rw = cl::unit_reward<false>(rkind, B, S, O.net);
+                    s_soc[m][i] = S.soc; s_eff[m][i] = S.eff; s_deg[m][i] = S.degcap;
+                    o_net[i] = O.net; o_rw[i] = rw;
+                    q_net[i] += O.net; q_cost[i] += O.cost; q_em[i] += O.emission;
+                    q_rw[i] += (FLEX && rkind == CLR_EV) ? cl::marl_reward(O.net, 1.0f) : rw;
+                }
+            } else {
+                // The lean unit (cl::unit_step<false> + cl::unit_reward<false>, restated with the same expressions) with everything that
+                // does not depend on the env taken out of the env loop: the t = 0 booking of the load, the battery's curve parameters
+                // (in VGPRs once per building instead of one v_mov per select per env), the has-battery and reward-kind tests.
+                // 111 -> 90 VALU instructions per unit (SQ_INSTS_VALU).
+                const bool first = quirk && a.t == 0;
+                float c_ns = first ? 3.0f * R.nsl : R.nsl;           // booked at reset, by the step and by update_variables
+                float sol = R.sol;
+                const float cbk = first ? 2.0f : 1.0f;               // c_b = first ? 2 eb : eb
+                CL_PIN_V(c_ns); CL_PIN_V(sol);
+                if constexpr (UNI) {
+                    // The scalar group is complete HERE, at the row's first use, and nothing moves across: left alone, the scheduler sinks the row's
+                    // loads behind the battery map (a fresh scalar round trip in the middle of the wave), and the optimiser lifts the actions'
+                    // float -> double conversions into the plane-load block (a vector wait between the two buildings' loads, in front of the
+                    // scalar group) -- the action stays opaque until this point.  No instruction either way.
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) CL_PIN_V(a_es[m][i]);
+                }
+                float soc_rw[VEC];
+                if (F64 && batt) {
+                    // the battery map in float64 on the unrounded parameters (CLD_F64_MAPS, cl_unit.h)
+                    if constexpr (F64) {
+                        cl::BattP64 B64;
+                        cl::load_batt64(B64, B.p);
+                        if (B.a_es < 0) {
+#pragma unroll
+                            for (int i = 0; i < VEC; ++i) a_es[m][i] = 0.0f;
+                        }
+#pragma unroll
+                        for (int i = 0; i < VEC; ++i) {
+                            cl::State S = {s_soc[m][i], s_eff[m][i], s_deg[m][i], 0.0f, 0.0f, 0.0f, s_efl[m][i], s_dgl[m][i]};
+                            const float eb = cl::battery_charge_ref(B64, (double)a_es[m][i] * B64.pow * B64.dt / B64.r, a.t == 0, S);     // (flexibility = +inf)
+                            s_soc[m][i] = S.soc; s_eff[m][i] = S.eff; s_deg[m][i] = S.degcap; s_efl[m][i] = S.eff_lo; s_dgl[m][i] = S.deg_lo;
+                            soc_rw[i] = S.soc;
+                            o_cb[i] = cbk * eb;
+                            o_net[i] = fmaf(c_ns + o_cb[i], B.r, sol);
+                        }
+                    }
+                } else if (PREC == 2 && batt) {
+                    // the soc chain in float64, the degraded capacity as the capacity loss (CLD_F64_CHAIN, cl_unit.h)
+                    if constexpr (PREC == 2) {
+                        cl::BattC bc;
+                        if constexpr (UNI) bc = bc_uni;
+                        else cl::load_battc_from(bc, pb);
+                        if (no_es) {
+#pragma unroll
+                            for (int i = 0; i < VEC; ++i) a_es[m][i] = 0.0f;
+                        }
+#pragma unroll
+                        for (int i = 0; i < VEC; ++i) {
+                            cl::State S = {s_soc[m][i], s_eff[m][i], s_deg[m][i], 0.0f, 0.0f, 0.0f};
+                            const float eb = cl::battery_charge_chain(bc, a_es[m][i], INFINITY, S);
+                            s_soc[m][i] = S.soc; s_eff[m][i] = S.eff; s_deg[m][i] = S.degcap;
+                            soc_rw[i] = S.soc;
+                            o_cb[i] = cbk * eb;
+                            o_net[i] = fmaf(c_ns + o_cb[i], B.r, sol);
+                        }
+                    }
+                } else if (batt) {
+                    cl::BattP Bv = B.batt;
+                    CL_PIN_V(Bv.cpc_a0); CL_PIN_V(Bv.cpc_b0); CL_PIN_V(Bv.cpc_a1); CL_PIN_V(Bv.cpc_b1);
+                    CL_PIN_V(Bv.pec_a0); CL_PIN_V(Bv.pec_b0); CL_PIN_V(Bv.pec_a1); CL_PIN_V(Bv.pec_b1);
+                    CL_PIN_V(Bv.pec_a2); CL_PIN_V(Bv.pec_b2); CL_PIN_V(Bv.pec_a3); CL_PIN_V(Bv.pec_b3);
                     if (no_es) {
 #pragma unroll
                         for (int i = 0; i < VEC; ++i) a_es[m][i] = 0.0f;
@@ -970,116 +1010,102 @@ CL_DEV void lean_step_body(const StepArgs& a, float* lds, const ObsFusedArgs* of
 #pragma unroll
                     for (int i = 0; i < VEC; ++i) {
                         cl::State S = {s_soc[m][i], s_eff[m][i], s_deg[m][i], 0.0f, 0.0f, 0.0f};
-                        const float eb = cl::battery_charge_chain(bc, a_es[m][i], INFINITY, S);
+                        // battery_step with flexibility = +inf (no outage in a lean district)
+                        const float eb = cl::battery_energy(Bv, a_es[m][i] * Bv.pdt, S);
                         s_soc[m][i] = S.soc; s_eff[m][i] = S.eff; s_deg[m][i] = S.degcap;
                         soc_rw[i] = S.soc;
-                        o_cb[i] = cbk * eb;
+                        o_cb[i] = cbk * eb;                           // the battery's booked consumption (doubled at t = 0)
                         o_net[i] = fmaf(c_ns + o_cb[i], B.r, sol);
                     }
-                }
-            } else if (batt) {
-                cl::BattP Bv = B.batt;
-                CL_PIN_V(Bv.cpc_a0); CL_PIN_V(Bv.cpc_b0); CL_PIN_V(Bv.cpc_a1); CL_PIN_V(Bv.cpc_b1);
-                CL_PIN_V(Bv.pec_a0); CL_PIN_V(Bv.pec_b0); CL_PIN_V(Bv.pec_a1); CL_PIN_V(Bv.pec_b1);
-                CL_PIN_V(Bv.pec_a2); CL_PIN_V(Bv.pec_b2); CL_PIN_V(Bv.pec_a3); CL_PIN_V(Bv.pec_b3);
-                if (no_es) {
+                } else {
+                    // (no battery: nobody reads the state rows requested at the top.  Waited for HERE, on the path that leaves them behind --
+                    //  otherwise every wave pays for them at its stores: STORE ACKNOWLEDGEMENTS, above.  s_waitcnt vmcnt(0), the other counters
+                    //  open; the first building's covers the second one's rows, and behind a first building WITH a battery they have landed)
+                    if (m == 0) __builtin_amdgcn_s_waitcnt(0x0F70);
 #pragma unroll
-                    for (int i = 0; i < VEC; ++i) a_es[m][i] = 0.0f;
+                    for (int i = 0; i < VEC; ++i) { o_net[i] = fmaf(c_ns + 0.0f, B.r, sol); soc_rw[i] = 0.0f; o_cb[i] = 0.0f; }
+                }
+                if constexpr (UNI) {                                      // lean_rewards' default kind at exponent 1
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) o_rw[i] = -fmaxf(o_net[i], 0.0f);
+                } else cl::lean_rewards_from<VEC>(rkind, B, pb, soc_rw, o_net, o_rw);
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) {
+                    q_net[i] += o_net[i]; q_cost[i] += cl::mul_rn(o_net[i], R.price); q_em[i] += fmaxf(0.0f, o_net[i] * R.carbon);
+                    q_rw[i] += o_rw[i];
+                }
+            }
+            CL_TRACE_AFTER(2 + 4 * m, o_rw[VEC - 1]);
+            if (batt) {
+                pstore<VEC, NT>(a.state + CLS_B_SOC * plane + off, s_soc[m]);
+                pstore<VEC, NT>(a.state + CLS_B_EFF * plane + off, s_eff[m]);
+                pstore<VEC, NT>(a.state + CLS_B_DEGCAP * plane + off, s_deg[m]);
+                if constexpr (F64) {
+                    pstore<VEC, NT>(a.state + CLS_B_EFF_LO * plane + off, s_efl[m]);
+                    pstore<VEC, NT>(a.state + CLS_B_DEGCAP_LO * plane + off, s_dgl[m]);
+                }
+            }
+            pstore<VEC, NT>(a.out_bldg + CLO_NET * plane + off, o_net);
+            if (rkind != CLR_MARL && !(FLEX && rkind == CLR_EV)) pstore<VEC, NT>(a.out_bldg + CLO_REWARD * plane + off, o_rw);
+            if constexpr (KPI && !FLEX) {
+                // The streaming KPI accumulators of this building, updated by the wave that holds its step in registers (cl_kpi_bldg_kernel's
+                // arithmetic, citylearn.py:1136-1323).  A lean district has no outage and serves its whole load, so the unserved-energy sums
+                // do not move; and its baseline -- the net without the battery (building.py:345-366) = load + solar -- and its expected
+                // energy do not depend on the env at all: those five sums are kept ONCE per block of CL_ROW0_BLOCK envs (the envs that share
+                // a table row), at the block's first env.  Per (env, building) only the four control sums move: 32 B on top of the step's 37.
+                // (the four loads are issued together, before the first store.  Fetching them at the top of the kernel with the state planes was
+                //  measured and is slower -- 17.8 vs 15.9 us at 17 x 65 536: 117 instead of 89 VGPRs and 32 more floats per lane in the first burst)
+                float k_pos[VEC], k_net[VEC], k_em[VEC], k_cost[VEC];
+                float* kp = a.kpi_bldg + off;
+                vload<VEC>(k_pos, kp + (long long)CLK_C_POS * plane); vload<VEC>(k_net, kp + (long long)CLK_C_NET * plane);
+                vload<VEC>(k_em, kp + (long long)CLK_C_EMISSION * plane); vload<VEC>(k_cost, kp + (long long)CLK_C_COST * plane);
+                // ... and, in the same burst, the block's five env-independent sums (lane 0 of the block's first workgroup; they were five
+                // `+=` statements behind the stores below: five dependent round trips on every wave's way to the reduction)
+                const bool block_sums = lane == 0 && (blockIdx.x * TILE) % CL_ROW0_BLOCK == 0;
+                float b_pos = 0.0f, b_net = 0.0f, b_em = 0.0f, b_cost = 0.0f, b_exp = 0.0f;
+                if (block_sums) {
+                    b_pos = kp[(long long)CLK_B_POS * plane]; b_net = kp[(long long)CLK_B_NET * plane];
+                    b_em = kp[(long long)CLK_B_EMISSION * plane]; b_cost = kp[(long long)CLK_B_COST * plane];
+                    b_exp = kp[(long long)CLK_EXPECTED_ALL * plane];
                 }
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) {
-                    cl::State S = {s_soc[m][i], s_eff[m][i], s_deg[m][i], 0.0f, 0.0f, 0.0f};
-                    // battery_step with flexibility = +inf (no outage in a lean district)
-                    const float eb = cl::battery_energy(Bv, a_es[m][i] * Bv.pdt, S);
-                    s_soc[m][i] = S.soc; s_eff[m][i] = S.eff; s_deg[m][i] = S.degcap;
-                    soc_rw[i] = S.soc;
-                    o_cb[i] = cbk * eb;                           // the battery's booked consumption (doubled at t = 0)
-                    o_net[i] = fmaf(c_ns + o_cb[i], B.r, sol);
+                    k_pos[i] += fmaxf(o_net[i], 0.0f); k_net[i] += o_net[i];
+                    k_em[i] += fmaxf(o_net[i] * R.carbon, 0.0f); k_cost[i] += fmaxf(o_net[i] * R.price, 0.0f);
                 }
-            } else {
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) { o_net[i] = fmaf(c_ns + 0.0f, B.r, sol); soc_rw[i] = 0.0f; o_cb[i] = 0.0f; }
-            }
-            if constexpr (UNI) {                                      // lean_rewards' default kind at exponent 1
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) o_rw[i] = -fmaxf(o_net[i], 0.0f);
-            } else cl::lean_rewards<VEC>(rkind, B, soc_rw, o_net, o_rw);
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                q_net[i] += o_net[i]; q_cost[i] += cl::mul_rn(o_net[i], R.price); q_em[i] += fmaxf(0.0f, o_net[i] * R.carbon);
-                q_rw[i] += o_rw[i];
-            }
-        }
-        CL_TRACE_AFTER(2 + 4 * m, o_rw[VEC - 1]);
-        if (batt) {
-            pstore<VEC, NT>(a.state + CLS_B_SOC * plane + off, s_soc[m]);
-            pstore<VEC, NT>(a.state + CLS_B_EFF * plane + off, s_eff[m]);
-            pstore<VEC, NT>(a.state + CLS_B_DEGCAP * plane + off, s_deg[m]);
-            if constexpr (F64) {
-                pstore<VEC, NT>(a.state + CLS_B_EFF_LO * plane + off, s_efl[m]);
-                pstore<VEC, NT>(a.state + CLS_B_DEGCAP_LO * plane + off, s_dgl[m]);
-            }
-        }
-        pstore<VEC, NT>(a.out_bldg + CLO_NET * plane + off, o_net);
-        if (rkind != CLR_MARL && !(FLEX && rkind == CLR_EV)) pstore<VEC, NT>(a.out_bldg + CLO_REWARD * plane + off, o_rw);
-        if constexpr (KPI && !FLEX) {
-            // The streaming KPI accumulators of this building, updated by the wave that holds its step in registers (cl_kpi_bldg_kernel's
-            // arithmetic, citylearn.py:1136-1323).  A lean district has no outage and serves its whole load, so the unserved-energy sums
-            // do not move; and its baseline -- the net without the battery (building.py:345-366) = load + solar -- and its expected
-            // energy do not depend on the env at all: those five sums are kept ONCE per block of CL_ROW0_BLOCK envs (the envs that share
-            // a table row), at the block's first env.  Per (env, building) only the four control sums move: 32 B on top of the step's 37.
-            // (the four loads are issued together, before the first store.  Fetching them at the top of the kernel with the state planes was
-            //  measured and is slower -- 17.8 vs 15.9 us at 17 x 65 536: 117 instead of 89 VGPRs and 32 more floats per lane in the first burst)
-            float k_pos[VEC], k_net[VEC], k_em[VEC], k_cost[VEC];
-            float* kp = a.kpi_bldg + off;
-            vload<VEC>(k_pos, kp + (long long)CLK_C_POS * plane); vload<VEC>(k_net, kp + (long long)CLK_C_NET * plane);
-            vload<VEC>(k_em, kp + (long long)CLK_C_EMISSION * plane); vload<VEC>(k_cost, kp + (long long)CLK_C_COST * plane);
-            // ... and, in the same burst, the block's five env-independent sums (lane 0 of the block's first workgroup; they were five
-            // `+=` statements behind the stores below: five dependent round trips on every wave's way to the reduction)
-            const bool block_sums = lane == 0 && (blockIdx.x * TILE) % CL_ROW0_BLOCK == 0;
-            float b_pos = 0.0f, b_net = 0.0f, b_em = 0.0f, b_cost = 0.0f, b_exp = 0.0f;
-            if (block_sums) {
-                b_pos = kp[(long long)CLK_B_POS * plane]; b_net = kp[(long long)CLK_B_NET * plane];
-                b_em = kp[(long long)CLK_B_EMISSION * plane]; b_cost = kp[(long long)CLK_B_COST * plane];
-                b_exp = kp[(long long)CLK_EXPECTED_ALL * plane];
-            }
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) {
-                k_pos[i] += fmaxf(o_net[i], 0.0f); k_net[i] += o_net[i];
-                k_em[i] += fmaxf(o_net[i] * R.carbon, 0.0f); k_cost[i] += fmaxf(o_net[i] * R.price, 0.0f);
-            }
-            pstore<VEC, NT>(kp + (long long)CLK_C_POS * plane, k_pos); pstore<VEC, NT>(kp + (long long)CLK_C_NET * plane, k_net);
-            pstore<VEC, NT>(kp + (long long)CLK_C_EMISSION * plane, k_em); pstore<VEC, NT>(kp + (long long)CLK_C_COST * plane, k_cost);
-            const float c_ns0 = (quirk && a.t == 0) ? 3.0f * R.nsl : R.nsl;
-            const float base = fmaf(c_ns0, B.r, R.sol);                          // the step's net with the battery term left out
-            if (lane == 0) lds[(size_t)a.nw * NQ * TILE + b] = base;               // for the district baseline series (below)
-            if (block_sums) {                                                      // (lane 0: kp = this building's row at the block's first env)
-                kp[(long long)CLK_B_POS * plane] = b_pos + fmaxf(base, 0.0f);
-                kp[(long long)CLK_B_NET * plane] = b_net + base;
-                kp[(long long)CLK_B_EMISSION * plane] = b_em + fmaxf(base * R.carbon, 0.0f);
-                kp[(long long)CLK_B_COST * plane] = b_cost + fmaxf(base * R.price, 0.0f);
-                kp[(long long)CLK_EXPECTED_ALL * plane] = b_exp + R.nsl;
-            }
-        }
-        if constexpr (OBS) {
-            // this building's observation columns, into the workgroup's [64 * VEC envs][pitch] tile (streamed out below)
-            float* tile = lds + (size_t)a.nw * NQ * TILE;
-#pragma unroll
-            for (int k = 0; k < CL_OBS_FUSED_PER_BLDG; ++k) {
-                if (k >= od_n) break;                                                // wave-uniform
-                const int col = od_col[k], src = od_src[k];
-                const float scale = od_scale[k], base = od_base[k];
-                const bool is_out = (src >> 28) == CLOB_KIND_OUT;
-                const int pl = (src >> 20) & 0xFF;
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) {
-                    const float v = is_out ? (pl == CLO_NET ? o_net[i] : o_rw[i])
-                                           : (pl == CLS_B_SOC ? s_soc[m][i] : pl == CLS_B_EFF ? s_eff[m][i] : s_deg[m][i]);
-                    tile[(size_t)(lane * VEC + i) * of->pitch + col] = fmaf(v, scale, base);
+                pstore<VEC, NT>(kp + (long long)CLK_C_POS * plane, k_pos); pstore<VEC, NT>(kp + (long long)CLK_C_NET * plane, k_net);
+                pstore<VEC, NT>(kp + (long long)CLK_C_EMISSION * plane, k_em); pstore<VEC, NT>(kp + (long long)CLK_C_COST * plane, k_cost);
+                const float c_ns0 = (quirk && a.t == 0) ? 3.0f * R.nsl : R.nsl;
+                const float base = fmaf(c_ns0, B.r, R.sol);                          // the step's net with the battery term left out
+                if (lane == 0) lds[(size_t)a.nw * NQ * TILE + b] = base;               // for the district baseline series (below)
+                if (block_sums) {                                                      // (lane 0: kp = this building's row at the block's first env)
+                    kp[(long long)CLK_B_POS * plane] = b_pos + fmaxf(base, 0.0f);
+                    kp[(long long)CLK_B_NET * plane] = b_net + base;
+                    kp[(long long)CLK_B_EMISSION * plane] = b_em + fmaxf(base * R.carbon, 0.0f);
+                    kp[(long long)CLK_B_COST * plane] = b_cost + fmaxf(base * R.price, 0.0f);
+                    kp[(long long)CLK_EXPECTED_ALL * plane] = b_exp + R.nsl;
                 }
             }
+            if constexpr (OBS) {
+                // this building's observation columns, into the workgroup's [64 * VEC envs][pitch] tile (streamed out below)
+                float* tile = lds + (size_t)a.nw * NQ * TILE;
+#pragma unroll
+                for (int k = 0; k < CL_OBS_FUSED_PER_BLDG; ++k) {
+                    if (k >= od_n) break;                                                // wave-uniform
+                    const int col = od_col[k], src = od_src[k];
+                    const float scale = od_scale[k], base = od_base[k];
+                    const bool is_out = (src >> 28) == CLOB_KIND_OUT;
+                    const int pl = (src >> 20) & 0xFF;
+#pragma unroll
+                    for (int i = 0; i < VEC; ++i) {
+                        const float v = is_out ? (pl == CLO_NET ? o_net[i] : o_rw[i])
+                                               : (pl == CLS_B_SOC ? s_soc[m][i] : pl == CLS_B_EFF ? s_eff[m][i] : s_deg[m][i]);
+                        tile[(size_t)(lane * VEC + i) * of->pitch + col] = fmaf(v, scale, base);
+                    }
+                }
+            }
+            CL_TRACE_AFTER(3 + 4 * m, q_rw[0]);
         }
-        CL_TRACE_AFTER(3 + 4 * m, q_rw[0]);
     }
     if constexpr (OBS) {
         if (w == 0) {                                                              // pad columns: zeros (like cl_observe_f32)
@@ -1130,7 +1156,8 @@ CL_DEV void lean_step_body(const StepArgs& a, float* lds, const ObsFusedArgs* of
 // district and env-contiguous actions -> lean_step_body<.., UNI>.  A strided action tensor runs the generic body with the hint set.
 // (The fp32 launch cl_step_lean_kernel keeps the generic body alone.  With both it measured 6.39 - 6.45 against 6.54 - 6.56 us at 17 x 65 536,
 //  but the second copy of the plane loads takes the kernel past the vector-load count tests/test_isa_guards.py pins for it (37 > 32); and ONE
-//  copy of the loads in front of the branch costs registers instead -- 101 VGPRs there, 128 + 20 bytes of scratch under the chain.)
+//  copy of the loads in front of the branch costs registers instead -- 101 VGPRs there, 128 + 20 bytes of scratch under the chain.
+//  Since the generic body reads its tables by scalar loads it holds 19 vector loads in 73 VGPRs: a second copy would fit now.  Not measured again.)
 template <int VEC, bool NT>
 CL_DEV void lean_step_dispatch(const StepArgs& a, float* lds) {
     if ((a.flags & CLD_LEAN_UNIFORM) && a.act_stride_env == 1) lean_step_body<VEC, false, NT, false, false, 2, true>(a, lds, nullptr);

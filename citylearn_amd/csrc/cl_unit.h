@@ -104,7 +104,9 @@ CL_DEV float mul_rn(float a, float b) {
     return a * b;
 }
 
-CL_DEV void load_batt(BattP& B, const uint32_t* __restrict__ p) {
+// (P: a plain pointer or a cl_ctab, as in load_battc_from below)
+template <class P>
+CL_DEV void load_batt_from(BattP& B, P p) {
     B.r = pw(p, CLP_L_TSR); B.pdt = pw(p, CLP_L_PDT); B.pow = pw(p, CLP_L_POW); B.cap = pw(p, CLP_L_CAP);
     B.capl = pw(p, CLP_L_CAPL); B.inv_cap = pw(p, CLP_L_INV_CAP); B.inv_pow = pw(p, CLP_L_INV_POW);
     B.omd = pw(p, CLP_L_OMD); B.degk = pw(p, CLP_L_DEGK);
@@ -115,27 +117,31 @@ CL_DEV void load_batt(BattP& B, const uint32_t* __restrict__ p) {
     B.pec_b1 = pw(p, CLP_L_PEC_B1); B.pec_a2 = pw(p, CLP_L_PEC_A2); B.pec_b2 = pw(p, CLP_L_PEC_B2);
     B.pec_a3 = pw(p, CLP_L_PEC_A3); B.pec_b3 = pw(p, CLP_L_PEC_B3);
 }
+CL_DEV void load_batt(BattP& B, const uint32_t* __restrict__ p) { load_batt_from(B, p); }
 
 CL_DEV void load_tank(TankP& T, const uint32_t* __restrict__ p, int raw, int der) {
     T.cap = pw(p, raw); T.rte = pw(p, raw + 2); T.maxin = pw(p, raw + 4); T.maxout = pw(p, raw + 5);
     T.irte = pw(p, der); T.icap = pw(p, der + 1); T.capl = pw(p, der + 2);
 }
 
-template <bool FULL>
-CL_DEV void load_bp(Bp& B, const uint32_t* __restrict__ p) {
+// `t`: the block the words are read through -- `p` itself, or `p` as a cl_ctab (B.p stays the plain pointer)
+template <bool FULL, class P>
+CL_DEV void load_bp_from(Bp& B, const uint32_t* __restrict__ p, P t) {
     B.p = p;
-    B.flags = p[CLP_L_FLAGS]; B.a_es = (int)p[CLP_L_ACT_ES];
-    B.r = pw(p, CLP_L_TSR); B.rw_exponent = pw(p, CLP_L_RW_EXPONENT);
+    B.flags = t[CLP_L_FLAGS]; B.a_es = (int)t[CLP_L_ACT_ES];
+    B.r = pw(t, CLP_L_TSR); B.rw_exponent = pw(t, CLP_L_RW_EXPONENT);
     if constexpr (!FULL) {
-        load_batt(B.batt, p);
+        load_batt_from(B.batt, t);
     } else {
-        B.dt = pw(p, CLP_DT_HOURS);
-        B.cd_pow = pw(p, CLP_CD_POW); B.hd_pow = pw(p, CLP_HD_POW); B.dd_pow = pw(p, CLP_DD_POW);
-        B.t0_iheat_div = pw(p, CLP_T0_IHEAT_DIV); B.dyn_warmup = pw(p, CLP_DYN_WARMUP);
-        B.a_cs = (int)p[CLP_ACT_COOL_STO]; B.a_hs = (int)p[CLP_ACT_HEAT_STO]; B.a_ds = (int)p[CLP_ACT_DHW_STO];
-        B.a_cd = (int)p[CLP_ACT_COOL_DEV]; B.a_hd = (int)p[CLP_ACT_HEAT_DEV]; B.a_coh = (int)p[CLP_ACT_COH_DEV];
+        B.dt = pw(t, CLP_DT_HOURS);
+        B.cd_pow = pw(t, CLP_CD_POW); B.hd_pow = pw(t, CLP_HD_POW); B.dd_pow = pw(t, CLP_DD_POW);
+        B.t0_iheat_div = pw(t, CLP_T0_IHEAT_DIV); B.dyn_warmup = pw(t, CLP_DYN_WARMUP);
+        B.a_cs = (int)t[CLP_ACT_COOL_STO]; B.a_hs = (int)t[CLP_ACT_HEAT_STO]; B.a_ds = (int)t[CLP_ACT_DHW_STO];
+        B.a_cd = (int)t[CLP_ACT_COOL_DEV]; B.a_hd = (int)t[CLP_ACT_HEAT_DEV]; B.a_coh = (int)t[CLP_ACT_COH_DEV];
     }
 }
+template <bool FULL>
+CL_DEV void load_bp(Bp& B, const uint32_t* __restrict__ p) { load_bp_from<FULL>(B, p, p); }
 
 // Time-series row of (t, building): wave-uniform.
 // (Field order: values that sit next to each other in the table -- load / solar, price / carbon -- are kept apart here.  With them
@@ -696,15 +702,16 @@ CL_DEV float unit_reward(int kind, const Bp& B, const State& S, float net) {
 }
 
 // unit_reward<false> for the N envs of a lane with the (wave-uniform) switch outside the env loop: same expressions, same bits.
-template <int N>
-CL_DEV void lean_rewards(int kind, const Bp& B, const float (&soc)[N], const float (&net)[N], float (&rw)[N]) {
+// (`t`: the building's parameter block -- B.p, or B.p as a cl_ctab, as in load_bp_from)
+template <int N, class P>
+CL_DEV void lean_rewards_from(int kind, const Bp& B, P t, const float (&soc)[N], const float (&net)[N], float (&rw)[N]) {
     switch (kind) {
     case CLR_INDEPENDENT_SAC:
 #pragma unroll
         for (int i = 0; i < N; ++i) rw[i] = fminf(-net[i], 0.0f);
         break;
     case CLR_SOLAR_PENALTY: {
-        const bool has = pw(B.p, CLP_L_CAP) > CL_ZDP;
+        const bool has = pw(t, CLP_L_CAP) > CL_ZDP;
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             const float sg = net[i] > 0.0f ? 1.0f : (net[i] < 0.0f ? -1.0f : 0.0f), an = fabsf(net[i]);
@@ -725,6 +732,10 @@ CL_DEV void lean_rewards(int kind, const Bp& B, const float (&soc)[N], const flo
             for (int i = 0; i < N; ++i) rw[i] = -__powf(fmaxf(net[i], 0.0f), B.rw_exponent);
         }
     }
+}
+template <int N>
+CL_DEV void lean_rewards(int kind, const Bp& B, const float (&soc)[N], const float (&net)[N], float (&rw)[N]) {
+    lean_rewards_from<N>(kind, B, B.p, soc, net, rw);
 }
 
 CL_DEV float marl_reward(float net, float district_net) {

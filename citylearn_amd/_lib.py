@@ -77,6 +77,12 @@ class PolicyFullMLP(ctypes.Structure):
                 ('seed', ctypes.c_uint64)]
 
 
+class PolicyDeepMLP(ctypes.Structure):
+    """``clpd_mlp`` (include/citylearn_amd_policy_deep.h): the packed tables of a per-building MLP policy with two hidden layers
+    (`policy.DeepMLPPolicy.pack`) -- `PolicyMLP`'s fields, then the second layer's."""
+    _fields_ = [*PolicyMLP._fields_, ('n_hidden2', ctypes.c_int32), ('reserved2', ctypes.c_int32), ('l2', ctypes.c_void_p)]
+
+
 def _compile(sources, out: Path, deps, force: bool, verbose: bool) -> Path:
     """`sources`: paths, or (path, extra flags) pairs -- translation units with flags of their own are compiled to objects first."""
     if not force and out.exists() and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
@@ -220,6 +226,11 @@ CHUNK_KPI_EXTENSIONS = (POLICY_FULL_CHUNK_KPI,)
 # `__graft_entry__.build()` builds ALL_EXTENSIONS + CHUNK_KPI_EXTENSIONS + LEAN_CHUNK_EXTENSIONS.
 POLICY_CHUNK = _Extension('policy_chunk', 'clpc', 'chunked policy', ['-fno-slp-vectorize'], 'rollout_mlp_f32', PolicyMLP, headers=[POLICY.header])
 LEAN_CHUNK_EXTENSIONS = (POLICY_CHUNK,)
+# ... and the battery + PV one whose policy has TWO hidden layers (cl_policy_deep.hip, without SLP vectorisation like cl_policy.hip; `clpd_mlp`,
+# which is `clpol_mlp` + the second layer).  A tuple of its own again: `__graft_entry__.build()` builds ALL_EXTENSIONS + CHUNK_KPI_EXTENSIONS +
+# LEAN_CHUNK_EXTENSIONS + DEEP_EXTENSIONS.
+POLICY_DEEP = _Extension('policy_deep', 'clpd', 'deep policy', ['-fno-slp-vectorize'], 'rollout_mlp_f32', PolicyDeepMLP, headers=[POLICY.header])
+DEEP_EXTENSIONS = (POLICY_DEEP,)
 
 # The names other code and the tests use: read-only views of the descriptions above (build / load / check read the description, so rebinding one
 # of these changes nothing -- change the description's attribute instead)
@@ -252,6 +263,22 @@ def policy_kpi_lds_bytes(nw: int, vec: int) -> int:
     policy's staged rows [nw][2][3 x 32 + 8] (tests/test_policy_kpi_host.py holds it against the header's formula)."""
     tile = 64 * vec
     return 4 * (8 * nw * tile + 12 * tile + 16 + 8 * 4 * 32 + 5 * 32 + nw * 2 * (3 * 32 + 8))
+
+
+def policy_deep_lds_bytes(nw: int, h1: int, h2: int) -> int:
+    """Dynamic LDS of one `cl_rollout_policy_deep_kernel` workgroup of ``nw`` waves (two buildings each, one env per lane) at ``h1`` x ``h2``
+    hidden units: csrc/cl_policy_deep.h's `rollout_policy_deep_lds_floats` -- the reduction rows [nw][4][64], then per building the staged row
+    [h1 / 4][2][4] + [h1 + 1][h2] + [h2] + 8 -- 164 864 bytes at sixteen waves and 32 x 32, which the library refuses (a CU has 163 840)."""
+    return 4 * (nw * 4 * 64 + nw * 2 * (2 * h1 + (h1 + 1) * h2 + h2 + 8))
+
+
+LDS_PER_CU = 160 * 1024        # csrc/cl_rollout.h's CL_LDS_PER_CU: what the policy entries hold a workgroup's dynamic LDS against
+
+
+def policy_deep_mma_lds_bytes(nw: int) -> int:
+    """... and of its matrix-core family (`clpd_mlp.flags & CLPD_MATRIX_CORES`): the reduction rows, then per building the staged row
+    [32] x 4 + 8 + the A fragments [2][2][64][4] = 1160 floats at every h1, h2 -- 154 560 bytes at fifteen waves (30 buildings), 164 864 at sixteen."""
+    return 4 * (nw * 4 * 64 + nw * 2 * 1160)
 
 
 def policy_chunk_lds_bytes(nw: int, vec: int) -> int:

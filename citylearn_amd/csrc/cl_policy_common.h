@@ -1,6 +1,6 @@
-// cl_policy_common.h -- what the seven closed-loop policy units share (cl_policy.hip, cl_policy_kpi.hip, cl_policy_chunk.hip for battery + PV
-// districts; cl_policy_full.hip, cl_policy_full_kpi.hip, cl_policy_full_chunk.hip, cl_policy_full_chunk_kpi.hip for thermal ones; each behind
-// cl_kernels.hip's helpers and cl_rollout.h).  The ONE copy of each:
+// cl_policy_common.h -- what the eight closed-loop policy units share (cl_policy.hip, cl_policy_kpi.hip, cl_policy_chunk.hip, cl_policy_deep.hip
+// for battery + PV districts; cl_policy_full.hip, cl_policy_full_kpi.hip, cl_policy_full_chunk.hip, cl_policy_full_chunk_kpi.hip for thermal ones;
+// each behind cl_kernels.hip's helpers and cl_rollout.h).  The ONE copy of each:
 //   device  PolicyArgs, the hidden unit's activation (clpol_unit), the Box-Muller draw (clpol_gauss);
 //   host    the three entry points every library exports besides its rollout (CL_POLICY_ABI);
 //           the coverage refusals whose text is the same up to the entry's name (no_f64_maps, no_reward_ev, no_chunked_marl, no_detail_planes,

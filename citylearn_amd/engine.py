@@ -561,7 +561,17 @@ class StepEngine:
         steps are cut into windows of at most ``self.policy_kpi_window`` (64) steps, one call each -- ``traj`` and the step index advance,
         ``ret_env`` accumulates -- so that the scratch stays ``window x 2 x n_chunks x n_env`` floats: 64 MB at 1024 buildings x 1024 envs instead
         of 755 MB for a 720-step launch.  The windows do not show in the result: state, outputs, record and every KPI plane are bit for bit what
-        one call leaves.  ``chunked=True, kpi=False`` on a ``kpi=True`` engine stays `clpfc_rollout_mlp_f32`'s refusal."""
+        one call leaves.  ``chunked=True, kpi=False`` on a ``kpi=True`` engine stays `clpfc_rollout_mlp_f32`'s refusal.
+
+        ``policy_tables`` from `policy.DeepMLPPolicy.pack` (a `DeepPolicyTables`: TWO hidden layers of 4 .. 32 units each) sends a battery + PV
+        district of up to 32 buildings to `cl_rollout_policy_deep_kernel` (`clpd_rollout_mlp_f32`, ``libcitylearn_amd_policy_deep.so``): the
+        steps, record ``[k_steps, CLPOL_NT, n_bldg, n_env]`` and noise stream of `cl_rollout_policy_kernel`, one env per lane.  Tables packed with
+        ``matrix_cores=False`` run layer 2 in exact fp32 from weights the waves keep in LDS (`<1, PREC, 0>`); tables packed with
+        ``matrix_cores=True`` run it on the f16 matrix cores with split operands (`<1, PREC, 1>`), whose LDS rows have the 32 x 32 size at every
+        H1, H2 -- that family is the library's refusal from 31 buildings up (``pack(matrix_cores=None)`` never picks it there).  No MARL, no thermal district, no more than 32 buildings and no ``kpi=True`` engine (the
+        library's refusals; 32 buildings at 32 x 32 units exceed a CU's LDS and are refused too); ``chunked=True`` is the `ValueError` above (no
+        chunked kernel at all) and ``kpi=True`` a `NotImplementedError` that names the route: record, then replay the action plane on a
+        ``kpi=True`` engine."""
         kind = policy_tables.kind           # (`policy._Kind`: the libraries, the trajectory's plane count and what a build without KPIs raises)
         ext_chunk = kind.ext_chunk or kind.ext_chunk_pair
         if chunked and (ext_chunk is None or (kind.ext_chunk is None and not self.dims.flags & abi.CLD_LEAN)):
@@ -572,6 +582,10 @@ class StepEngine:
             raise NotImplementedError(f'rollout_policy(chunked=True, kpi=True) with {type(policy_tables).__name__}: there is no chunked lean KPI kernel -- the '
                                       'building-chunked battery + PV policy launch keeps no streaming KPI accumulators.  Record the rollout (traj) and feed '
                                       'its action plane through step_many() on a second engine built with kpi=True')
+        if kpi and kind.ext_kpi is None:
+            raise NotImplementedError(f'rollout_policy(kpi=True) with {type(policy_tables).__name__}: there is no KPI kernel for a policy with two hidden '
+                                      'layers.  Record the rollout (traj) and replay its action plane (policy.CLPOL_T_ACTION) through '
+                                      'rollout(actions=..., fused=True) on a second engine built with kpi=True')
         if kpi and not self.kpi and kind.no_kpi_error is NotImplementedError:
             raise NotImplementedError('rollout_policy(kpi=True) with StoragePolicyTables: this engine was built without the streaming KPI accumulators -- '
                                       'build it with kpi=True (the thermal policy KPI kernel, cl_rollout_full_policy_kpi_kernel, needs them)')

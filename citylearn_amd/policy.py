@@ -1,5 +1,6 @@
-"""A closed-loop policy INSIDE the fused K-step rollout: a one-hidden-layer tanh MLP per building over that building's own observation
-vector, evaluated by `cl_rollout_policy_kernel` (csrc/cl_policy.h, ``libcitylearn_amd_policy.so``, include/citylearn_amd_policy.h).
+"""A closed-loop policy INSIDE the fused K-step rollout: a tanh MLP with one hidden layer (or two: `DeepMLPPolicy`, below) per building
+over that building's own observation vector, evaluated by `cl_rollout_policy_kernel` (csrc/cl_policy.h, ``libcitylearn_amd_policy.so``,
+include/citylearn_amd_policy.h).
 
 Inference of a GIVEN policy only -- no training, no agent: the weights come from the caller (a learner in torch, an evolution strategy that
 scores a population of controllers by return: one parameter set per block of ``abi.CL_ROW0_BLOCK`` envs).
@@ -71,7 +72,22 @@ policy, same noise stream, same record ``[k_steps, CLPOL_NT, n_bldg, n_envs]``. 
 with `PolicyTables` raises `NotImplementedError`): score such a district by the replay above -- record, then `StepEngine.step_many` of the action
 plane on a second, ``kpi=True`` engine.
 
-Open: device-action heads, streaming KPIs in the chunked battery + PV launch, and MARL in chunked launches (the libraries' refusal).
+An actor with TWO hidden layers (the SAC / PPO actors of the CityLearn examples) is a `DeepMLPPolicy`: ``h1 = tanh(W1 obs + b1)``,
+``h2 = tanh(W2 h1 + b2)``, ``a = clamp(mid + half tanh(w3 . h2 + b3) + sigma z, low, high)`` with H1, H2 in 4, 8, .. 32, on battery + PV districts
+of up to 32 buildings: one launch of `cl_rollout_policy_deep_kernel` (csrc/cl_policy_deep.h, ``libcitylearn_amd_policy_deep.so``,
+include/citylearn_amd_policy_deep.h) through the same `rollout_policy` call, with `MLPPolicy`'s record ``[k_steps, CLPOL_NT, n_bldg, n_envs]`` and
+noise stream:
+
+    deep = DeepMLPPolicy(w1, b1, w2, b2, w3, b3, sigma=0.1)        # w2 [n_sets, n_bldg, H2, H1], w3 [n_sets, n_bldg, H2]
+    ret, traj = env.rollout_policy(deep, 24, seed=3, record=True)
+
+Layer 2 runs in exact fp32 or, ``pack(matrix_cores=True)``, on the f16 matrix cores with split operands; ``matrix_cores=None`` (what the env
+uses) is `default_matrix_cores`: the family profiles/policy_deep_probe.log shows faster.  No streaming KPIs (``kpi=True`` raises
+`NotImplementedError`: record, then replay the action plane on a ``kpi=True`` env as above), no chunked launch (more than 32 buildings is the
+library's refusal), no MARL, no thermal district.
+
+Open: device-action heads, streaming KPIs in the chunked battery + PV launch, MARL in chunked launches (the libraries' refusal); for the deep
+policy a KPI twin, a chunked twin, MARL, thermal districts, hidden layers wider than 32 or deeper than two.
 """
 from __future__ import annotations
 
@@ -108,6 +124,9 @@ CLPF_T_ACTION, CLPF_T_REWARD, CLPF_T_NET, CLPF_T_SOC = (FULL_CONSTANTS[k] for k 
 CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET = (FULL_CONSTANTS[k] for k in ('CLPF_D_SOC', 'CLPF_D_CS', 'CLPF_D_HS', 'CLPF_D_DS', 'CLPF_D_NET'))
 CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS = (FULL_CONSTANTS[k] for k in ('CLPF_A_ES', 'CLPF_A_CS', 'CLPF_A_HS', 'CLPF_A_DS'))
 assert FULL_CONSTANTS['CLPF_NOISE_KEY'] == CLPOL_NOISE_KEY                       # `noise_host` replays both kernels' streams
+# two hidden layers (csrc/cl_policy_deep.h, libcitylearn_amd_policy_deep.so): the record and the noise stream are the lean kernel's
+DEEP_CONSTANTS = _header_constants(_lib.POLICY_DEEP.header, 'CLPD_')
+CLPD_MAX_HIDDEN, CLPD_MATRIX_CORES = DEEP_CONSTANTS['CLPD_MAX_HIDDEN'], DEEP_CONSTANTS['CLPD_MATRIX_CORES']
 HEAD_NAMES = ('electrical_storage', 'cooling_storage', 'heating_storage', 'dhw_storage')                  # heads in CLPF_A_* order
 
 
@@ -182,6 +201,70 @@ class StoragePolicyTables(_Tables):
     """`StorageMLPPolicy.pack`'s result (`_Tables`), ``[n_bldg, CLPF_NA]`` on the host side."""
 
 
+class DeepPolicyTables(_Tables):
+    """`DeepMLPPolicy.pack`'s result: `PolicyTables`' members for the first layer (``pre`` / ``dep``), then the second layer ``l2`` in the layout
+    of the kernel family ``matrix_cores`` names, and ``out = [w3 | b3]`` ``[n_sets, n_bldg, H2 + 1]``.  ``n_hidden`` is H1, ``n_hidden2`` H2.
+
+    ``matrix_cores=False`` (exact fp32): ``l2 [n_sets, n_bldg, H1 + 1, H2]`` -- ``ACT_SCALE * W2`` TRANSPOSED (one row per first-layer unit: the
+    H2 weights the kernel's inner loop reads are consecutive), ``ACT_SCALE * b2`` as the last row.
+
+    ``matrix_cores=True`` (f16 matrix cores, split operands): ``l2 [n_sets, n_bldg, 1024 + 32 + 4]`` -- the A-operand fragments of
+    ``W' = sw * ACT_SCALE * W2`` zero-padded to 32 x 32, ``[kk][term][lane][8]`` f16 (two per float32 word) with element ``[lane][j]`` = term of
+    ``W'[lane & 31][16 kk + 8 (lane >> 5) + j]``, terms ``A0 = f16(W')``, ``A1 = f16(2^11 (W' - A0))`` (`l2_fragments` reads them back); then
+    ``2^12 * sw * ACT_SCALE * b2`` zero-padded to 32; then ``inv = 2^-12 / sw`` and three zeros.  ``sw`` is the power of two that puts the
+    building's largest ``|ACT_SCALE * W2|`` into ``[2^13, 2^14)``: no f16 term that matters is subnormal (csrc/cl_policy_deep.h says why)."""
+
+    def __init__(self, pre, dep, l2, out, net_reset, act_low, act_high, sigma, set_of_block, es_cols, low_bldg, high_bldg, sigma_bldg, version,
+                 matrix_cores=False):
+        super().__init__(pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, es_cols, low_bldg, high_bldg, sigma_bldg, 0, version)
+        self.l2, self.n_hidden2, self.matrix_cores = l2, int(out.shape[-1]) - 1, bool(matrix_cores)
+
+    es_cols = property(lambda self: self.cols)
+
+    def struct(self, seed: int):
+        p = lambda t: None if t is None else t.data_ptr()
+        return self.kind.struct(self.n_hidden, self.n_sets, CLPD_MATRIX_CORES if self.matrix_cores else 0, 0, p(self.pre), p(self.dep), p(self.out),
+                                p(self.set_of_block), p(self.net_reset), p(self.act_low), p(self.act_high), p(self.sigma), int(seed) & (2 ** 64 - 1),
+                                self.n_hidden2, 0, p(self.l2))
+
+    def l2_fragments(self) -> np.ndarray:
+        """``matrix_cores=True``: the two f16 terms ``A0``, ``A1`` reassembled from the fragments as they are stored, float32
+        ``[2, n_sets, n_bldg, 32, 32]`` (term, then ``[unit of layer 2][unit of layer 1]``): ``(A0 + 2^-11 A1) * 2^12 * inv`` is
+        ``ACT_SCALE * W2``, with ``inv = l2[..., 1056]``."""
+        raw = np.ascontiguousarray(self.l2.cpu().numpy()[:, :, :1024]).view(np.float16).reshape(self.n_sets, self.n_bldg, 2, 2, 64, 8)
+        lane, j = np.arange(64), np.arange(8)
+        w = np.zeros((2, self.n_sets, self.n_bldg, 32, 32), dtype=np.float32)
+        for kk in range(2):
+            k = 16 * kk + 8 * (lane[:, None] >> 5) + j[None, :]
+            for term in range(2):
+                w[term][:, :, (lane & 31)[:, None], k] = raw[:, :, kk, term].astype(np.float32)
+        return w
+
+
+def _l2_fragments(w2s: np.ndarray, b2s: np.ndarray) -> np.ndarray:
+    """The matrix-core layout of layer 2 (`DeepPolicyTables`) from the scaled weights ``[S, B, H2, H1]`` and biases ``[S, B, H2]`` (float64):
+    float32 ``[S, B, 1024 + 32 + 4]``."""
+    S, B, H2, H1 = w2s.shape
+    amax = np.abs(w2s).reshape(S, B, -1).max(axis=2)
+    if not np.all(np.isfinite(amax)):
+        raise ValueError('w2 is not finite')
+    sw = 2.0 ** np.clip(13 - np.floor(np.log2(np.where(amax > 0, amax, 1.0))), -100, 100)         # amax * sw in [2^13, 2^14)
+    W = np.zeros((S, B, 32, 32), dtype=np.float32)
+    W[:, :, :H2, :H1] = (w2s * sw[:, :, None, None]).astype(np.float32)
+    lane, j = np.arange(64), np.arange(8)
+    frag = np.zeros((S, B, 2, 2, 64, 8), dtype=np.float16)
+    for kk in range(2):
+        k = 16 * kk + 8 * (lane[:, None] >> 5) + j[None, :]                     # [64, 8]: the first-layer unit of (lane, slot)
+        x = W[:, :, (lane & 31)[:, None], k]                                    # [S, B, 64, 8]
+        t0 = x.astype(np.float16)
+        frag[:, :, kk, 0] = t0
+        frag[:, :, kk, 1] = ((x - t0.astype(np.float32)) * np.float32(2048.0)).astype(np.float16)      # (residual and scaling exact in fp32)
+    tail = np.zeros((S, B, 32 + 4), dtype=np.float32)
+    tail[:, :, :H2] = b2s * (4096.0 * sw[:, :, None])
+    tail[:, :, 32] = 1.0 / (4096.0 * sw)
+    return np.concatenate([frag.reshape(S, B, -1).view(np.float32), tail], axis=2)
+
+
 @dataclass(frozen=True)
 class _Kind:
     """What tells the two policies apart, as data -- the packer, the references and `rollout_policy` read it and are written once."""
@@ -196,7 +279,7 @@ class _Kind:
     max_hidden: int
     n_planes: int                     # of a recorded trajectory
     ext: '_lib._Extension'            # the rollout library, and the one that also keeps the streaming KPIs
-    ext_kpi: '_lib._Extension'
+    ext_kpi: Optional['_lib._Extension']              # (None: the kind has no KPI kernel -- `rollout_policy(kpi=True)` raises NotImplementedError)
     no_kpi_error: type                # what `rollout_policy(kpi=True)` raises on a build without KPIs
     ext_chunk: Optional['_lib._Extension'] = None      # the building-chunked rollout library (`rollout_policy(chunked=True)`), where the kind has one
     ext_chunk_kpi: Optional['_lib._Extension'] = None  # ... and the one that also keeps the streaming KPIs (`rollout_policy(chunked=True, kpi=True)`)
@@ -222,6 +305,10 @@ _THERMAL = _Kind(terms=(((SRC_STATE, abi.CLS_B_SOC), abi.CLF_BATTERY), ((SRC_STA
                  tables=StoragePolicyTables, struct=_lib.PolicyFullMLP, constants=FULL_CONSTANTS, max_hidden=CLPF_MAX_HIDDEN, n_planes=CLPF_NT,
                  ext=_lib.POLICY_FULL, ext_kpi=_lib.POLICY_FULL_KPI, no_kpi_error=NotImplementedError, ext_chunk=_lib.POLICY_FULL_CHUNK,
                  ext_chunk_kpi=_lib.POLICY_FULL_CHUNK_KPI, one_row_max=16)
+# two hidden layers: the lean kind's inputs, head, record and one-row geometry; a library of its own and neither a KPI nor a chunked twin
+_DEEP = _Kind(terms=_LEAN.terms, head_slots=_LEAN.head_slots, head_shape=(), refuse_device_actions=False, only=_LEAN.only, tables=DeepPolicyTables,
+              struct=_lib.PolicyDeepMLP, constants=DEEP_CONSTANTS, max_hidden=CLPD_MAX_HIDDEN, n_planes=CLPOL_NT, ext=_lib.POLICY_DEEP, ext_kpi=None,
+              no_kpi_error=NotImplementedError, one_row_max=32)
 # (terms and heads above are written in the header's order)
 assert (CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET) == tuple(range(CLPF_ND)) and (CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS) == tuple(range(CLPF_NA))
 
@@ -455,3 +542,149 @@ class StorageMLPPolicy(_MLPBase):
         each head's sigma.  The heads' columns, bounds and sigmas come from ``tables`` (a `pack` result).  Nothing is remembered between calls."""
         a = self._actions_host(obs_vectors, tables.low_bldg, tables.high_bldg, noise, lambda: tables.sigma_bldg, set_index)
         return np.where(tables.cols >= 0, a, 0.0)
+
+
+def default_matrix_cores(n_hidden: int, n_hidden2: int, n_bldg: Optional[int] = None) -> bool:
+    """What `DeepMLPPolicy.pack(matrix_cores=None)` resolves to: the matrix-core family where the probe's logs show it faster than the exact-fp32
+    one by more than the spread (max - min) of its own seven repetitions AND its launch fits, the exact-fp32 family -- the fallback -- everywhere
+    else.
+
+    Fit: a matrix-core row is 1160 floats per building at every H1, H2, two rows per wave, so the sixteen waves of 31 or 32 buildings need
+    164 864 bytes of LDS with the reduction rows and the library refuses them (a CU has 163 840; `_lib.policy_deep_mma_lds_bytes`).  With
+    ``n_bldg`` given (`pack` gives it) such a district gets the exact-fp32 family, whose rows follow H1, H2: 32 buildings fit up to 32 x 28.
+
+    The rule: ``H1 * H2 >= 512``.  The matrix-core kernel always computes the zero-padded 32 x 32 problem and costs the same at every size --
+    19.2 - 19.6 us per step at 17 x 32 768 with the record under the float64 chain -- while the exact-fp32 kernel's cost follows H1 * H2:
+    8.50 us at (8, 8), 16.87 at (16, 16), 26.95 / 26.79 at (16, 32) / (32, 16), 28.51 at (24, 24), 35.98 / 35.59 at (24, 32) / (32, 24), 40.67 at
+    (32, 28), 44.89 at (32, 32).  Every measured shape with H1 * H2 >= 512 reads "matrix_cores_faster_beyond_its_spread: 8 of 8 cases" (two batch
+    sizes x two precision models x record off / on), (8, 8) and (16, 16) read "0 of 8" (profiles/policy_deep_probe.log: (16, 16), (32, 32);
+    profiles/policy_deep_probe_shapes.log: the others).  Between 256 and 512 nothing is measured, so the exact-fp32 family stays."""
+    fits = n_bldg is None or _lib.policy_deep_mma_lds_bytes((int(n_bldg) + 1) // 2) <= _lib.LDS_PER_CU
+    return n_hidden * n_hidden2 >= 512 and fits
+
+
+class DeepMLPPolicy:
+    """`MLPPolicy` with TWO hidden layers -- the shape of the SAC / PPO actors of the CityLearn examples -- per building:
+
+        h1 = tanh(W1 obs + b1),   h2 = tanh(W2 h1 + b2),   a = clamp(mid + half tanh(w3 . h2 + b3) + sigma z, low, high)
+
+    `obs`, the bounds, z and the env-dependent inputs (the building's own ``electrical_storage_soc`` and ``net_electricity_consumption``) are
+    `MLPPolicy`'s.  Battery + PV districts of up to 32 buildings: one launch of `cl_rollout_policy_deep_kernel` (csrc/cl_policy_deep.h,
+    ``libcitylearn_amd_policy_deep.so``).
+
+    ``w1 [n_sets, n_bldg, H1, n_obs]``, ``b1 [n_sets, n_bldg, H1]``, ``w2 [n_sets, n_bldg, H2, H1]``, ``b2 [n_sets, n_bldg, H2]``,
+    ``w3 [n_sets, n_bldg, H2]``, ``b3 [n_sets, n_bldg]`` (anything array-like; kept in float64); a leading dimension of 1 broadcasts.  ``H1``,
+    ``H2``: 4, 8, .. 32, independent of each other.  ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
+
+    The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
+    kind = _DEEP
+    _NAMES = ('w1', 'b1', 'w2', 'b2', 'w3', 'b3')
+
+    def __init__(self, w1, b1, w2, b2, w3, b3, sigma=None):
+        self.w1, self.b1, self.w2, self.b2, self.w3, self.b3 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2, w3, b3))
+        if [getattr(self, n).ndim for n in self._NAMES] != [4, 3, 4, 3, 3, 2]:
+            raise ValueError('w1 [n_sets, n_bldg, H1, n_obs], b1 [n_sets, n_bldg, H1], w2 [n_sets, n_bldg, H2, H1], b2 [n_sets, n_bldg, H2], '
+                             'w3 [n_sets, n_bldg, H2], b3 [n_sets, n_bldg]')
+        self.n_hidden, self.n_obs, self.n_hidden2 = int(self.w1.shape[2]), int(self.w1.shape[3]), int(self.w2.shape[2])
+        for name, h in (('H1', self.n_hidden), ('H2', self.n_hidden2)):
+            if h % 4 or not 4 <= h <= CLPD_MAX_HIDDEN:
+                raise ValueError(f'{name}={h}: the deep policy kernel takes 4, 8, .. {CLPD_MAX_HIDDEN} units per hidden layer')
+        if self.b1.shape[2] != self.n_hidden or self.w2.shape[3] != self.n_hidden:
+            raise ValueError('b1 / w2 disagree with w1 about H1')
+        if self.b2.shape[2] != self.n_hidden2 or self.w3.shape[2] != self.n_hidden2:
+            raise ValueError('b2 / w3 disagree with w2 about H2')
+        self.n_sets = max(getattr(self, n).shape[0] for n in self._NAMES)
+        self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
+        self.version = 0
+
+    def invalidate(self) -> None:
+        """Tell the caches that the weights changed (see `MLPPolicy`'s docstring)."""
+        self.version += 1
+
+    def update(self, w1=None, b1=None, w2=None, b2=None, w3=None, b3=None, sigma=None) -> None:
+        """Replace some of the weight arrays (same shapes) and / or sigma, and bump `version`: the learner's step between two rollouts."""
+        for name, v in zip(self._NAMES, (w1, b1, w2, b2, w3, b3)):
+            if v is not None:
+                v = np.asarray(v, dtype=np.float64)
+                if v.shape != getattr(self, name).shape:
+                    raise ValueError(f'{name}: shape {v.shape} != {getattr(self, name).shape}')
+                setattr(self, name, v)
+        if sigma is not None:
+            self.sigma = np.asarray(sigma, dtype=np.float64)
+        self.invalidate()
+
+    def _full(self, n_bldg: int):
+        S, H1, H2 = self.n_sets, self.n_hidden, self.n_hidden2
+        shapes = ((S, n_bldg, H1, self.n_obs), (S, n_bldg, H1), (S, n_bldg, H2, H1), (S, n_bldg, H2), (S, n_bldg, H2), (S, n_bldg))
+        try:
+            return tuple(np.broadcast_to(getattr(self, n), sh) for n, sh in zip(self._NAMES, shapes))
+        except ValueError as e:
+            raise ValueError(f'the weights do not broadcast to {S} sets x {n_bldg} buildings: {e}') from None
+
+    # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
+    def actions_host(self, obs_vectors, noise=None, tables: Optional[DeepPolicyTables] = None, low=None, high=None, sigma_bldg=None,
+                     set_index: int = 0) -> np.ndarray:
+        """float64 numpy evaluation of the plain MLP: ``obs_vectors [..., n_bldg, n_obs]`` -> actions ``[..., n_bldg]``; the arguments are
+        `MLPPolicy.actions_host`'s."""
+        pick = lambda arg, attr, default: np.asarray(arg if arg is not None else getattr(tables, attr) if tables is not None else default, dtype=np.float64)
+        x = np.asarray(obs_vectors, dtype=np.float64)
+        w1, b1, w2, b2, w3, b3 = (v[set_index] for v in self._full(x.shape[-2]))
+        h1 = np.tanh(np.einsum('bjc,...bc->...bj', w1, x) + b1)
+        h2 = np.tanh(np.einsum('bij,...bj->...bi', w2, h1) + b2)
+        lo, hi = pick(low, 'low_bldg', -1.0), pick(high, 'high_bldg', 1.0)
+        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('bi,...bi->...b', w3, h2) + b3)
+        if noise is not None:
+            if sigma_bldg is None and tables is None and self.sigma is not None and self.sigma.ndim:
+                raise ValueError('a per-column sigma needs `tables` (or `sigma_bldg`): which column drives which building')
+            a = a + pick(sigma_bldg, 'sigma_bldg', 0.0 if self.sigma is None or self.sigma.ndim else float(self.sigma)) * np.asarray(noise, dtype=np.float64)
+        return np.clip(a, lo, hi)
+
+    def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
+        """The same MLP (no noise) written in torch over the env's observation TENSOR: a `VectorCityLearnEnv.capture_rollout` policy
+        ``f(obs [n_envs, n_obs_total], i=None) -> actions [n_act_cols, n_envs]``, as `MLPPolicy.torch_policy`."""
+        cols = building_columns(layout)
+        w1, b1, w2, b2, w3, b3 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(len(cols)))
+        idx = torch.as_tensor(np.array([c + [c[0]] * (self.n_obs - len(c)) for c in cols]), device=device)
+        mask = torch.as_tensor(np.array([[1.0] * len(c) + [0.0] * (self.n_obs - len(c)) for c in cols]), dtype=dtype, device=device)
+        hc = _head_columns(tab, self.kind)
+        low, high = layout.spec.action_limits()
+        sel = np.nonzero(hc >= 0)[0]                                             # the buildings that have a storage column
+        rows, bsel = torch.as_tensor(hc[sel], device=device), torch.as_tensor(sel, device=device)
+        lo = torch.as_tensor(np.asarray(low)[hc[sel]], dtype=dtype, device=device)
+        hi = torch.as_tensor(np.asarray(high)[hc[sel]], dtype=dtype, device=device)
+        n_act = len(low)
+
+        def f(obs, i=None):
+            x = obs.to(dtype)[:, idx] * mask                                     # [E, B, n_obs]
+            h1 = torch.tanh(torch.einsum('bjc,ebc->ebj', w1, x) + b1)
+            h2 = torch.tanh(torch.einsum('bij,ebj->ebi', w2, h1) + b2)
+            o = torch.tanh((w3 * h2).sum(dim=-1) + b3)[:, bsel]                  # [E, driven buildings]
+            a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
+            out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
+            out[rows] = a.t().to(torch.float32)
+            return out
+        return f
+
+    # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
+    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None, matrix_cores=None) -> DeepPolicyTables:
+        """The first layer split exactly as `MLPPolicy.pack` splits it (the same code and the same refusals: a one-hidden-layer policy over
+        W1 / b1 is packed and its ``pre`` / ``dep`` / bounds / sigma taken), then ``l2`` and ``out`` as `DeepPolicyTables` describes them, in
+        float64 rounded once.  ``matrix_cores``: the kernel family of layer 2 -- False: exact fp32 (`cl_rollout_policy_deep_kernel<1, PREC, 0>`);
+        True: the f16 matrix cores with both operands split into two f16 terms (`<1, PREC, 1>`: the action moves by at most the split's
+        3 x 2^-22 sum |W2| per layer-2 sum, see tests/policy_deep_util.py `split_bound`); None: `default_matrix_cores(H1, H2, n_bldg)`
+        -- the faster family by the probe's logs that fits this district."""
+        S, H1 = self.n_sets, self.n_hidden
+        front = MLPPolicy(self.w1, self.b1, np.zeros((S, 1, H1)), np.zeros((1, 1)), sigma=self.sigma)
+        ft = front.pack(layout, tab, device=device, set_of_block=set_of_block)
+        if matrix_cores is None:
+            matrix_cores = default_matrix_cores(self.n_hidden, self.n_hidden2, ft.n_bldg)
+        _, _, w2, b2, w3, b3 = self._full(ft.n_bldg)
+        dev = torch.device(device)
+        f64 = lambda v: torch.from_numpy(np.array(v, dtype=np.float64)).to(dev)
+        if matrix_cores:
+            l2 = torch.from_numpy(_l2_fragments(np.array(w2) * ACT_SCALE, np.array(b2) * ACT_SCALE)).to(dev)
+        else:
+            l2 = (torch.cat([f64(w2).transpose(2, 3), f64(b2)[:, :, None, :]], dim=2) * ACT_SCALE).to(torch.float32)
+        out = torch.cat([f64(w3), f64(b3)[..., None]], dim=-1)
+        return DeepPolicyTables(ft.pre, ft.dep, l2.contiguous(), out.to(torch.float32).contiguous(), ft.net_reset, ft.act_low, ft.act_high,
+                                ft.sigma, ft.set_of_block, ft.cols, ft.low_bldg, ft.high_bldg, ft.sigma_bldg, self.version, matrix_cores=matrix_cores)

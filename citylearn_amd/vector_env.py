@@ -444,8 +444,16 @@ class VectorCityLearnEnv:
         A BATTERY + PV district of MORE than 32 buildings (the 1024-building tiling of the 2022 schema) with an `MLPPolicy` is routed by itself
         too: `cl_rollout_policy_chunk_kernel` + one `cl_finish_kernel` (`StepEngine.rollout_policy(chunked=True)` with `PolicyTables`), same
         policy, record and noise stream.  That launch keeps no streaming KPIs: ``kpi=True`` there raises `NotImplementedError` (record, then replay
-        the action plane on a ``kpi=True`` env), and MARL is the library's refusal."""
+        the action plane on a ``kpi=True`` env), and MARL is the library's refusal.
+
+        A `policy.DeepMLPPolicy` (TWO hidden layers) drives a battery + PV district of up to 32 buildings through
+        `cl_rollout_policy_deep_kernel`, same record and noise stream as an `MLPPolicy`.  More than 32 buildings, a thermal district and a MARL
+        reward are the library's refusals; ``kpi=True`` raises `NotImplementedError` (record, then replay the action plane on a ``kpi=True`` env)."""
         chunked = (policy.kind.ext_chunk or policy.kind.ext_chunk_pair) is not None and self.engine.n_bldg > policy.kind.one_row_max
+        if kpi and policy.kind.ext_kpi is None:
+            raise NotImplementedError(f'rollout_policy(kpi=True) with a {type(policy).__name__}: there is no KPI kernel for a policy with two hidden '
+                                      'layers -- record the rollout (record=True) and replay its action plane (policy.CLPOL_T_ACTION) through '
+                                      'rollout(actions=..., fused=True) on an env built with kpi=True')
         if kpi and not self.kpi and policy.kind.no_kpi_error is NotImplementedError:
             raise NotImplementedError('rollout_policy(kpi=True) with a StorageMLPPolicy: this env was built without the streaming KPI accumulators -- '
                                       'build it with VectorCityLearnEnv(..., kpi=True)')

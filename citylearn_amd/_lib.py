@@ -83,6 +83,13 @@ class PolicyDeepMLP(ctypes.Structure):
     _fields_ = [*PolicyMLP._fields_, ('n_hidden2', ctypes.c_int32), ('reserved2', ctypes.c_int32), ('l2', ctypes.c_void_p)]
 
 
+class PolicyFullDeepMLP(ctypes.Structure):
+    """``clpfd_mlp`` (include/citylearn_amd_policy_full_deep.h): the packed tables of a per-building storage MLP policy with two hidden layers
+    (`policy.DeepStorageMLPPolicy.pack`) -- `PolicyFullMLP`'s fields, then the second layer's (``flags``: 0 or ``CLPFD_MATRIX_CORES``;
+    `PolicyFullMLP` has no flags word)."""
+    _fields_ = [*PolicyFullMLP._fields_, ('n_hidden2', ctypes.c_int32), ('flags', ctypes.c_int32), ('l2', ctypes.c_void_p)]
+
+
 def _compile(sources, out: Path, deps, force: bool, verbose: bool) -> Path:
     """`sources`: paths, or (path, extra flags) pairs -- translation units with flags of their own are compiled to objects first."""
     if not force and out.exists() and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
@@ -231,6 +238,13 @@ LEAN_CHUNK_EXTENSIONS = (POLICY_CHUNK,)
 # LEAN_CHUNK_EXTENSIONS + DEEP_EXTENSIONS.
 POLICY_DEEP = _Extension('policy_deep', 'clpd', 'deep policy', ['-fno-slp-vectorize'], 'rollout_mlp_f32', PolicyDeepMLP, headers=[POLICY.header])
 DEEP_EXTENSIONS = (POLICY_DEEP,)
+# ... and the THERMAL one whose policy has two hidden layers (cl_policy_full_deep.hip; `clpfd_mlp`, which is `clpf_mlp` + the second layer).
+# Without SLP vectorisation, unlike cl_policy_full.hip: with it the exact-fp32 policy block spills to scratch memory (the translation unit says
+# how).  A tuple of its own: `__graft_entry__.build()` builds ALL_EXTENSIONS + CHUNK_KPI_EXTENSIONS + LEAN_CHUNK_EXTENSIONS + DEEP_EXTENSIONS +
+# DEEP_THERMAL_EXTENSIONS.
+POLICY_FULL_DEEP = _Extension('policy_full_deep', 'clpfd', 'deep thermal policy', ['-fno-slp-vectorize'], 'rollout_mlp_f32', PolicyFullDeepMLP,
+                              headers=[POLICY_FULL.header])
+DEEP_THERMAL_EXTENSIONS = (POLICY_FULL_DEEP,)
 
 # The names other code and the tests use: read-only views of the descriptions above (build / load / check read the description, so rebinding one
 # of these changes nothing -- change the description's attribute instead)
@@ -279,6 +293,15 @@ def policy_deep_mma_lds_bytes(nw: int) -> int:
     """... and of its matrix-core family (`clpd_mlp.flags & CLPD_MATRIX_CORES`): the reduction rows, then per building the staged row
     [32] x 4 + 8 + the A fragments [2][2][64][4] = 1160 floats at every h1, h2 -- 154 560 bytes at fifteen waves (30 buildings), 164 864 at sixteen."""
     return 4 * (nw * 4 * 64 + nw * 2 * 1160)
+
+
+def policy_full_deep_lds_bytes(nw: int, h1: int, h2: int, matrix_cores: bool = False) -> int:
+    """Dynamic LDS of one `cl_rollout_full_policy_deep_kernel` workgroup of ``nw`` waves (= buildings, one env per lane) at ``h1`` x ``h2`` hidden
+    units: csrc/cl_policy_full_deep.h's `rollout_full_policy_deep_lds_floats` -- the reduction rows [nw][4][64], then per building the staged row
+    [h1 / 4][5][4] + [h1 + 1][h2] + [4][h2] + 4 x 8, or in the matrix-core family [5][32] + [32] + [4][32] + 4 x 8 + the A fragments
+    [2][2][64][4] = 1376 floats at every h1, h2 (the exact family's row at 32 x 32) -- 104 448 bytes at sixteen waves and 32 x 32."""
+    row = 1376 if matrix_cores else 5 * h1 + (h1 + 1) * h2 + 4 * h2 + 32
+    return 4 * (nw * 4 * 64 + nw * row)
 
 
 def policy_chunk_lds_bytes(nw: int, vec: int) -> int:

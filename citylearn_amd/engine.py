@@ -571,7 +571,15 @@ class StepEngine:
         H1, H2 -- that family is the library's refusal from 31 buildings up (``pack(matrix_cores=None)`` never picks it there).  No MARL, no thermal district, no more than 32 buildings and no ``kpi=True`` engine (the
         library's refusals; 32 buildings at 32 x 32 units exceed a CU's LDS and are refused too); ``chunked=True`` is the `ValueError` above (no
         chunked kernel at all) and ``kpi=True`` a `NotImplementedError` that names the route: record, then replay the action plane on a
-        ``kpi=True`` engine."""
+        ``kpi=True`` engine.
+
+        ``policy_tables`` from `policy.DeepStorageMLPPolicy.pack` (a `DeepStoragePolicyTables`: two hidden layers and up to four storage heads)
+        sends a THERMAL district of up to 16 buildings to `cl_rollout_full_policy_deep_kernel` (`clpfd_rollout_mlp_f32`,
+        ``libcitylearn_amd_policy_full_deep.so``): the steps, record ``[k_steps, CLPF_NT, n_bldg, n_env]`` and noise stream of
+        `cl_rollout_full_policy_kernel` at one env per lane, layer 2 in exact fp32 (`<PREC, 0, MARL>`) or on the f16 matrix cores
+        (`<PREC, 1, MARL>`) as the tables were packed; every reward kind of the thermal kernel, MARL included, in both families.  A battery + PV
+        district, more than 16 buildings and a ``kpi=True`` engine are the library's refusals; ``chunked=True`` is the `ValueError` above and
+        ``kpi=True`` the `NotImplementedError` that names the route: record, then replay the heads' action planes on a ``kpi=True`` engine."""
         kind = policy_tables.kind           # (`policy._Kind`: the libraries, the trajectory's plane count and what a build without KPIs raises)
         ext_chunk = kind.ext_chunk or kind.ext_chunk_pair
         if chunked and (ext_chunk is None or (kind.ext_chunk is None and not self.dims.flags & abi.CLD_LEAN)):
@@ -583,8 +591,10 @@ class StepEngine:
                                       'building-chunked battery + PV policy launch keeps no streaming KPI accumulators.  Record the rollout (traj) and feed '
                                       'its action plane through step_many() on a second engine built with kpi=True')
         if kpi and kind.ext_kpi is None:
+            planes = ('its action plane (policy.CLPOL_T_ACTION)' if not kind.head_shape else
+                      "its action planes (policy.CLPF_T_ACTION + head, each head's plane into its action column: policy.head_columns)")
             raise NotImplementedError(f'rollout_policy(kpi=True) with {type(policy_tables).__name__}: there is no KPI kernel for a policy with two hidden '
-                                      'layers.  Record the rollout (traj) and replay its action plane (policy.CLPOL_T_ACTION) through '
+                                      f'layers.  Record the rollout (traj) and replay {planes} through '
                                       'rollout(actions=..., fused=True) on a second engine built with kpi=True')
         if kpi and not self.kpi and kind.no_kpi_error is NotImplementedError:
             raise NotImplementedError('rollout_policy(kpi=True) with StoragePolicyTables: this engine was built without the streaming KPI accumulators -- '

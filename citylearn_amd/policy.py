@@ -84,10 +84,23 @@ noise stream:
 Layer 2 runs in exact fp32 or, ``pack(matrix_cores=True)``, on the f16 matrix cores with split operands; ``matrix_cores=None`` (what the env
 uses) is `default_matrix_cores`: the family profiles/policy_deep_probe.log shows faster.  No streaming KPIs (``kpi=True`` raises
 `NotImplementedError`: record, then replay the action plane on a ``kpi=True`` env as above), no chunked launch (more than 32 buildings is the
-library's refusal), no MARL, no thermal district.
+library's refusal), no MARL.
+
+On a THERMAL district of up to 16 buildings the actor with two hidden layers is a `DeepStorageMLPPolicy`: the same two layers with
+`StorageMLPPolicy`'s four heads, five env-dependent inputs, record ``[k_steps, CLPF_NT, n_bldg, n_envs]`` and noise stream -- one launch of
+`cl_rollout_full_policy_deep_kernel` (csrc/cl_policy_full_deep.h, ``libcitylearn_amd_policy_full_deep.so``,
+include/citylearn_amd_policy_full_deep.h), one env per lane, one building per wave, every reward kind of the thermal kernel (MARL included):
+
+    sdeep = DeepStorageMLPPolicy(w1, b1, w2, b2, w3, b3, sigma=0.1)    # w2 [n_sets, n_bldg, H2, H1], w3 [n_sets, n_bldg, 4, H2], b3 [n_sets, n_bldg, 4]
+    ret, traj = env.rollout_policy(sdeep, 24, seed=3, record=True)
+
+Layer 2 again in exact fp32 or on the f16 matrix cores; ``matrix_cores=None`` is `default_thermal_matrix_cores`, a rule measured on THIS kernel
+(profiles/policy_full_deep_probe.log).  No streaming KPIs (``kpi=True`` raises `NotImplementedError`: record, then replay the heads' action
+planes on a ``kpi=True`` env), no chunked launch (more than 16 buildings is the library's refusal).
 
 Open: device-action heads, streaming KPIs in the chunked battery + PV launch, MARL in chunked launches (the libraries' refusal); for the deep
-policy a KPI twin, a chunked twin, MARL, thermal districts, hidden layers wider than 32 or deeper than two.
+policy a KPI twin, a chunked twin, MARL, hidden layers wider than 32 or deeper than two; for the deep thermal policy a KPI twin, more than 16
+buildings, device-action heads, two envs per lane, hidden layers wider than 32 or deeper than two.
 """
 from __future__ import annotations
 
@@ -127,6 +140,10 @@ assert FULL_CONSTANTS['CLPF_NOISE_KEY'] == CLPOL_NOISE_KEY                      
 # two hidden layers (csrc/cl_policy_deep.h, libcitylearn_amd_policy_deep.so): the record and the noise stream are the lean kernel's
 DEEP_CONSTANTS = _header_constants(_lib.POLICY_DEEP.header, 'CLPD_')
 CLPD_MAX_HIDDEN, CLPD_MATRIX_CORES = DEEP_CONSTANTS['CLPD_MAX_HIDDEN'], DEEP_CONSTANTS['CLPD_MATRIX_CORES']
+# two hidden layers on a thermal district (csrc/cl_policy_full_deep.h, libcitylearn_amd_policy_full_deep.so): the record and the noise stream are
+# the thermal kernel's
+FULL_DEEP_CONSTANTS = _header_constants(_lib.POLICY_FULL_DEEP.header, 'CLPFD_')
+CLPFD_MAX_HIDDEN, CLPFD_MATRIX_CORES = FULL_DEEP_CONSTANTS['CLPFD_MAX_HIDDEN'], FULL_DEEP_CONSTANTS['CLPFD_MATRIX_CORES']
 HEAD_NAMES = ('electrical_storage', 'cooling_storage', 'heating_storage', 'dhw_storage')                  # heads in CLPF_A_* order
 
 
@@ -241,6 +258,26 @@ class DeepPolicyTables(_Tables):
         return w
 
 
+class DeepStoragePolicyTables(_Tables):
+    """`DeepStorageMLPPolicy.pack`'s result: `StoragePolicyTables`' members for the first layer (``pre`` / ``dep [n_sets, n_bldg, CLPF_ND, H1]``) and
+    the host side ``[n_bldg, CLPF_NA]``, then the second layer ``l2`` in the layout of the kernel family ``matrix_cores`` names -- the two layouts
+    of `DeepPolicyTables`, layer 2 is the same matrix problem -- and ``out = [w3 | b3]`` ``[n_sets, n_bldg, CLPF_NA, H2 + 1]``.  ``n_hidden`` is H1,
+    ``n_hidden2`` H2."""
+
+    def __init__(self, pre, dep, l2, out, net_reset, act_low, act_high, sigma, set_of_block, cols, low_bldg, high_bldg, sigma_bldg, version,
+                 matrix_cores=False):
+        super().__init__(pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, cols, low_bldg, high_bldg, sigma_bldg, 0, version)
+        self.l2, self.n_hidden2, self.matrix_cores = l2, int(out.shape[-1]) - 1, bool(matrix_cores)
+
+    def struct(self, seed: int):
+        p = lambda t: None if t is None else t.data_ptr()
+        return self.kind.struct(self.n_hidden, self.n_sets, self.n_device_cols, 0, p(self.pre), p(self.dep), p(self.out), p(self.set_of_block),
+                                p(self.net_reset), p(self.act_low), p(self.act_high), p(self.sigma), int(seed) & (2 ** 64 - 1),
+                                self.n_hidden2, CLPFD_MATRIX_CORES if self.matrix_cores else 0, p(self.l2))
+
+    l2_fragments = DeepPolicyTables.l2_fragments
+
+
 def _l2_fragments(w2s: np.ndarray, b2s: np.ndarray) -> np.ndarray:
     """The matrix-core layout of layer 2 (`DeepPolicyTables`) from the scaled weights ``[S, B, H2, H1]`` and biases ``[S, B, H2]`` (float64):
     float32 ``[S, B, 1024 + 32 + 4]``."""
@@ -309,6 +346,11 @@ _THERMAL = _Kind(terms=(((SRC_STATE, abi.CLS_B_SOC), abi.CLF_BATTERY), ((SRC_STA
 _DEEP = _Kind(terms=_LEAN.terms, head_slots=_LEAN.head_slots, head_shape=(), refuse_device_actions=False, only=_LEAN.only, tables=DeepPolicyTables,
               struct=_lib.PolicyDeepMLP, constants=DEEP_CONSTANTS, max_hidden=CLPD_MAX_HIDDEN, n_planes=CLPOL_NT, ext=_lib.POLICY_DEEP, ext_kpi=None,
               no_kpi_error=NotImplementedError, one_row_max=32)
+# two hidden layers on a thermal district: the thermal kind's inputs, heads, record and one-row geometry; a library of its own and neither a KPI nor
+# a chunked twin
+_DEEP_THERMAL = _Kind(terms=_THERMAL.terms, head_slots=_THERMAL.head_slots, head_shape=_THERMAL.head_shape, refuse_device_actions=True, only=_THERMAL.only,
+                      tables=DeepStoragePolicyTables, struct=_lib.PolicyFullDeepMLP, constants=FULL_DEEP_CONSTANTS, max_hidden=CLPFD_MAX_HIDDEN,
+                      n_planes=CLPF_NT, ext=_lib.POLICY_FULL_DEEP, ext_kpi=None, no_kpi_error=NotImplementedError, one_row_max=16)
 # (terms and heads above are written in the header's order)
 assert (CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET) == tuple(range(CLPF_ND)) and (CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS) == tuple(range(CLPF_NA))
 
@@ -688,3 +730,136 @@ class DeepMLPPolicy:
         out = torch.cat([f64(w3), f64(b3)[..., None]], dim=-1)
         return DeepPolicyTables(ft.pre, ft.dep, l2.contiguous(), out.to(torch.float32).contiguous(), ft.net_reset, ft.act_low, ft.act_high,
                                 ft.sigma, ft.set_of_block, ft.cols, ft.low_bldg, ft.high_bldg, ft.sigma_bldg, self.version, matrix_cores=matrix_cores)
+
+
+def default_thermal_matrix_cores(n_hidden: int, n_hidden2: int, n_bldg: Optional[int] = None) -> bool:
+    """What `DeepStorageMLPPolicy.pack(matrix_cores=None)` resolves to: the matrix-core family exactly where profiles/policy_full_deep_probe.log
+    shows it faster than the exact-fp32 one by more than the spread (max - min) of its own seven repetitions in EVERY measured case of that shape,
+    the exact-fp32 family -- the arithmetic reference -- everywhere else.  `default_matrix_cores`'s rule (H1 * H2 >= 512) is NOT inherited: that
+    one was measured on another kernel (two buildings per wave, two inputs, one head, the lean unit).  Both families fit a CU's LDS at every
+    accepted geometry (`_lib.policy_full_deep_lds_bytes`: 104 448 bytes at sixteen buildings), so ``n_bldg`` does not enter.
+
+    The rule: ``H1 * H2 >= 512``.  The matrix-core kernel always computes the zero-padded 32 x 32 problem and costs the same at every size --
+    16.6 - 17.0 us per step at 9 x 32 768 with the record under the float64 chain -- while the exact-fp32 kernel's cost follows H1 * H2: 9.21 us
+    at (8, 8), 13.60 at (16, 16), 15.49 / 15.79 at (16, 24) / (24, 16), 15.73 at (20, 20), 16.00 / 17.11 at (16, 28) / (28, 16), 16.80 / 17.18 at
+    (20, 24) / (24, 20), 17.16 / 18.53 at (16, 32) / (32, 16), 18.45 at (24, 24), 24.71 at (32, 32).  The four measured shapes with
+    H1 * H2 >= 512 -- (16, 32), (32, 16), (24, 24), (32, 32) -- read "matrix_cores_faster_beyond_its_spread: 8 of 8 cases" (two batch sizes x two
+    precision models x record off / on; profiles/policy_full_deep_probe.log, which also has (8, 8) and (16, 16): "0 of 8").  Below 512 no shape
+    reads 8 of 8: (16, 24), (24, 16), (20, 20), (16, 28) "0 of 8", (20, 24) "1 of 8", (28, 16) and (24, 20) "3 of 8"
+    (profiles/policy_full_deep_probe_shapes.log) -- near 450 the two families cost the same within their spreads, and the exact one stays.  No
+    admissible product lies between 480 and 512."""
+    return n_hidden * n_hidden2 >= 512
+
+
+class DeepStorageMLPPolicy:
+    """`StorageMLPPolicy` with TWO hidden layers -- the shape of the SAC / PPO actors of the CityLearn examples -- per building and head a, the heads
+    in the fixed order electrical, cooling, heating, DHW storage (`HEAD_NAMES`):
+
+        h1 = tanh(W1 obs + b1),   h2 = tanh(W2 h1 + b2),   act_a = clamp(mid_a + half_a tanh(w3[a] . h2 + b3[a]) + sigma_a z_a, low_a, high_a)
+
+    `obs`, the five env-dependent inputs (the building's own four storage socs and ``net_electricity_consumption``), the heads' columns, bounds,
+    sigma and the noise stream are `StorageMLPPolicy`'s; the heads of columns a building lacks are ignored.  Thermal districts without the LSTM
+    stage and without device actions of up to 16 buildings: one launch of `cl_rollout_full_policy_deep_kernel` (csrc/cl_policy_full_deep.h,
+    ``libcitylearn_amd_policy_full_deep.so``).
+
+    ``w1 [n_sets, n_bldg, H1, n_obs]``, ``b1 [n_sets, n_bldg, H1]``, ``w2 [n_sets, n_bldg, H2, H1]``, ``b2 [n_sets, n_bldg, H2]``,
+    ``w3 [n_sets, n_bldg, 4, H2]``, ``b3 [n_sets, n_bldg, 4]`` (anything array-like; kept in float64); a leading dimension of 1 broadcasts.
+    ``H1``, ``H2``: 4, 8, .. 32, independent of each other.  ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
+
+    The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
+    kind = _DEEP_THERMAL
+    _NAMES = DeepMLPPolicy._NAMES
+
+    def __init__(self, w1, b1, w2, b2, w3, b3, sigma=None):
+        self.w1, self.b1, self.w2, self.b2, self.w3, self.b3 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2, w3, b3))
+        if [getattr(self, n).ndim for n in self._NAMES] != [4, 3, 4, 3, 4, 3]:
+            raise ValueError('w1 [n_sets, n_bldg, H1, n_obs], b1 [n_sets, n_bldg, H1], w2 [n_sets, n_bldg, H2, H1], b2 [n_sets, n_bldg, H2], '
+                             f'w3 [n_sets, n_bldg, {CLPF_NA}, H2], b3 [n_sets, n_bldg, {CLPF_NA}]')
+        self.n_hidden, self.n_obs, self.n_hidden2 = int(self.w1.shape[2]), int(self.w1.shape[3]), int(self.w2.shape[2])
+        for name, h in (('H1', self.n_hidden), ('H2', self.n_hidden2)):
+            if h % 4 or not 4 <= h <= CLPFD_MAX_HIDDEN:
+                raise ValueError(f'{name}={h}: the deep thermal policy kernel takes 4, 8, .. {CLPFD_MAX_HIDDEN} units per hidden layer')
+        if self.b1.shape[2] != self.n_hidden or self.w2.shape[3] != self.n_hidden:
+            raise ValueError('b1 / w2 disagree with w1 about H1')
+        if self.b2.shape[2] != self.n_hidden2 or self.w3.shape[2:] != (CLPF_NA, self.n_hidden2) or self.b3.shape[2:] != (CLPF_NA,):
+            raise ValueError(f'b2 / w3 disagree with w2 about H2, or w3 / b3 do not have {CLPF_NA} heads')
+        self.n_sets = max(getattr(self, n).shape[0] for n in self._NAMES)
+        self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
+        self.version = 0
+
+    invalidate = DeepMLPPolicy.invalidate
+    update = DeepMLPPolicy.update
+
+    def _full(self, n_bldg: int):
+        S, H1, H2 = self.n_sets, self.n_hidden, self.n_hidden2
+        shapes = ((S, n_bldg, H1, self.n_obs), (S, n_bldg, H1), (S, n_bldg, H2, H1), (S, n_bldg, H2), (S, n_bldg, CLPF_NA, H2), (S, n_bldg, CLPF_NA))
+        try:
+            return tuple(np.broadcast_to(getattr(self, n), sh) for n, sh in zip(self._NAMES, shapes))
+        except ValueError as e:
+            raise ValueError(f'the weights do not broadcast to {S} sets x {n_bldg} buildings: {e}') from None
+
+    # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
+    def actions_host(self, obs_vectors, tables: DeepStoragePolicyTables, noise=None, set_index: int = 0) -> np.ndarray:
+        """float64 numpy evaluation of the plain MLP: ``obs_vectors [..., n_bldg, n_obs]`` -> actions ``[..., n_bldg, 4]`` (0 for a head whose
+        column the building lacks); the arguments are `StorageMLPPolicy.actions_host`'s."""
+        x = np.asarray(obs_vectors, dtype=np.float64)
+        w1, b1, w2, b2, w3, b3 = (v[set_index] for v in self._full(x.shape[-2]))
+        h1 = np.tanh(np.einsum('bjc,...bc->...bj', w1, x) + b1)
+        h2 = np.tanh(np.einsum('bij,...bj->...bi', w2, h1) + b2)
+        lo, hi = tables.low_bldg, tables.high_bldg
+        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('bai,...bi->...ba', w3, h2) + b3)
+        if noise is not None:
+            a = a + tables.sigma_bldg * np.asarray(noise, dtype=np.float64)
+        return np.where(tables.cols >= 0, np.clip(a, lo, hi), 0.0)
+
+    def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
+        """The same MLP (no noise) written in torch over the env's observation TENSOR: a `VectorCityLearnEnv.capture_rollout` policy
+        ``f(obs [n_envs, n_obs_total], i=None) -> actions [n_act_cols, n_envs]``, as `StorageMLPPolicy.torch_policy`."""
+        cols = building_columns(layout)
+        w1, b1, w2, b2, w3, b3 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(len(cols)))
+        idx = torch.as_tensor(np.array([c + [c[0]] * (self.n_obs - len(c)) for c in cols]), device=device)
+        mask = torch.as_tensor(np.array([[1.0] * len(c) + [0.0] * (self.n_obs - len(c)) for c in cols]), dtype=dtype, device=device)
+        hc = _head_columns(tab, self.kind)
+        low, high = layout.spec.action_limits()
+        sel = np.nonzero(hc >= 0)                                                # the heads that have a column
+        rows = torch.as_tensor(hc[sel], device=device)
+        lo = torch.as_tensor(np.asarray(low)[hc[sel]], dtype=dtype, device=device)
+        hi = torch.as_tensor(np.asarray(high)[hc[sel]], dtype=dtype, device=device)
+        flat = torch.as_tensor(np.ravel_multi_index(sel, hc.shape), device=device)
+        n_act = len(low)
+
+        def f(obs, i=None):
+            x = obs.to(dtype)[:, idx] * mask                                     # [E, B, n_obs]
+            h1 = torch.tanh(torch.einsum('bjc,ebc->ebj', w1, x) + b1)
+            h2 = torch.tanh(torch.einsum('bij,ebj->ebi', w2, h1) + b2)
+            o = torch.tanh(torch.einsum('bai,ebi->eba', w3, h2) + b3).reshape(obs.shape[0], -1)[:, flat]         # [E, present heads]
+            a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
+            out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
+            out[rows] = a.t().to(torch.float32)
+            return out
+        return f
+
+    # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
+    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None, matrix_cores=None) -> DeepStoragePolicyTables:
+        """The first layer split exactly as `StorageMLPPolicy.pack` splits it (the same code and the same refusals, device-action columns
+        included: a one-hidden-layer storage policy over W1 / b1 is packed and its ``pre`` / ``dep`` / bounds / sigma taken), then ``l2`` and
+        ``out`` as `DeepStoragePolicyTables` describes them, in float64 rounded once -- layer 2 exactly as `DeepMLPPolicy.pack` hands it over.
+        ``matrix_cores``: the kernel family of layer 2 -- False: exact fp32 (`cl_rollout_full_policy_deep_kernel<PREC, 0, MARL>`); True: the f16
+        matrix cores with both operands split into two f16 terms (`<PREC, 1, MARL>`: every head's action moves by at most the split's bound,
+        tests/policy_full_deep_util.py `split_bound`); None: `default_thermal_matrix_cores(H1, H2, n_bldg)`."""
+        S, H1 = self.n_sets, self.n_hidden
+        front = StorageMLPPolicy(self.w1, self.b1, np.zeros((S, 1, CLPF_NA, H1)), np.zeros((1, 1, CLPF_NA)), sigma=self.sigma)
+        ft = front.pack(layout, tab, device=device, set_of_block=set_of_block)
+        if matrix_cores is None:
+            matrix_cores = default_thermal_matrix_cores(self.n_hidden, self.n_hidden2, ft.n_bldg)
+        _, _, w2, b2, w3, b3 = self._full(ft.n_bldg)
+        dev = torch.device(device)
+        f64 = lambda v: torch.from_numpy(np.array(v, dtype=np.float64)).to(dev)
+        if matrix_cores:
+            l2 = torch.from_numpy(_l2_fragments(np.array(w2) * ACT_SCALE, np.array(b2) * ACT_SCALE)).to(dev)
+        else:
+            l2 = (torch.cat([f64(w2).transpose(2, 3), f64(b2)[:, :, None, :]], dim=2) * ACT_SCALE).to(torch.float32)
+        out = torch.cat([f64(w3), f64(b3)[..., None]], dim=-1)
+        return DeepStoragePolicyTables(ft.pre, ft.dep, l2.contiguous(), out.to(torch.float32).contiguous(), ft.net_reset, ft.act_low, ft.act_high,
+                                       ft.sigma, ft.set_of_block, ft.cols, ft.low_bldg, ft.high_bldg, ft.sigma_bldg, self.version,
+                                       matrix_cores=matrix_cores)

@@ -448,11 +448,18 @@ class VectorCityLearnEnv:
 
         A `policy.DeepMLPPolicy` (TWO hidden layers) drives a battery + PV district of up to 32 buildings through
         `cl_rollout_policy_deep_kernel`, same record and noise stream as an `MLPPolicy`.  More than 32 buildings, a thermal district and a MARL
-        reward are the library's refusals; ``kpi=True`` raises `NotImplementedError` (record, then replay the action plane on a ``kpi=True`` env)."""
+        reward are the library's refusals; ``kpi=True`` raises `NotImplementedError` (record, then replay the action plane on a ``kpi=True`` env).
+
+        A `policy.DeepStorageMLPPolicy` (two hidden layers, up to four storage heads) drives a THERMAL district of up to 16 buildings through
+        `cl_rollout_full_policy_deep_kernel`, same record (`policy.CLPF_NT` planes) and noise stream as a `StorageMLPPolicy`, MARL included.  More
+        than 16 buildings and a battery + PV district are the library's refusals; ``kpi=True`` raises `NotImplementedError` (record, then replay
+        the heads' action planes on a ``kpi=True`` env)."""
         chunked = (policy.kind.ext_chunk or policy.kind.ext_chunk_pair) is not None and self.engine.n_bldg > policy.kind.one_row_max
         if kpi and policy.kind.ext_kpi is None:
+            planes = ('its action plane (policy.CLPOL_T_ACTION)' if not policy.kind.head_shape else
+                      "its action planes (policy.CLPF_T_ACTION + head, each head's plane into its action column: policy.head_columns)")
             raise NotImplementedError(f'rollout_policy(kpi=True) with a {type(policy).__name__}: there is no KPI kernel for a policy with two hidden '
-                                      'layers -- record the rollout (record=True) and replay its action plane (policy.CLPOL_T_ACTION) through '
+                                      f'layers -- record the rollout (record=True) and replay {planes} through '
                                       'rollout(actions=..., fused=True) on an env built with kpi=True')
         if kpi and not self.kpi and policy.kind.no_kpi_error is NotImplementedError:
             raise NotImplementedError('rollout_policy(kpi=True) with a StorageMLPPolicy: this env was built without the streaming KPI accumulators -- '

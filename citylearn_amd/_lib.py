@@ -245,6 +245,11 @@ DEEP_EXTENSIONS = (POLICY_DEEP,)
 POLICY_FULL_DEEP = _Extension('policy_full_deep', 'clpfd', 'deep thermal policy', ['-fno-slp-vectorize'], 'rollout_mlp_f32', PolicyFullDeepMLP,
                               headers=[POLICY_FULL.header])
 DEEP_THERMAL_EXTENSIONS = (POLICY_FULL_DEEP,)
+# ... and the battery + PV one under a CENTRAL-AGENT policy: one MLP over the district's observation vector (cl_policy_central.hip, without SLP
+# vectorisation like cl_policy.hip; `clpca_mlp` has `clpol_mlp`'s fields, so `PolicyMLP` serves it -- only the shapes of pre / dep differ).  A tuple
+# of its own: the tuples above stay what they are; `__graft_entry__.build()` builds it behind them.
+POLICY_CENTRAL = _Extension('policy_central', 'clpca', 'central policy', ['-fno-slp-vectorize'], 'rollout_mlp_f32', PolicyMLP, headers=[POLICY.header])
+CENTRAL_EXTENSIONS = (POLICY_CENTRAL,)
 
 # The names other code and the tests use: read-only views of the descriptions above (build / load / check read the description, so rebinding one
 # of these changes nothing -- change the description's attribute instead)
@@ -302,6 +307,15 @@ def policy_full_deep_lds_bytes(nw: int, h1: int, h2: int, matrix_cores: bool = F
     [2][2][64][4] = 1376 floats at every h1, h2 (the exact family's row at 32 x 32) -- 104 448 bytes at sixteen waves and 32 x 32."""
     row = 1376 if matrix_cores else 5 * h1 + (h1 + 1) * h2 + 4 * h2 + 32
     return 4 * (nw * 4 * 64 + nw * row)
+
+
+def policy_central_lds_bytes(nw: int, n_bldg: int, h: int) -> int:
+    """Dynamic LDS of one `cl_rollout_policy_central_kernel` workgroup of ``nw`` waves (two buildings each, one env per lane) over ``n_bldg``
+    buildings at ``h`` hidden units: include/citylearn_amd_policy_central.h's formula (csrc/cl_policy_central.h's
+    `rollout_policy_central_lds_floats`) -- the reduction rows [nw][4][64], the published soc / net planes X [2][n_bldg][64], the hidden layer
+    Hh [h][64], the staged ``dep`` [h / 4][n_bldg][8], the staged out rows [nw][2][64 + 8] -- 74 752 bytes at sixteen waves, 32 buildings and 64
+    units (tests/test_policy_central_host.py holds it against the header's formula)."""
+    return 4 * (nw * 4 * 64 + 2 * n_bldg * 64 + h * 64 + 2 * h * n_bldg + nw * 2 * (64 + 8))
 
 
 def policy_chunk_lds_bytes(nw: int, vec: int) -> int:

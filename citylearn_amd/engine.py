@@ -579,7 +579,15 @@ class StepEngine:
         `cl_rollout_full_policy_kernel` at one env per lane, layer 2 in exact fp32 (`<PREC, 0, MARL>`) or on the f16 matrix cores
         (`<PREC, 1, MARL>`) as the tables were packed; every reward kind of the thermal kernel, MARL included, in both families.  A battery + PV
         district, more than 16 buildings and a ``kpi=True`` engine are the library's refusals; ``chunked=True`` is the `ValueError` above and
-        ``kpi=True`` the `NotImplementedError` that names the route: record, then replay the heads' action planes on a ``kpi=True`` engine."""
+        ``kpi=True`` the `NotImplementedError` that names the route: record, then replay the heads' action planes on a ``kpi=True`` engine.
+
+        ``policy_tables`` from `policy.CentralMLPPolicy.pack` (a `CentralPolicyTables`: ONE hidden layer of 4 .. 64 units over the district's
+        central-agent observation vector, one head per driven building) sends a battery + PV district of up to 32 buildings to
+        `cl_rollout_policy_central_kernel` (`clpca_rollout_mlp_f32`, ``libcitylearn_amd_policy_central.so``): the steps, record
+        ``[k_steps, CLPOL_NT, n_bldg, n_env]`` and noise stream of `cl_rollout_policy_kernel` at one env per lane, every lean reward kind, MARL
+        included; ``tuning=dict(nw=...)`` changes no action, net or soc.  A thermal district, more than 32 buildings and a ``kpi=True`` engine
+        are the library's refusals; ``chunked=True`` is the `ValueError` above and ``kpi=True`` a `NotImplementedError` of its own wording:
+        record, then replay the action plane on a ``kpi=True`` engine."""
         kind = policy_tables.kind           # (`policy._Kind`: the libraries, the trajectory's plane count and what a build without KPIs raises)
         ext_chunk = kind.ext_chunk or kind.ext_chunk_pair
         if chunked and (ext_chunk is None or (kind.ext_chunk is None and not self.dims.flags & abi.CLD_LEAN)):
@@ -590,6 +598,10 @@ class StepEngine:
             raise NotImplementedError(f'rollout_policy(chunked=True, kpi=True) with {type(policy_tables).__name__}: there is no chunked lean KPI kernel -- the '
                                       'building-chunked battery + PV policy launch keeps no streaming KPI accumulators.  Record the rollout (traj) and feed '
                                       'its action plane through step_many() on a second engine built with kpi=True')
+        if kpi and kind.ext_kpi is None and kind.central:
+            raise NotImplementedError(f'rollout_policy(kpi=True) with {type(policy_tables).__name__}: a central-agent policy has no KPI kernel.  Record '
+                                      'the rollout (traj) and replay its action plane (policy.CLPOL_T_ACTION) through rollout(actions=..., fused=True) '
+                                      'on a second engine built with kpi=True')
         if kpi and kind.ext_kpi is None:
             planes = ('its action plane (policy.CLPOL_T_ACTION)' if not kind.head_shape else
                       "its action planes (policy.CLPF_T_ACTION + head, each head's plane into its action column: policy.head_columns)")

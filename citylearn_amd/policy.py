@@ -98,9 +98,27 @@ Layer 2 again in exact fp32 or on the f16 matrix cores; ``matrix_cores=None`` is
 (profiles/policy_full_deep_probe.log).  No streaming KPIs (``kpi=True`` raises `NotImplementedError`: record, then replay the heads' action
 planes on a ``kpi=True`` env), no chunked launch (more than 16 buildings is the library's refusal).
 
+CityLearn's other mode, ``central_agent=True`` -- ONE actor that sees the district's observation vector and returns every building's action, what
+the Stable-Baselines3 route needs -- is a `CentralMLPPolicy`: ``h = tanh(W1 obs + b1)`` over ``ObservationLayout(..., central_agent=True).columns``
+with H in 4, 8, .. 64, then one head per building that has a storage action, ``a_b = clamp(mid_b + half_b tanh(w2[b] . h + b2[b]) + sigma_b z,
+low_b, high_b)``.  Battery + PV districts of up to 32 buildings, every lean reward kind (MARL included): one launch of
+`cl_rollout_policy_central_kernel` (csrc/cl_policy_central.h, ``libcitylearn_amd_policy_central.so``, include/citylearn_amd_policy_central.h) through
+the same `rollout_policy` call of an env built with ``central_agent=True``, with `MLPPolicy`'s record ``[k_steps, CLPOL_NT, n_bldg, n_envs]``, bounds,
+sigma and noise stream:
+
+    cenv = VectorCityLearnEnv(schema, n_envs, observations='tensor', normalize_observations=True, central_agent=True)
+    central = CentralMLPPolicy(w1, b1, w2, b2, sigma=0.1)          # w1 [n_sets, H, n_cols], b1 [n_sets, H], w2 [n_sets, n_bldg, H], b2 [n_sets, n_bldg]
+    ret, traj = cenv.rollout_policy(central, 24, seed=3, record=True)
+
+The hidden layer sums over ALL buildings' soc and previous net, so the kernel exchanges them through LDS with two workgroup barriers per step; the
+sums have a fixed order and ``tuning=dict(nw=...)`` changes no action.  An env built with ``central_agent=False`` raises `ValueError` (its
+observation tensor is not the vector the weights are defined over); ``kpi=True`` raises `NotImplementedError` (record, then replay the action
+plane on a ``kpi=True`` env); more than 32 buildings and a thermal district are the library's refusals.
+
 Open: device-action heads, streaming KPIs in the chunked battery + PV launch, MARL in chunked launches (the libraries' refusal); for the deep
 policy a KPI twin, a chunked twin, MARL, hidden layers wider than 32 or deeper than two; for the deep thermal policy a KPI twin, more than 16
-buildings, device-action heads, two envs per lane, hidden layers wider than 32 or deeper than two.
+buildings, device-action heads, two envs per lane, hidden layers wider than 32 or deeper than two; for the central policy a KPI twin, two hidden
+layers, more than 32 buildings, thermal districts.
 """
 from __future__ import annotations
 
@@ -144,6 +162,9 @@ CLPD_MAX_HIDDEN, CLPD_MATRIX_CORES = DEEP_CONSTANTS['CLPD_MAX_HIDDEN'], DEEP_CON
 # the thermal kernel's
 FULL_DEEP_CONSTANTS = _header_constants(_lib.POLICY_FULL_DEEP.header, 'CLPFD_')
 CLPFD_MAX_HIDDEN, CLPFD_MATRIX_CORES = FULL_DEEP_CONSTANTS['CLPFD_MAX_HIDDEN'], FULL_DEEP_CONSTANTS['CLPFD_MATRIX_CORES']
+# a central agent (csrc/cl_policy_central.h, libcitylearn_amd_policy_central.so): the record and the noise stream are the lean kernel's
+CENTRAL_CONSTANTS = _header_constants(_lib.POLICY_CENTRAL.header, 'CLPCA_')
+CLPCA_MAX_HIDDEN, CLPCA_MAX_BLDG = CENTRAL_CONSTANTS['CLPCA_MAX_HIDDEN'], CENTRAL_CONSTANTS['CLPCA_MAX_BLDG']
 HEAD_NAMES = ('electrical_storage', 'cooling_storage', 'heating_storage', 'dhw_storage')                  # heads in CLPF_A_* order
 
 
@@ -278,6 +299,30 @@ class DeepStoragePolicyTables(_Tables):
     l2_fragments = DeepPolicyTables.l2_fragments
 
 
+class CentralPolicyTables(_Tables):
+    """`CentralMLPPolicy.pack`'s result.  ``pre [n_sets, n_rows, H]`` has NO building axis (one hidden layer for the district); ``dep
+    [n_sets, H / 4, n_bldg, 2, 4]`` holds, per group of four hidden units and building, the four soc weights then the four net weights
+    (``ACT_SCALE * W1[j][c] * col_scale[c]``, 0 where the building has no such column) -- the order the kernel walks them in; ``out = [w2 | b2]``
+    ``[n_sets, n_bldg, H + 1]``.  The host side is `PolicyTables`': ``[n_bldg]`` each, `es_cols` = every building's storage action column (-1: an
+    undriven building, which feeds the hidden layer and has no head)."""
+
+    def __init__(self, pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, es_cols, low_bldg, high_bldg, sigma_bldg, version):
+        self.pre, self.dep, self.out, self.net_reset = pre, dep, out, net_reset
+        self.act_low, self.act_high, self.sigma, self.set_of_block = act_low, act_high, sigma, set_of_block
+        self.cols, self.low_bldg, self.high_bldg, self.sigma_bldg = es_cols, low_bldg, high_bldg, sigma_bldg
+        self.n_device_cols = 0                                           # (the struct's third word: clpca_mlp.flags)
+        self.version = version
+        self.n_sets, self.n_rows, self.n_hidden = (int(x) for x in pre.shape)
+        self.n_bldg = int(out.shape[1])
+
+    es_cols = property(lambda self: self.cols)
+
+    def dep_terms(self) -> torch.Tensor:
+        """``dep`` as ``[n_sets, n_bldg, 2, H]`` (building, term soc / net, hidden unit): `PolicyTables.dep`'s axes."""
+        S, G, B = self.n_sets, self.n_hidden // 4, self.n_bldg
+        return self.dep.reshape(S, G, B, 2, 4).permute(0, 2, 3, 1, 4).reshape(S, B, 2, G * 4)
+
+
 def _l2_fragments(w2s: np.ndarray, b2s: np.ndarray) -> np.ndarray:
     """The matrix-core layout of layer 2 (`DeepPolicyTables`) from the scaled weights ``[S, B, H2, H1]`` and biases ``[S, B, H2]`` (float64):
     float32 ``[S, B, 1024 + 32 + 4]``."""
@@ -322,6 +367,7 @@ class _Kind:
     ext_chunk_kpi: Optional['_lib._Extension'] = None  # ... and the one that also keeps the streaming KPIs (`rollout_policy(chunked=True, kpi=True)`)
     ext_chunk_pair: Optional['_lib._Extension'] = None  # the chunked library of a kind that runs TWO buildings per wave (no KPI twin yet)
     one_row_max: int = 16             # buildings one workgroup row holds: beyond it `VectorCityLearnEnv.rollout_policy` asks for the chunked launch
+    central: bool = False             # ONE MLP over the district's central-agent observation vector (`CentralMLPPolicy`), not one per building
 
     def __post_init__(self):
         self.tables.kind = self
@@ -351,6 +397,11 @@ _DEEP = _Kind(terms=_LEAN.terms, head_slots=_LEAN.head_slots, head_shape=(), ref
 _DEEP_THERMAL = _Kind(terms=_THERMAL.terms, head_slots=_THERMAL.head_slots, head_shape=_THERMAL.head_shape, refuse_device_actions=True, only=_THERMAL.only,
                       tables=DeepStoragePolicyTables, struct=_lib.PolicyFullDeepMLP, constants=FULL_DEEP_CONSTANTS, max_hidden=CLPFD_MAX_HIDDEN,
                       n_planes=CLPF_NT, ext=_lib.POLICY_FULL_DEEP, ext_kpi=None, no_kpi_error=NotImplementedError, one_row_max=16)
+# a central agent: the lean kind's inputs (of EVERY building), heads, record and one-row geometry; a library of its own and neither a KPI nor a
+# chunked twin
+_CENTRAL = _Kind(terms=_LEAN.terms, head_slots=_LEAN.head_slots, head_shape=(), refuse_device_actions=False, only=_LEAN.only, tables=CentralPolicyTables,
+                 struct=_lib.PolicyMLP, constants=CENTRAL_CONSTANTS, max_hidden=CLPCA_MAX_HIDDEN, n_planes=CLPOL_NT, ext=_lib.POLICY_CENTRAL, ext_kpi=None,
+                 no_kpi_error=NotImplementedError, one_row_max=CLPCA_MAX_BLDG, central=True)
 # (terms and heads above are written in the header's order)
 assert (CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET) == tuple(range(CLPF_ND)) and (CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS) == tuple(range(CLPF_NA))
 
@@ -863,3 +914,162 @@ class DeepStorageMLPPolicy:
         return DeepStoragePolicyTables(ft.pre, ft.dep, l2.contiguous(), out.to(torch.float32).contiguous(), ft.net_reset, ft.act_low, ft.act_high,
                                        ft.sigma, ft.set_of_block, ft.cols, ft.low_bldg, ft.high_bldg, ft.sigma_bldg, self.version,
                                        matrix_cores=matrix_cores)
+
+
+class CentralMLPPolicy:
+    """CityLearn's ``central_agent=True`` actor: ONE tanh MLP with one hidden layer over the district's observation vector returns every
+    building's electrical-storage action,
+
+        h = tanh(W1 obs + b1),   a_b = clamp(mid_b + half_b tanh(w2[b] . h + b2[b]) + sigma_b z, low_b, high_b)
+
+    `obs` = the central-agent observation vector as the env defines it (``ObservationLayout(..., central_agent=True).columns``: a shared
+    observation once, normalised or not, whatever the env was built with); the bounds, sigma, z and the noise stream are `MLPPolicy`'s.  The
+    env-dependent inputs are EVERY building's own ``electrical_storage_soc`` and ``net_electricity_consumption``; a building without a storage
+    action column feeds the hidden layer like any other and has no head.  Battery + PV districts of up to 32 buildings: one launch of
+    `cl_rollout_policy_central_kernel` (csrc/cl_policy_central.h, ``libcitylearn_amd_policy_central.so``).
+
+    ``w1 [n_sets, H, n_cols]``, ``b1 [n_sets, H]``, ``w2 [n_sets, n_bldg, H]``, ``b2 [n_sets, n_bldg]`` (anything array-like; kept in float64); a
+    leading dimension of 1 broadcasts.  ``H``: 4, 8, .. 64.  ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
+
+    The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
+    kind = _CENTRAL
+    _NAMES = ('w1', 'b1', 'w2', 'b2')
+
+    def __init__(self, w1, b1, w2, b2, sigma=None):
+        self.w1, self.b1, self.w2, self.b2 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2))
+        if [getattr(self, n).ndim for n in self._NAMES] != [3, 2, 3, 2]:
+            raise ValueError('w1 [n_sets, H, n_cols], b1 [n_sets, H], w2 [n_sets, n_bldg, H], b2 [n_sets, n_bldg]')
+        self.n_hidden, self.n_obs, self.n_bldg = int(self.w1.shape[1]), int(self.w1.shape[2]), int(self.w2.shape[1])
+        if self.n_hidden % 4 or not 4 <= self.n_hidden <= CLPCA_MAX_HIDDEN:
+            raise ValueError(f'H={self.n_hidden}: the central policy kernel takes 4, 8, .. {CLPCA_MAX_HIDDEN} hidden units')
+        if self.b1.shape[1] != self.n_hidden or self.w2.shape[2] != self.n_hidden or self.b2.shape[1] != self.n_bldg:
+            raise ValueError('b1 / w2 disagree with w1 about H, or b2 with w2 about n_bldg')
+        self.n_sets = max(getattr(self, n).shape[0] for n in self._NAMES)
+        self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
+        self.version = 0
+
+    invalidate = _MLPBase.invalidate
+    update = _MLPBase.update
+
+    def _full(self, n_bldg: Optional[int] = None):
+        S, H, B = self.n_sets, self.n_hidden, self.n_bldg
+        if n_bldg is not None and n_bldg != B:
+            raise ValueError(f'w2 has heads for {B} buildings, the district has {n_bldg}')
+        try:
+            return tuple(np.broadcast_to(getattr(self, n), sh) for n, sh in zip(self._NAMES, ((S, H, self.n_obs), (S, H), (S, B, H), (S, B))))
+        except ValueError as e:
+            raise ValueError(f'the weights do not broadcast to {S} sets: {e}') from None
+
+    # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
+    def actions_host(self, obs, noise=None, tables: Optional[CentralPolicyTables] = None, low=None, high=None, sigma_bldg=None,
+                     set_index: int = 0) -> np.ndarray:
+        """float64 numpy evaluation of the plain MLP: ``obs [..., n_cols]`` (the central-agent vector) -> actions ``[..., n_bldg]``; the other
+        arguments are `MLPPolicy.actions_host`'s."""
+        pick = lambda arg, attr, default: np.asarray(arg if arg is not None else getattr(tables, attr) if tables is not None else default, dtype=np.float64)
+        x = np.asarray(obs, dtype=np.float64)
+        w1, b1, w2, b2 = (v[set_index] for v in self._full())
+        h = np.tanh(np.einsum('jc,...c->...j', w1, x) + b1)
+        lo, hi = pick(low, 'low_bldg', -1.0), pick(high, 'high_bldg', 1.0)
+        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('bj,...j->...b', w2, h) + b2)
+        if noise is not None:
+            if sigma_bldg is None and tables is None and self.sigma is not None and self.sigma.ndim:
+                raise ValueError('a per-column sigma needs `tables` (or `sigma_bldg`): which column drives which building')
+            a = a + pick(sigma_bldg, 'sigma_bldg', 0.0 if self.sigma is None or self.sigma.ndim else float(self.sigma)) * np.asarray(noise, dtype=np.float64)
+        return np.clip(a, lo, hi)
+
+    def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
+        """The same MLP (no noise) written in torch over the env's observation TENSOR of a ``central_agent=True`` env: a
+        `VectorCityLearnEnv.capture_rollout` policy ``f(obs [n_envs, n_cols], i=None) -> actions [n_act_cols, n_envs]``."""
+        self._check_layout(layout)
+        w1, b1, w2, b2 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(len(layout.building_names)))
+        hc = _head_columns(tab, self.kind)
+        low, high = layout.spec.action_limits()
+        sel = np.nonzero(hc >= 0)[0]                                             # the buildings that have a storage column
+        rows, bsel = torch.as_tensor(hc[sel], device=device), torch.as_tensor(sel, device=device)
+        lo = torch.as_tensor(np.asarray(low)[hc[sel]], dtype=dtype, device=device)
+        hi = torch.as_tensor(np.asarray(high)[hc[sel]], dtype=dtype, device=device)
+        n_act = len(low)
+
+        def f(obs, i=None):
+            h = torch.tanh(obs.to(dtype) @ w1.t() + b1)                          # [E, H]
+            o = torch.tanh(h @ w2.t() + b2)[:, bsel]                             # [E, driven buildings]
+            a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
+            out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
+            out[rows] = a.t().to(torch.float32)
+            return out
+        return f
+
+    def _check_layout(self, layout: ObservationLayout) -> None:
+        if not layout.central_agent:
+            raise ValueError('a CentralMLPPolicy is defined over the central-agent observation vector: the layout was built with central_agent=False '
+                             '(per-building vectors side by side, shared observations repeated)')
+        if layout.n_cols != self.n_obs:
+            raise ValueError(f'w1 takes {self.n_obs} observations, the central-agent vector has {layout.n_cols}')
+
+    # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
+    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None) -> CentralPolicyTables:
+        """Split the first layer as `MLPPolicy.pack` splits it, over the central-agent vector of `layout` (built with ``central_agent=True``):
+        the env-independent columns of every table row go into ``pre [n_sets, n_rows, H]`` (one matmul in float64 on `device`, rounded once) --
+        no building axis --, ``W1[j][c] * col_scale[c]`` of the env-dependent columns (every building's own ``electrical_storage_soc`` and
+        ``net_electricity_consumption``) into ``dep`` in the kernel's order (`CentralPolicyTables`), their table offsets into ``pre``;
+        ``ACT_SCALE`` is folded into both.  A column fed by any other device plane raises `MLPPolicy.pack`'s ``ValueError``."""
+        kind = self.kind
+        self._check_layout(layout)
+        obs = layout.episode(tab, reset_table=True)
+        n_bldg, T, N = len(layout.building_names), int(obs.table.shape[0]), layout.n_cols
+        w1, b1, w2, b2 = self._full(n_bldg)
+        params_i = np.ascontiguousarray(tab.params).view(np.int32)
+        term_of = {src: k for k, (src, _) in enumerate(kind.terms)}
+        table = obs.table
+        x = np.zeros((T, N))
+        scale = np.zeros((n_bldg, len(kind.terms), N))                   # [b][term][column of the central vector]
+        net_reset = np.zeros((T, n_bldg))
+        for c, (i, cname) in enumerate(layout.columns):
+            name = f'{cname!r} of building {i} (column {c})'
+            src = int(obs.col_src[c])
+            if src < 0:
+                if T > 1 and not np.array_equal(obs.reset_table[1:, c], table[1:, c]):
+                    raise ValueError(f'observation {name} is reset to a value its table row does not hold (observation_mode="reference"?): '
+                                     'the policy kernel reads the tables of observation_mode="current"')
+                x[:, c] = table[:, c]
+                continue
+            kind_, plane, b = src >> 28, (src >> 20) & 0xFF, src & 0xFFFFF
+            which = term_of.get((kind_, plane))
+            if which is None or b != i:
+                raise ValueError(f'observation {name} is fed by device plane (kind {kind_}, plane {plane}, building {b}): {kind.only}'
+                                 + (' -- the indoor temperature comes from the LSTM stage' if kind_ == SRC_TEMP else ''))
+            offset = table[1:, c] if T > 1 else np.zeros(1)
+            if np.ptp(offset) != 0.0:
+                raise ValueError(f'observation {name}: a table offset that changes with the row')
+            x[:, c] = offset[0]
+            scale[i, which, c] = float(obs.col_scale[c])
+            if kind.terms[which][0] == (SRC_OUT, abi.CLO_NET) and scale[i, which, c] != 0.0:
+                net_reset[:, i] = (obs.reset_table[:, c] - offset[0]) / scale[i, which, c]
+        dev = torch.device(device)
+        f64 = lambda v: torch.from_numpy(np.array(v, dtype=np.float64)).to(dev)
+        S, H = self.n_sets, self.n_hidden
+        pre = (torch.einsum('sjc,tc->stj', f64(w1), f64(x)) + f64(b1)[:, None]) * ACT_SCALE
+        dep = torch.einsum('sjc,bkc->sjbk', f64(w1), f64(scale)) * ACT_SCALE                          # [S, H, B, 2]
+        dep = dep.reshape(S, H // 4, 4, n_bldg, len(kind.terms)).permute(0, 1, 3, 4, 2)              # [S, H / 4, B, 2, 4]
+        out = torch.cat([f64(w2), f64(b2)[..., None]], dim=-1)
+        hc = _head_columns(tab, kind)
+        n_act = int(params_i[:, abi.CLP_ACT_COOL_STO:abi.CLP_ACT_COH_DEV + 1].max()) + 1
+        low, high = layout.spec.action_limits()
+        if len(low) != n_act:
+            raise ValueError(f'{len(low)} action limits for {n_act} action columns')
+        at = lambda v, fill: np.where(hc >= 0, np.asarray(v, dtype=np.float64)[np.maximum(hc, 0)], fill)
+        sigma = None
+        if self.sigma is not None:
+            sigma = np.full(n_act, float(self.sigma)) if self.sigma.ndim == 0 else self.sigma
+            if sigma.shape != (n_act,) or np.any(sigma < 0):
+                raise ValueError(f'sigma: a non-negative scalar or [{n_act}] (one per action column)')
+        f32 = lambda v: None if v is None else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to(dev)
+        sob = None
+        if set_of_block is not None:
+            sob = np.asarray(set_of_block, dtype=np.int64).reshape(-1)
+            if sob.min() < 0 or sob.max() >= self.n_sets:
+                raise ValueError(f'set_of_block outside [0, {self.n_sets})')
+            sob = torch.from_numpy(sob.astype(np.int32)).to(dev)
+        return CentralPolicyTables(pre.to(torch.float32).contiguous(), dep.to(torch.float32).contiguous(), out.to(torch.float32).contiguous(),
+                                   f32(net_reset), f32(low), f32(high), f32(sigma), sob, hc, at(low, -1.0), at(high, 1.0),
+                                   np.zeros(hc.shape) if sigma is None else at(sigma, 0.0), self.version)

@@ -453,8 +453,20 @@ class VectorCityLearnEnv:
         A `policy.DeepStorageMLPPolicy` (two hidden layers, up to four storage heads) drives a THERMAL district of up to 16 buildings through
         `cl_rollout_full_policy_deep_kernel`, same record (`policy.CLPF_NT` planes) and noise stream as a `StorageMLPPolicy`, MARL included.  More
         than 16 buildings and a battery + PV district are the library's refusals; ``kpi=True`` raises `NotImplementedError` (record, then replay
-        the heads' action planes on a ``kpi=True`` env)."""
+        the heads' action planes on a ``kpi=True`` env).
+
+        A `policy.CentralMLPPolicy` (ONE MLP over the central-agent observation vector) drives a battery + PV district of up to 32 buildings of
+        an env built with ``central_agent=True`` through `cl_rollout_policy_central_kernel`, same record and noise stream as an `MLPPolicy`,
+        MARL included; on an env built with ``central_agent=False`` it is a `ValueError`.  More than 32 buildings and a thermal district are the
+        library's refusals; ``kpi=True`` raises `NotImplementedError` (record, then replay the action plane on a ``kpi=True`` env)."""
         chunked = (policy.kind.ext_chunk or policy.kind.ext_chunk_pair) is not None and self.engine.n_bldg > policy.kind.one_row_max
+        if policy.kind.central and not self.central_agent:
+            raise ValueError(f'a {type(policy).__name__} needs an env built with central_agent=True: this env hands out one observation vector per '
+                             'building, which is not the vector the policy\'s weights are defined over')
+        if kpi and policy.kind.ext_kpi is None and policy.kind.central:
+            raise NotImplementedError(f'rollout_policy(kpi=True) with a {type(policy).__name__}: a central-agent policy has no KPI kernel -- record the '
+                                      'rollout (record=True) and replay its action plane (policy.CLPOL_T_ACTION) through '
+                                      'rollout(actions=..., fused=True) on an env built with kpi=True')
         if kpi and policy.kind.ext_kpi is None:
             planes = ('its action plane (policy.CLPOL_T_ACTION)' if not policy.kind.head_shape else
                       "its action planes (policy.CLPF_T_ACTION + head, each head's plane into its action column: policy.head_columns)")

@@ -250,6 +250,12 @@ DEEP_THERMAL_EXTENSIONS = (POLICY_FULL_DEEP,)
 # of its own: the tuples above stay what they are; `__graft_entry__.build()` builds it behind them.
 POLICY_CENTRAL = _Extension('policy_central', 'clpca', 'central policy', ['-fno-slp-vectorize'], 'rollout_mlp_f32', PolicyMLP, headers=[POLICY.header])
 CENTRAL_EXTENSIONS = (POLICY_CENTRAL,)
+# ... and the central-agent one whose MLP has TWO hidden layers (cl_policy_central_deep.hip, without SLP vectorisation like cl_policy.hip;
+# `clpcd_mlp` extends `clpca_mlp` as `clpd_mlp` extends `clpol_mlp`, so `PolicyDeepMLP` serves it).  A tuple of its own again:
+# `__graft_entry__.build()` builds it behind CENTRAL_EXTENSIONS.
+POLICY_CENTRAL_DEEP = _Extension('policy_central_deep', 'clpcd', 'deep central policy', ['-fno-slp-vectorize'], 'rollout_mlp_f32', PolicyDeepMLP,
+                                 headers=[POLICY.header])
+CENTRAL_DEEP_EXTENSIONS = (POLICY_CENTRAL_DEEP,)
 
 # The names other code and the tests use: read-only views of the descriptions above (build / load / check read the description, so rebinding one
 # of these changes nothing -- change the description's attribute instead)
@@ -316,6 +322,14 @@ def policy_central_lds_bytes(nw: int, n_bldg: int, h: int) -> int:
     Hh [h][64], the staged ``dep`` [h / 4][n_bldg][8], the staged out rows [nw][2][64 + 8] -- 74 752 bytes at sixteen waves, 32 buildings and 64
     units (tests/test_policy_central_host.py holds it against the header's formula)."""
     return 4 * (nw * 4 * 64 + 2 * n_bldg * 64 + h * 64 + 2 * h * n_bldg + nw * 2 * (64 + 8))
+
+
+def policy_central_deep_lds_bytes(nw: int, n_bldg: int, h1: int, h2: int) -> int:
+    """Dynamic LDS of one `cl_rollout_policy_central_deep_kernel` workgroup of ``nw`` waves over ``n_bldg`` buildings at ``h1`` x ``h2`` hidden
+    units: include/citylearn_amd_policy_central_deep.h's formula (csrc/cl_policy_central_deep.h's `rollout_policy_central_deep_lds_floats`) --
+    `policy_central_lds_bytes`' regions at ``h1`` units, plus the second hidden layer Hh2 [h2][64] and the staged ``l2`` [h1 + 1][h2] -- 107 776
+    bytes at sixteen waves, 32 buildings and 64 x 64 units (tests/test_policy_central_deep_host.py holds it against the header's formula)."""
+    return 4 * (nw * 4 * 64 + 2 * n_bldg * 64 + h1 * 64 + h2 * 64 + 2 * h1 * n_bldg + (h1 + 1) * h2 + nw * 2 * (64 + 8))
 
 
 def policy_chunk_lds_bytes(nw: int, vec: int) -> int:

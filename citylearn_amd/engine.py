@@ -587,8 +587,15 @@ class StepEngine:
         ``[k_steps, CLPOL_NT, n_bldg, n_env]`` and noise stream of `cl_rollout_policy_kernel` at one env per lane, every lean reward kind, MARL
         included; ``tuning=dict(nw=...)`` changes no action, net or soc.  A thermal district, more than 32 buildings and a ``kpi=True`` engine
         are the library's refusals; ``chunked=True`` is the `ValueError` above and ``kpi=True`` a `NotImplementedError` of its own wording:
-        record, then replay the action plane on a ``kpi=True`` engine."""
-        kind = policy_tables.kind           # (`policy._Kind`: the libraries, the trajectory's plane count and what a build without KPIs raises)
+        record, then replay the action plane on a ``kpi=True`` engine.
+
+        ``policy_tables`` from `policy.DeepCentralMLPPolicy.pack` (a `DeepCentralPolicyTables`: the central agent's MLP with TWO hidden layers of
+        4 .. 64 units each) sends the same districts to `cl_rollout_policy_central_deep_kernel` (`clpcd_rollout_mlp_f32`,
+        ``libcitylearn_amd_policy_central_deep.so``): the central kernel's step with a third phase and workgroup barrier for layer 2, in exact
+        fp32; same record, noise stream, reward kinds (MARL included) and ``nw`` invariance.  Its refusals are the central tables': the
+        library's for a thermal district, more than 32 buildings and a ``kpi=True`` engine, the `ValueError` above for ``chunked=True`` and the
+        central `NotImplementedError` for ``kpi=True``."""
+        kind = policy_tables.kind          # (`policy._Kind`: the libraries, the trajectory's plane count and what a build without KPIs raises)
         ext_chunk = kind.ext_chunk or kind.ext_chunk_pair
         if chunked and (ext_chunk is None or (kind.ext_chunk is None and not self.dims.flags & abi.CLD_LEAN)):
             raise ValueError(f'rollout_policy(chunked=True) needs StoragePolicyTables here: there is no building-chunked policy kernel for '

@@ -115,10 +115,21 @@ sums have a fixed order and ``tuning=dict(nw=...)`` changes no action.  An env b
 observation tensor is not the vector the weights are defined over); ``kpi=True`` raises `NotImplementedError` (record, then replay the action
 plane on a ``kpi=True`` env); more than 32 buildings and a thermal district are the library's refusals.
 
+A central actor with TWO hidden layers -- a SAC / PPO actor trained with ``central_agent=True`` -- is a `DeepCentralMLPPolicy`: ``h1 = tanh(W1 obs
++ b1)``, ``h2 = tanh(W2 h1 + b2)``, ``a_b = clamp(mid_b + half_b tanh(w3[b] . h2 + b3[b]) + sigma_b z, low_b, high_b)`` with H1, H2 in 4, 8, .. 64
+independently, same districts, reward kinds, record and noise stream as the `CentralMLPPolicy`: one launch of
+`cl_rollout_policy_central_deep_kernel` (csrc/cl_policy_central_deep.h, ``libcitylearn_amd_policy_central_deep.so``,
+include/citylearn_amd_policy_central_deep.h), whose step has a third phase and barrier for layer 2 -- one H1 x H2 product per ENV, in exact fp32:
+
+    dcentral = DeepCentralMLPPolicy(w1, b1, w2, b2, w3, b3, sigma=0.1)    # w2 [n_sets, H2, H1], b2 [n_sets, H2], w3 [n_sets, n_bldg, H2], b3 [n_sets, n_bldg]
+    ret, traj = cenv.rollout_policy(dcentral, 24, seed=3, record=True)
+
+Its refusals are the central policy's.
+
 Open: device-action heads, streaming KPIs in the chunked battery + PV launch, MARL in chunked launches (the libraries' refusal); for the deep
 policy a KPI twin, a chunked twin, MARL, hidden layers wider than 32 or deeper than two; for the deep thermal policy a KPI twin, more than 16
-buildings, device-action heads, two envs per lane, hidden layers wider than 32 or deeper than two; for the central policy a KPI twin, two hidden
-layers, more than 32 buildings, thermal districts.
+buildings, device-action heads, two envs per lane, hidden layers wider than 32 or deeper than two; for both central policies a KPI twin, more
+than 32 buildings, thermal districts; for the deep central policy a matrix-core family of layer 2, hidden layers deeper than two.
 """
 from __future__ import annotations
 
@@ -165,6 +176,9 @@ CLPFD_MAX_HIDDEN, CLPFD_MATRIX_CORES = FULL_DEEP_CONSTANTS['CLPFD_MAX_HIDDEN'], 
 # a central agent (csrc/cl_policy_central.h, libcitylearn_amd_policy_central.so): the record and the noise stream are the lean kernel's
 CENTRAL_CONSTANTS = _header_constants(_lib.POLICY_CENTRAL.header, 'CLPCA_')
 CLPCA_MAX_HIDDEN, CLPCA_MAX_BLDG = CENTRAL_CONSTANTS['CLPCA_MAX_HIDDEN'], CENTRAL_CONSTANTS['CLPCA_MAX_BLDG']
+# ... with two hidden layers (csrc/cl_policy_central_deep.h, libcitylearn_amd_policy_central_deep.so)
+CENTRAL_DEEP_CONSTANTS = _header_constants(_lib.POLICY_CENTRAL_DEEP.header, 'CLPCD_')
+CLPCD_MAX_HIDDEN, CLPCD_MAX_BLDG = CENTRAL_DEEP_CONSTANTS['CLPCD_MAX_HIDDEN'], CENTRAL_DEEP_CONSTANTS['CLPCD_MAX_BLDG']
 HEAD_NAMES = ('electrical_storage', 'cooling_storage', 'heating_storage', 'dhw_storage')                  # heads in CLPF_A_* order
 
 
@@ -323,6 +337,22 @@ class CentralPolicyTables(_Tables):
         return self.dep.reshape(S, G, B, 2, 4).permute(0, 2, 3, 1, 4).reshape(S, B, 2, G * 4)
 
 
+class DeepCentralPolicyTables(CentralPolicyTables):
+    """`DeepCentralMLPPolicy.pack`'s result: `CentralPolicyTables`' members for the first layer (``pre [n_sets, n_rows, H1]``, ``dep
+    [n_sets, H1 / 4, n_bldg, 2, 4]``) and the host side, then the second layer ``l2 [n_sets, H1 + 1, H2]`` -- ``ACT_SCALE * W2`` TRANSPOSED (one row
+    per first-layer unit), ``ACT_SCALE * b2`` as the last row: `DeepPolicyTables`' exact-fp32 layout without the building axis -- and
+    ``out = [w3 | b3]`` ``[n_sets, n_bldg, H2 + 1]``.  ``n_hidden`` is H1, ``n_hidden2`` H2."""
+
+    def __init__(self, pre, dep, l2, out, net_reset, act_low, act_high, sigma, set_of_block, es_cols, low_bldg, high_bldg, sigma_bldg, version):
+        super().__init__(pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, es_cols, low_bldg, high_bldg, sigma_bldg, version)
+        self.l2, self.n_hidden2 = l2, int(out.shape[-1]) - 1
+
+    def struct(self, seed: int):
+        p = lambda t: None if t is None else t.data_ptr()
+        return self.kind.struct(self.n_hidden, self.n_sets, 0, 0, p(self.pre), p(self.dep), p(self.out), p(self.set_of_block), p(self.net_reset),
+                                p(self.act_low), p(self.act_high), p(self.sigma), int(seed) & (2 ** 64 - 1), self.n_hidden2, 0, p(self.l2))
+
+
 def _l2_fragments(w2s: np.ndarray, b2s: np.ndarray) -> np.ndarray:
     """The matrix-core layout of layer 2 (`DeepPolicyTables`) from the scaled weights ``[S, B, H2, H1]`` and biases ``[S, B, H2]`` (float64):
     float32 ``[S, B, 1024 + 32 + 4]``."""
@@ -402,6 +432,11 @@ _DEEP_THERMAL = _Kind(terms=_THERMAL.terms, head_slots=_THERMAL.head_slots, head
 _CENTRAL = _Kind(terms=_LEAN.terms, head_slots=_LEAN.head_slots, head_shape=(), refuse_device_actions=False, only=_LEAN.only, tables=CentralPolicyTables,
                  struct=_lib.PolicyMLP, constants=CENTRAL_CONSTANTS, max_hidden=CLPCA_MAX_HIDDEN, n_planes=CLPOL_NT, ext=_lib.POLICY_CENTRAL, ext_kpi=None,
                  no_kpi_error=NotImplementedError, one_row_max=CLPCA_MAX_BLDG, central=True)
+# a central agent with two hidden layers: the central kind's inputs, heads, record and geometry; a library of its own once more
+_CENTRAL_DEEP = _Kind(terms=_LEAN.terms, head_slots=_LEAN.head_slots, head_shape=(), refuse_device_actions=False, only=_LEAN.only,
+                      tables=DeepCentralPolicyTables, struct=_lib.PolicyDeepMLP, constants=CENTRAL_DEEP_CONSTANTS, max_hidden=CLPCD_MAX_HIDDEN,
+                      n_planes=CLPOL_NT, ext=_lib.POLICY_CENTRAL_DEEP, ext_kpi=None, no_kpi_error=NotImplementedError, one_row_max=CLPCD_MAX_BLDG,
+                      central=True)
 # (terms and heads above are written in the header's order)
 assert (CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET) == tuple(range(CLPF_ND)) and (CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS) == tuple(range(CLPF_NA))
 
@@ -1001,7 +1036,7 @@ class CentralMLPPolicy:
 
     def _check_layout(self, layout: ObservationLayout) -> None:
         if not layout.central_agent:
-            raise ValueError('a CentralMLPPolicy is defined over the central-agent observation vector: the layout was built with central_agent=False '
+            raise ValueError(f'a {type(self).__name__} is defined over the central-agent observation vector: the layout was built with central_agent=False '
                              '(per-building vectors side by side, shared observations repeated)')
         if layout.n_cols != self.n_obs:
             raise ValueError(f'w1 takes {self.n_obs} observations, the central-agent vector has {layout.n_cols}')
@@ -1013,11 +1048,19 @@ class CentralMLPPolicy:
         no building axis --, ``W1[j][c] * col_scale[c]`` of the env-dependent columns (every building's own ``electrical_storage_soc`` and
         ``net_electricity_consumption``) into ``dep`` in the kernel's order (`CentralPolicyTables`), their table offsets into ``pre``;
         ``ACT_SCALE`` is folded into both.  A column fed by any other device plane raises `MLPPolicy.pack`'s ``ValueError``."""
-        kind = self.kind
         self._check_layout(layout)
+        w1, b1, w2, b2 = self._full(len(layout.building_names))
+        pre, dep, rest = self._pack_front(layout, tab, w1, b1, device, set_of_block)
+        out = torch.cat([torch.from_numpy(np.array(v, dtype=np.float64)).to(pre.device) for v in (w2, b2[..., None])], dim=-1)
+        return CentralPolicyTables(pre, dep, out.to(torch.float32).contiguous(), *rest, self.version)
+
+    def _pack_front(self, layout: ObservationLayout, tab, w1, b1, device, set_of_block):
+        """The first layer ``w1 [n_sets, H, n_cols]``, ``b1 [n_sets, H]`` (broadcast) split over the central-agent vector as `pack` describes it:
+        ``(pre, dep, rest)`` with ``rest`` the tables' members behind ``out`` -- ``net_reset``, the bounds, sigma, ``set_of_block`` on `device`, the
+        host side.  What `CentralMLPPolicy.pack` and `DeepCentralMLPPolicy.pack` share."""
+        kind = self.kind
         obs = layout.episode(tab, reset_table=True)
         n_bldg, T, N = len(layout.building_names), int(obs.table.shape[0]), layout.n_cols
-        w1, b1, w2, b2 = self._full(n_bldg)
         params_i = np.ascontiguousarray(tab.params).view(np.int32)
         term_of = {src: k for k, (src, _) in enumerate(kind.terms)}
         table = obs.table
@@ -1051,7 +1094,6 @@ class CentralMLPPolicy:
         pre = (torch.einsum('sjc,tc->stj', f64(w1), f64(x)) + f64(b1)[:, None]) * ACT_SCALE
         dep = torch.einsum('sjc,bkc->sjbk', f64(w1), f64(scale)) * ACT_SCALE                          # [S, H, B, 2]
         dep = dep.reshape(S, H // 4, 4, n_bldg, len(kind.terms)).permute(0, 1, 3, 4, 2)              # [S, H / 4, B, 2, 4]
-        out = torch.cat([f64(w2), f64(b2)[..., None]], dim=-1)
         hc = _head_columns(tab, kind)
         n_act = int(params_i[:, abi.CLP_ACT_COOL_STO:abi.CLP_ACT_COH_DEV + 1].max()) + 1
         low, high = layout.spec.action_limits()
@@ -1070,6 +1112,109 @@ class CentralMLPPolicy:
             if sob.min() < 0 or sob.max() >= self.n_sets:
                 raise ValueError(f'set_of_block outside [0, {self.n_sets})')
             sob = torch.from_numpy(sob.astype(np.int32)).to(dev)
-        return CentralPolicyTables(pre.to(torch.float32).contiguous(), dep.to(torch.float32).contiguous(), out.to(torch.float32).contiguous(),
-                                   f32(net_reset), f32(low), f32(high), f32(sigma), sob, hc, at(low, -1.0), at(high, 1.0),
-                                   np.zeros(hc.shape) if sigma is None else at(sigma, 0.0), self.version)
+        return (pre.to(torch.float32).contiguous(), dep.to(torch.float32).contiguous(),
+                (f32(net_reset), f32(low), f32(high), f32(sigma), sob, hc, at(low, -1.0), at(high, 1.0),
+                 np.zeros(hc.shape) if sigma is None else at(sigma, 0.0)))
+
+
+class DeepCentralMLPPolicy:
+    """`CentralMLPPolicy` with TWO hidden layers -- a SAC / PPO actor trained with ``central_agent=True``:
+
+        h1 = tanh(W1 obs + b1),   h2 = tanh(W2 h1 + b2),   a_b = clamp(mid_b + half_b tanh(w3[b] . h2 + b3[b]) + sigma_b z, low_b, high_b)
+
+    `obs`, the bounds, sigma, z, the noise stream and the env-dependent inputs (EVERY building's own ``electrical_storage_soc`` and
+    ``net_electricity_consumption``) are `CentralMLPPolicy`'s.  Battery + PV districts of up to 32 buildings: one launch of
+    `cl_rollout_policy_central_deep_kernel` (csrc/cl_policy_central_deep.h, ``libcitylearn_amd_policy_central_deep.so``), layer 2 in exact fp32.
+
+    ``w1 [n_sets, H1, n_cols]``, ``b1 [n_sets, H1]``, ``w2 [n_sets, H2, H1]``, ``b2 [n_sets, H2]``, ``w3 [n_sets, n_bldg, H2]``,
+    ``b3 [n_sets, n_bldg]`` (anything array-like; kept in float64); a leading dimension of 1 broadcasts.  ``H1``, ``H2``: 4, 8, .. 64, independent of
+    each other.  ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
+
+    The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
+    kind = _CENTRAL_DEEP
+    _NAMES = ('w1', 'b1', 'w2', 'b2', 'w3', 'b3')
+
+    def __init__(self, w1, b1, w2, b2, w3, b3, sigma=None):
+        self.w1, self.b1, self.w2, self.b2, self.w3, self.b3 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2, w3, b3))
+        if [getattr(self, n).ndim for n in self._NAMES] != [3, 2, 3, 2, 3, 2]:
+            raise ValueError('w1 [n_sets, H1, n_cols], b1 [n_sets, H1], w2 [n_sets, H2, H1], b2 [n_sets, H2], w3 [n_sets, n_bldg, H2], b3 [n_sets, n_bldg]')
+        self.n_hidden, self.n_obs, self.n_hidden2, self.n_bldg = (int(self.w1.shape[1]), int(self.w1.shape[2]), int(self.w2.shape[1]),
+                                                                  int(self.w3.shape[1]))
+        for name, h in (('H1', self.n_hidden), ('H2', self.n_hidden2)):
+            if h % 4 or not 4 <= h <= CLPCD_MAX_HIDDEN:
+                raise ValueError(f'{name}={h}: the deep central policy kernel takes 4, 8, .. {CLPCD_MAX_HIDDEN} units per hidden layer')
+        if self.b1.shape[1] != self.n_hidden or self.w2.shape[2] != self.n_hidden:
+            raise ValueError('b1 / w2 disagree with w1 about H1')
+        if self.b2.shape[1] != self.n_hidden2 or self.w3.shape[2] != self.n_hidden2 or self.b3.shape[1] != self.n_bldg:
+            raise ValueError('b2 / w3 disagree with w2 about H2, or b3 with w3 about n_bldg')
+        self.n_sets = max(getattr(self, n).shape[0] for n in self._NAMES)
+        self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
+        self.version = 0
+
+    invalidate = DeepMLPPolicy.invalidate
+    update = DeepMLPPolicy.update
+    _check_layout = CentralMLPPolicy._check_layout
+    _pack_front = CentralMLPPolicy._pack_front
+
+    def _full(self, n_bldg: Optional[int] = None):
+        S, H1, H2, B = self.n_sets, self.n_hidden, self.n_hidden2, self.n_bldg
+        if n_bldg is not None and n_bldg != B:
+            raise ValueError(f'w3 has heads for {B} buildings, the district has {n_bldg}')
+        shapes = ((S, H1, self.n_obs), (S, H1), (S, H2, H1), (S, H2), (S, B, H2), (S, B))
+        try:
+            return tuple(np.broadcast_to(getattr(self, n), sh) for n, sh in zip(self._NAMES, shapes))
+        except ValueError as e:
+            raise ValueError(f'the weights do not broadcast to {S} sets: {e}') from None
+
+    # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
+    def actions_host(self, obs, noise=None, tables: Optional[DeepCentralPolicyTables] = None, low=None, high=None, sigma_bldg=None,
+                     set_index: int = 0) -> np.ndarray:
+        """float64 numpy evaluation of the plain MLP: ``obs [..., n_cols]`` (the central-agent vector) -> actions ``[..., n_bldg]``; the other
+        arguments are `MLPPolicy.actions_host`'s."""
+        pick = lambda arg, attr, default: np.asarray(arg if arg is not None else getattr(tables, attr) if tables is not None else default, dtype=np.float64)
+        x = np.asarray(obs, dtype=np.float64)
+        w1, b1, w2, b2, w3, b3 = (v[set_index] for v in self._full())
+        h1 = np.tanh(np.einsum('jc,...c->...j', w1, x) + b1)
+        h2 = np.tanh(np.einsum('ij,...j->...i', w2, h1) + b2)
+        lo, hi = pick(low, 'low_bldg', -1.0), pick(high, 'high_bldg', 1.0)
+        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('bi,...i->...b', w3, h2) + b3)
+        if noise is not None:
+            if sigma_bldg is None and tables is None and self.sigma is not None and self.sigma.ndim:
+                raise ValueError('a per-column sigma needs `tables` (or `sigma_bldg`): which column drives which building')
+            a = a + pick(sigma_bldg, 'sigma_bldg', 0.0 if self.sigma is None or self.sigma.ndim else float(self.sigma)) * np.asarray(noise, dtype=np.float64)
+        return np.clip(a, lo, hi)
+
+    def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
+        """The same MLP (no noise) written in torch over the env's observation TENSOR of a ``central_agent=True`` env: a
+        `VectorCityLearnEnv.capture_rollout` policy ``f(obs [n_envs, n_cols], i=None) -> actions [n_act_cols, n_envs]``."""
+        self._check_layout(layout)
+        w1, b1, w2, b2, w3, b3 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(len(layout.building_names)))
+        hc = _head_columns(tab, self.kind)
+        low, high = layout.spec.action_limits()
+        sel = np.nonzero(hc >= 0)[0]                                             # the buildings that have a storage column
+        rows, bsel = torch.as_tensor(hc[sel], device=device), torch.as_tensor(sel, device=device)
+        lo = torch.as_tensor(np.asarray(low)[hc[sel]], dtype=dtype, device=device)
+        hi = torch.as_tensor(np.asarray(high)[hc[sel]], dtype=dtype, device=device)
+        n_act = len(low)
+
+        def f(obs, i=None):
+            h1 = torch.tanh(obs.to(dtype) @ w1.t() + b1)                         # [E, H1]
+            h2 = torch.tanh(h1 @ w2.t() + b2)                                    # [E, H2]
+            o = torch.tanh(h2 @ w3.t() + b3)[:, bsel]                            # [E, driven buildings]
+            a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
+            out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
+            out[rows] = a.t().to(torch.float32)
+            return out
+        return f
+
+    # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
+    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None) -> DeepCentralPolicyTables:
+        """The first layer split exactly as `CentralMLPPolicy.pack` splits it (the same function, the same refusals), then ``l2`` and ``out`` as
+        `DeepCentralPolicyTables` describes them, in float64 rounded once."""
+        self._check_layout(layout)
+        w1, b1, w2, b2, w3, b3 = self._full(len(layout.building_names))
+        pre, dep, rest = self._pack_front(layout, tab, w1, b1, device, set_of_block)
+        f64 = lambda v: torch.from_numpy(np.array(v, dtype=np.float64)).to(pre.device)
+        l2 = (torch.cat([f64(w2).transpose(1, 2), f64(b2)[:, None, :]], dim=1) * ACT_SCALE).to(torch.float32)
+        out = torch.cat([f64(w3), f64(b3)[..., None]], dim=-1)
+        return DeepCentralPolicyTables(pre, dep, l2.contiguous(), out.to(torch.float32).contiguous(), *rest, self.version)

@@ -458,8 +458,12 @@ class VectorCityLearnEnv:
         A `policy.CentralMLPPolicy` (ONE MLP over the central-agent observation vector) drives a battery + PV district of up to 32 buildings of
         an env built with ``central_agent=True`` through `cl_rollout_policy_central_kernel`, same record and noise stream as an `MLPPolicy`,
         MARL included; on an env built with ``central_agent=False`` it is a `ValueError`.  More than 32 buildings and a thermal district are the
-        library's refusals; ``kpi=True`` raises `NotImplementedError` (record, then replay the action plane on a ``kpi=True`` env)."""
-        chunked = (policy.kind.ext_chunk or policy.kind.ext_chunk_pair) is not None and self.engine.n_bldg > policy.kind.one_row_max
+        library's refusals; ``kpi=True`` raises `NotImplementedError` (record, then replay the action plane on a ``kpi=True`` env).
+
+        A `policy.DeepCentralMLPPolicy` (the central agent's MLP with TWO hidden layers of 4 .. 64 units each) drives the same districts of an
+        env built with ``central_agent=True`` through `cl_rollout_policy_central_deep_kernel`; record, noise stream, MARL and every refusal are
+        the `CentralMLPPolicy`'s."""
+        chunked =(policy.kind.ext_chunk or policy.kind.ext_chunk_pair) is not None and self.engine.n_bldg > policy.kind.one_row_max
         if policy.kind.central and not self.central_agent:
             raise ValueError(f'a {type(policy).__name__} needs an env built with central_agent=True: this env hands out one observation vector per '
                              'building, which is not the vector the policy\'s weights are defined over')

@@ -96,6 +96,10 @@ struct StepArgs {
     int fused_finish;   // building-chunked launches: the last chunk of an env tile folds the chunk partial sums itself (district_reduce)
 };
 
+// StepArgs::flags, library-internal (not a CLD_* bit a caller can set: step_impl clears it, then sets it from StepPlan::strips -- with the LDS row
+// the strips need): the uniform body of cl_step_lean_chain_kernel<4, ..> shares the building beyond the waves out as strips (lean_step_body, STRIPS)
+constexpr uint32_t CLA_LEAN_STRIPS = (uint32_t)1 << 31;
+
 constexpr int CL_OBS_FUSED_PER_BLDG = 4;      // observation columns per building the step launch writes itself
 
 template <int VEC> struct Vec;
@@ -264,10 +268,15 @@ CL_DEV void fold_finish(const StepArgs& a, const float* lds_fold, int w, int lan
 // against 109.9 us.  An XCD that owns four chunks touches 128 building rows of every plane instead of all 1024: its requests crowd a
 // fraction of the rows the memory system interleaves over, and 2 MB of parameter re-reads (L2 misses that the Infinity Cache serves) were
 // never on the critical path.
-template <int VEC, bool FLEX = false, bool FOLD = false, bool KPIS = false, bool PRESTORED = false>
+// STRIPS (lean_step_body's uniform body): with `strip_row` set, LDS row a.nw -- behind the wave rows -- holds the four quantities of building a.nw, written by the
+// strip waves before the first barrier, and row 0 holds building 0 alone.  The sum starts from that row instead of from zero: (row_nw + row_0) + row_1 + ..,
+// where wave 0 with two tiles gives (0 + row_0') + row_1 + .. with row_0' = (0 + b_0) + b_nw.  Same bits: row_0 = 0 + b_0 and row_nw = b_nw, the addition
+// commutes, and 0 + row_0' = row_0' because row_0' is never -0 -- 0 + b_0 is not (+0 + -0 = +0 in round-to-nearest), and a sum with a term that is not -0 is not.
+template <int VEC, bool FLEX = false, bool FOLD = false, bool KPIS = false, bool PRESTORED = false, bool STRIPS = false>
 CL_DEV void district_reduce(const StepArgs& a, float* lds, int w, int lane, int env0, bool live, long long plane, int rkind,
                             const float (&q_net)[VEC], const float (&q_cost)[VEC], const float (&q_em)[VEC],
-                            const float (&q_rw)[VEC], int stride, [[maybe_unused]] const float* lds_fold = nullptr) {
+                            const float (&q_rw)[VEC], int stride, [[maybe_unused]] const float* lds_fold = nullptr,
+                            [[maybe_unused]] bool strip_row = false) {
     constexpr int TILE = 64 * VEC;
     const int bx = blockIdx.x, by = blockIdx.y;       // env tile, building chunk
     if constexpr (!PRESTORED) {
@@ -407,6 +416,9 @@ CL_DEV void district_reduce(const StepArgs& a, float* lds, int w, int lane, int 
     for (int i = threadIdx.x; i < NQ * TILE; i += blockDim.x) {
         const int q = i / TILE, e = i - q * TILE;
         float s = 0.0f;
+        if constexpr (STRIPS) {
+            if (strip_row) s = lds[(size_t)a.nw * NQ * TILE + i];
+        }
         for (int k = 0; k < a.nw; ++k) s += lds[(size_t)k * NQ * TILE + i];
         if (coupled && q == CLQ_REWARD) {                      // finished below
             if (FLEX && rkind == CLR_EV) lds[i] = s;           // CLR_EV accumulated sign(-net) * 0.01 * net^2: the district MARL sum / max(0, district net)
@@ -811,15 +823,36 @@ struct ObsFusedArgs {
 //  - actions whose column is a parameter word are requested for both buildings in front of the first one's arithmetic;
 //  - the no-battery path, which truly leaves its state rows unread, waits for them itself.
 // Left as it was: two waits INSIDE the first building's store burst of the generic body (behind its first and third store; cause not found).
+// STRIPS (the uniform body at four envs per lane, a district of ONE building more than waves -- 17 buildings, 16 waves: the headline; the host asks
+// for it with CLA_LEAN_STRIPS, cl_tuning.lean_variant & 32 keeps the old mapping).  Wave 0 used to take building nw as a second tile: SIMD 0 then
+// holds five tiles of arithmetic and the other three SIMDs four, and all sixteen waves wait at the reduction's barrier for SIMD 0's last wave.  Now
+// wave 0 has no second building; the last four waves, nw - 4 + s on SIMD s, each take strip s of building nw -- envs tile + 64 s + lane, one env per
+// lane -- BEHIND their main tile.  The strip's four plane dwords are requested first in the load block (the main tile's wait covers them: older
+// loads), its parameter block, chain constants and table row are one group of scalar loads, its arithmetic is the tile path's at one env per lane,
+// its five planes go out as non-temporal dword stores, and its four district quantities go to LDS row nw (district_reduce: same bits).
+// The two round-2 builds of this idea (the notes at the top of this block: 7.89 vs 7.94 and 7.36 - 7.49 vs 7.37 - 7.63 us, "nothing") walked the strips
+// BEFORE the main building -- the only order in which the strip's parameter block stayed a scalar load then -- so every strip wave sat out its own
+// strip stores' acknowledgements in front of its main tile.  Table reads through cl::as_ctab are scalar loads wherever they stand and no wave waits
+// behind its stores any more (STORE ACKNOWLEDGEMENTS), so the strip can follow the main tile with nothing but a store burst nobody waits for in between.
+// That alone is still SLOWER than the second tile (7.16 - 7.21 against 7.05 - 7.09 us, twelve alternating rounds in one process): the last four waves
+// are the youngest of their SIMDs, the SIMD issues by priority, then age, so they finish their main tile last and walk the strip's latencies alone.
+// With `s_setprio 3` at their entry the strip hides under the other waves' arithmetic: 6.82 - 7.00 against 7.24 - 7.30 us (profiles/lean_strips_ab.md).
+// A ragged last tile: lane l of the main tile holds envs 4 l .., lane l of strip s env 64 s + l, so a lane can be dead in one and live in the other.
+// The region below is entered by lanes live in EITHER; a lane dead in the main tile walks it on the tile's first envs and stores nothing of it (its
+// partial sums land in LDS columns of dead envs, which the reducer never writes out); a dead lane of a strip does the same for the strip.
 template <int VEC, bool FLEX, bool NT, bool OBS, bool KPI = false, int PREC = 0, bool UNI = false>
 CL_DEV void lean_step_body(const StepArgs& a, float* lds, const ObsFusedArgs* of) {     // lds: [nw][NQ][64*VEC] (, then [64*VEC][pitch])
     static_assert(!UNI || (!FLEX && !OBS && !KPI && PREC == 2), "the uniform body is the plain float64-chain launch's");
     constexpr bool F64 = PREC == 1;
+    constexpr bool SC = UNI && VEC == 4;                            // the instantiation that carries the strip path (STRIPS, above)
     constexpr int TILE = 64 * VEC;
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int env0 = blockIdx.x * TILE + lane * VEC;
-    const bool live = env0 < a.n_env;
+    const int tile_env0 = blockIdx.x * TILE;
+    const bool live = tile_env0 + lane * VEC < a.n_env;
+    // (SC) a lane whose four envs lie beyond a ragged last tile may still hold a live env of a strip: it walks the main tile with the others, on the
+    // tile's first envs (a valid address: n_env is a multiple of four), and stores nothing of it
+    const int env0 = SC && !live ? tile_env0 : tile_env0 + lane * VEC;
     const long long plane = (long long)a.n_bldg * a.ld;
     const int rkind = UNI ? (int)CLR_DEFAULT : (int)((a.flags & CLD_REWARD_MASK) >> CLD_REWARD_SHIFT);
     const bool quirk = a.flags & CLD_REF_T0_QUIRK;
@@ -831,7 +864,23 @@ CL_DEV void lean_step_body(const StepArgs& a, float* lds, const ObsFusedArgs* of
     }
     const int ts_row = a.t + row0;
     const int bb[2] = {w, w + a.nw};
-    const bool own[2] = {bb[0] < a.n_bldg, bb[1] < a.n_bldg};       // wave-uniform
+    // (SC) the strip mapping: one building more than waves, and the host has sized the LDS for the strips' row -- wave-uniform, tested once
+    [[maybe_unused]] bool strips = false;
+    if constexpr (SC) strips = (a.flags & CLA_LEAN_STRIPS) && a.n_bldg == a.nw + 1;
+    const bool own[2] = {bb[0] < a.n_bldg, bb[1] < a.n_bldg && !strips};       // wave-uniform
+    // strip s = w - (nw - 4) of building nw: env tile_env0 + 64 s + lane, one per lane
+    [[maybe_unused]] const bool strip_w = strips && w >= a.nw - 4;
+    [[maybe_unused]] const int x_col = (w - (a.nw - 4)) * 64 + lane;
+    [[maybe_unused]] const bool x_live = strip_w && tile_env0 + x_col < a.n_env;
+    // The strip waves are the YOUNGEST of their SIMDs, and a SIMD issues by priority, then age: left at priority 0 they finish their main tile last
+    // and walk the strip -- a scalar round trip and one dependent float64 chain at one env per lane -- alone, behind everybody else (measured: 7.18
+    // against 7.07 us for wave 0's second tile).  Raised, they finish the main tile first and the strip's latencies hide under the other three
+    // waves' arithmetic (6.91 against 7.27 us; STRIPS, above).
+    if constexpr (SC) {
+        if (strip_w) __builtin_amdgcn_s_setprio(3);
+    }
+    [[maybe_unused]] float x_soc = 0.0f, x_eff = 0.0f, x_deg = 0.0f, x_act = 0.0f;      // the strip's state and action; then its four district quantities
+    [[maybe_unused]] float x_net = 0.0f, x_cost = 0.0f, x_em = 0.0f, x_rw = 0.0f;
 
     float q_net[VEC], q_cost[VEC], q_em[VEC], q_rw[VEC];
 #pragma unroll
@@ -853,7 +902,20 @@ CL_DEV void lean_step_body(const StepArgs& a, float* lds, const ObsFusedArgs* of
     CL_TRACE_DECL;
     CL_TRACE_ENTRY(0);
     CL_TRACE_CYCLES_ENTRY(4);
-    if (live && own[0]) {
+    if ((live || (SC && x_live)) && own[0]) {
+        if constexpr (SC) {
+            // The strip's four dwords, requested FIRST: they are the oldest loads of the wave, so the main building's own wait has them too and
+            // nothing is left to wait for behind its stores.  (A dead lane of a live strip reads the strip's building at the tile's first env.)
+            if (strip_w) {
+                const long long xo = (long long)a.nw * a.ld + tile_env0 + (x_live ? x_col : 0);
+                const float* xa = a.actions + (long long)a.nw * a.act_stride_col + tile_env0 + (x_live ? x_col : 0);
+                float v1[1];
+                pload<1, NTL>(v1, a.state + CLS_B_SOC * plane + xo); x_soc = v1[0];
+                pload<1, NTL>(v1, a.state + CLS_B_EFF * plane + xo); x_eff = v1[0];
+                pload<1, NTL>(v1, a.state + CLS_B_DEGCAP * plane + xo); x_deg = v1[0];
+                pload<1, NTL>(v1, xa); x_act = v1[0];
+            }
+        }
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             if (m && !own[1]) continue;
@@ -1036,17 +1098,20 @@ CL_DEV void lean_step_body(const StepArgs& a, float* lds, const ObsFusedArgs* of
                 }
             }
             CL_TRACE_AFTER(2 + 4 * m, o_rw[VEC - 1]);
-            if (batt) {
-                pstore<VEC, NT>(a.state + CLS_B_SOC * plane + off, s_soc[m]);
-                pstore<VEC, NT>(a.state + CLS_B_EFF * plane + off, s_eff[m]);
-                pstore<VEC, NT>(a.state + CLS_B_DEGCAP * plane + off, s_deg[m]);
-                if constexpr (F64) {
-                    pstore<VEC, NT>(a.state + CLS_B_EFF_LO * plane + off, s_efl[m]);
-                    pstore<VEC, NT>(a.state + CLS_B_DEGCAP_LO * plane + off, s_dgl[m]);
+            // ((SC) the lanes that walk the tile for a strip's sake alone store nothing)
+            if (!SC || live) {
+                if (batt) {
+                    pstore<VEC, NT>(a.state + CLS_B_SOC * plane + off, s_soc[m]);
+                    pstore<VEC, NT>(a.state + CLS_B_EFF * plane + off, s_eff[m]);
+                    pstore<VEC, NT>(a.state + CLS_B_DEGCAP * plane + off, s_deg[m]);
+                    if constexpr (F64) {
+                        pstore<VEC, NT>(a.state + CLS_B_EFF_LO * plane + off, s_efl[m]);
+                        pstore<VEC, NT>(a.state + CLS_B_DEGCAP_LO * plane + off, s_dgl[m]);
+                    }
                 }
+                pstore<VEC, NT>(a.out_bldg + CLO_NET * plane + off, o_net);
+                if (rkind != CLR_MARL && !(FLEX && rkind == CLR_EV)) pstore<VEC, NT>(a.out_bldg + CLO_REWARD * plane + off, o_rw);
             }
-            pstore<VEC, NT>(a.out_bldg + CLO_NET * plane + off, o_net);
-            if (rkind != CLR_MARL && !(FLEX && rkind == CLR_EV)) pstore<VEC, NT>(a.out_bldg + CLO_REWARD * plane + off, o_rw);
             if constexpr (KPI && !FLEX) {
                 // The streaming KPI accumulators of this building, updated by the wave that holds its step in registers (cl_kpi_bldg_kernel's
                 // arithmetic, citylearn.py:1136-1323).  A lean district has no outage and serves its whole load, so the unserved-energy sums
@@ -1106,6 +1171,47 @@ CL_DEV void lean_step_body(const StepArgs& a, float* lds, const ObsFusedArgs* of
             }
             CL_TRACE_AFTER(3 + 4 * m, q_rw[0]);
         }
+        if constexpr (SC) {
+            // The strip, BEHIND the main building's store burst: its inputs landed with the main building's (requested first, above), its scalars
+            // are one group of scalar loads, so nothing between the two pieces of arithmetic waits for a store.  The tile path's expressions at one env per lane.
+            if (strip_w) {
+                const int b = a.nw;
+                const cl::cl_ctab pb = cl::as_ctab(a.params + (long long)b * CL_NP);
+                const cl::cl_ctab qb = cl::as_ctab(a.ts + ((long long)ts_row * a.n_bldg + b) * CL_NF);
+                cl::BattC bc;
+                const float r = cl::pw(pb, CLP_L_TSR);
+                cl::load_battc_from(bc, pb);
+                const float nsl = cl::pw(qb, CLT_NSL), price = cl::pw(qb, CLT_PRICE), carbon = cl::pw(qb, CLT_CARBON);
+                const bool first = quirk && a.t == 0;
+                float c_ns = first ? 3.0f * nsl : nsl;
+                float sol = cl::pw(qb, CLT_SOLAR);
+                const float cbk = first ? 2.0f : 1.0f;
+                CL_PIN_V(c_ns); CL_PIN_V(sol);
+                __builtin_amdgcn_sched_barrier(0);                     // (as in the tile path: the scalar group is complete at the row's first use)
+                CL_PIN_V(x_act);
+                cl::State S = {x_soc, x_eff, x_deg, 0.0f, 0.0f, 0.0f};
+                const float eb = cl::battery_charge_chain(bc, x_act, INFINITY, S);
+                x_net = fmaf(c_ns + cbk * eb, r, sol);
+                x_rw = -fmaxf(x_net, 0.0f);
+                x_cost = cl::mul_rn(x_net, price); x_em = fmaxf(0.0f, x_net * carbon);
+                if (x_live) {
+                    const long long xo = (long long)b * a.ld + tile_env0 + x_col;
+                    const float v_soc[1] = {S.soc}, v_eff[1] = {S.eff}, v_deg[1] = {S.degcap}, v_net[1] = {x_net}, v_rw[1] = {x_rw};
+                    pstore<1, NT>(a.state + CLS_B_SOC * plane + xo, v_soc);
+                    pstore<1, NT>(a.state + CLS_B_EFF * plane + xo, v_eff);
+                    pstore<1, NT>(a.state + CLS_B_DEGCAP * plane + xo, v_deg);
+                    pstore<1, NT>(a.out_bldg + CLO_NET * plane + xo, v_net);
+                    pstore<1, NT>(a.out_bldg + CLO_REWARD * plane + xo, v_rw);
+                }
+            }
+        }
+    }
+    if constexpr (SC) {
+        // building nw's four quantities into the row behind the wave rows, strip s in columns 64 s .. 64 s + 63 (district_reduce, STRIPS)
+        if (strip_w) {
+            float* xr = lds + (size_t)a.nw * NQ * TILE + x_col;
+            xr[0 * TILE] = x_net; xr[1 * TILE] = x_cost; xr[2 * TILE] = x_em; xr[3 * TILE] = x_rw;
+        }
     }
     if constexpr (OBS) {
         if (w == 0) {                                                              // pad columns: zeros (like cl_observe_f32)
@@ -1124,7 +1230,7 @@ CL_DEV void lean_step_body(const StepArgs& a, float* lds, const ObsFusedArgs* of
         //  carry the control series)
         if (base_writer) kpi_series_fetch(base_pre, a.kpi_env + (long long)CLKE_PER_COND * a.n_env + blockIdx.x * TILE, a.n_env);
     }
-    district_reduce<VEC, FLEX, false, KPI && !FLEX>(a, lds, w, lane, env0, live, plane, rkind, q_net, q_cost, q_em, q_rw, a.nw);
+    district_reduce<VEC, FLEX, false, KPI && !FLEX, false, SC>(a, lds, w, lane, env0, live, plane, rkind, q_net, q_cost, q_em, q_rw, a.nw, nullptr, strips);
     if constexpr (KPI && !FLEX) {
         // baseline condition of the district series: the sum of the buildings' baselines in building order, once per env block
         // (district_reduce's barriers came after every wave's write of its buildings' values)
@@ -1922,7 +2028,7 @@ static int step_impl(const cl_dims* dims, const uint32_t* params, const float* t
     a.kpi_bldg = kpi_bldg; a.kpi_env = kpi_env;
     a.act_stride_col = act_stride_col; a.act_stride_env = act_stride_env;
     a.n_env = dims->n_env; a.n_bldg = dims->n_bldg; a.n_steps = dims->n_steps;
-    a.flags = dims->flags; a.t = t; a.env_row0 = dims->env_row0; a.env_offset = (unsigned)dims->env_offset;
+    a.flags = (dims->flags & ~CLA_LEAN_STRIPS) | (p.strips ? CLA_LEAN_STRIPS : 0u); a.t = t; a.env_row0 = dims->env_row0; a.env_offset = (unsigned)dims->env_offset;
     a.ld = ld;
     a.flex_out = nullptr; a.n_flex_bldg = 0; a.ev_penalty_coef = 0.0f;
     a.nw = p.nw; a.b_chunk = p.b_chunk; a.n_chunks = p.n_chunks; a.nt = p.nt; a.fused_finish = p.fused_finish;
@@ -1947,6 +2053,8 @@ static int step_impl(const cl_dims* dims, const uint32_t* params, const float* t
             return hip_fail((hipError_t)rc, "cl_step_lean_kernel launch");
     } else {
         const void* fn = step_kernel_fn(p);
+        if (p.lds > (size_t)CL_LDS_PER_CU)
+            return fail(CL_EINVAL, "the step launch would need %zu bytes of LDS per workgroup (nw=%d, %d envs per lane): a CU has %d", p.lds, p.nw, p.vec, CL_LDS_PER_CU);
         if (p.lds > 64 * 1024)
             if (hipError_t e = ensure_dynamic_lds(fn, p.lds); e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(step kernel)");
         // kernel arguments: (a), (a, of), (a, tp) or (a, tp, of)

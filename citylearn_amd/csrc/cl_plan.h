@@ -110,6 +110,7 @@ struct StepPlan {
     bool lp;                          // cl_step_full*_kernel: parameter blocks staged in LDS
     int maxt, wpe;                    // cl_step_full*_kernel: MAXT, WPE (the multi-tile kernels: WPE)
     int nb;                           // cl_step_envmajor_kernel: NB
+    bool strips;                      // cl_step_lean_chain_kernel<4, ..>, uniform body: the building beyond the waves goes to the last four waves as 64-env strips
     unsigned grid_x, grid_y, block;   // launch shape (block: threads)
     size_t lds;                       // dynamic LDS bytes
     int nw, b_chunk, n_chunks, fused_finish;    // the StepArgs fields the selection sets
@@ -359,6 +360,14 @@ int plan_step(StepPlan& p, const cl_dims& d, const cl_tuning& tun, int64_t act_s
         p.form = kpi_lean ? CLF_KPI : lean_obs ? CLF_OBS : CLF_PLAIN;
         // + one baseline value per building / the observation tile
         p.lds = lds + (kpi_lean ? CL_OBS_FUSED_BLDG * sizeof(float) : lean_obs ? (size_t)tile * obs_pitch * sizeof(float) : 0);
+        // One building more than waves under the uniform body of the plain chain launch at four envs per lane (17 buildings, 16 waves: the headline):
+        // the last four waves -- one per SIMD -- take the extra building as four 64-env strips instead of wave 0 taking a second tile
+        // (csrc/cl_kernels.hip lean_step_body, STRIPS).  Their district partials go to one more LDS row: 17 x 4 x 256 x 4 = 69 632 bytes at 16 waves,
+        // beyond the 64 KB a kernel gets without opting in (the launcher opts in and refuses a request beyond a CU's LDS).
+        // cl_tuning.lean_variant & 32 keeps wave 0's second tile (tests, A/B).
+        p.strips = chain && p.form == CLF_PLAIN && lean_vec == 4 && (d.flags & CLD_LEAN_UNIFORM) && act_stride_env == 1 && p.nw >= 4 &&
+                   d.n_bldg == p.nw + 1 && !(tun.lean_variant & 32);
+        if (p.strips) p.lds += (size_t)CL_NQ * 64 * lean_vec * sizeof(float);
         return CL_OK;
     };
     auto set_full = [&](int maxt, int wpe, bool lp_k) { p.kernel = CLK_FULL; p.maxt = maxt; p.wpe = wpe; p.lp = lp_k; };

@@ -2461,6 +2461,7 @@ int cl_lstm_generic_step_f32(const cl_dims* dims, const float* lstm_w, const flo
             return hip_fail(e, "hipFuncSetAttribute(cl_lstm_generic_kernel)");
     }
     const dim3 ggrid((dims->n_env + 63) / 64, dims->n_bldg), gblock(64 * CL_GEN_NWV);
+    name_add(tuning_of(dims), staged ? "cl_lstm_generic_kernel<true>" : "cl_lstm_generic_kernel<false>");   // (after cl_lstm_step_f32's entry: no reset)
     if (staged) hipLaunchKernelGGL(cl_lstm_generic_kernel<true>, ggrid, gblock, lds, (hipStream_t)stream, g);
     else hipLaunchKernelGGL(cl_lstm_generic_kernel<false>, ggrid, gblock, lds, (hipStream_t)stream, g);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "cl_lstm_generic_kernel launch");

@@ -188,7 +188,8 @@ def test_env_on_the_whole_baeda_district():
 
 def test_lstm_stage_at_full_batch_size_by_replication():
     """3 x 65 536 (the C3 shape): the batch is 128 distinct delivered-cooling columns tiled along the env axis; every env must
-    reproduce, bit for bit, the corresponding env of a 128-env stage (which the reference-fed test covers)."""
+    reproduce, bit for bit, the corresponding env of a 128-env stage (distinct envs against a reference:
+    tests/test_gpu_lstm_synthetic.py::test_trained_models_per_env, the same models at 132 envs)."""
     g = golden('g2023_p2')
     spec = g.spec()
     tab = spec.episode_tables(0)

@@ -256,6 +256,12 @@ CENTRAL_EXTENSIONS = (POLICY_CENTRAL,)
 POLICY_CENTRAL_DEEP = _Extension('policy_central_deep', 'clpcd', 'deep central policy', ['-fno-slp-vectorize'], 'rollout_mlp_f32', PolicyDeepMLP,
                                  headers=[POLICY.header])
 CENTRAL_DEEP_EXTENSIONS = (POLICY_CENTRAL_DEEP,)
+# ... and the THERMAL one under a central-agent policy (cl_policy_full_central.hip; `clpfca_mlp` has `clpf_mlp`'s fields, so `PolicyFullMLP` serves
+# it -- only the shapes of pre / dep differ).  With SLP vectorisation like cl_policy_full.hip (the translation unit says why).  A tuple of its
+# own: the tuples above stay what they are; `__graft_entry__.build()` builds it behind CENTRAL_DEEP_EXTENSIONS.
+POLICY_FULL_CENTRAL = _Extension('policy_full_central', 'clpfca', 'central thermal policy', [], 'rollout_mlp_f32', PolicyFullMLP,
+                                 headers=[POLICY_FULL.header])
+CENTRAL_THERMAL_EXTENSIONS = (POLICY_FULL_CENTRAL,)
 
 # The names other code and the tests use: read-only views of the descriptions above (build / load / check read the description, so rebinding one
 # of these changes nothing -- change the description's attribute instead)
@@ -330,6 +336,15 @@ def policy_central_deep_lds_bytes(nw: int, n_bldg: int, h1: int, h2: int) -> int
     `policy_central_lds_bytes`' regions at ``h1`` units, plus the second hidden layer Hh2 [h2][64] and the staged ``l2`` [h1 + 1][h2] -- 107 776
     bytes at sixteen waves, 32 buildings and 64 x 64 units (tests/test_policy_central_deep_host.py holds it against the header's formula)."""
     return 4 * (nw * 4 * 64 + 2 * n_bldg * 64 + h1 * 64 + h2 * 64 + 2 * h1 * n_bldg + (h1 + 1) * h2 + nw * 2 * (64 + 8))
+
+
+def policy_full_central_lds_bytes(n_bldg: int, h: int) -> int:
+    """Dynamic LDS of one `cl_rollout_full_policy_central_kernel` workgroup over ``n_bldg`` buildings (one wave each, one env per lane) at ``h``
+    hidden units: include/citylearn_amd_policy_full_central.h's formula (csrc/cl_policy_full_central.h's `rollout_full_policy_central_lds_floats`)
+    -- the reduction rows [n_bldg][4][64], the published planes X [5][n_bldg][64], the hidden layer Hh [h][64], the staged ``dep``
+    [h / 4][n_bldg][5][4], the staged head rows [n_bldg][4 x 64 + 4 x 8] -- 92 160 bytes at sixteen buildings and 64 units
+    (tests/test_policy_full_central_host.py holds it against the header's formula)."""
+    return 4 * (n_bldg * 4 * 64 + 5 * n_bldg * 64 + h * 64 + 5 * h * n_bldg + n_bldg * (4 * 64 + 4 * 8))
 
 
 def policy_chunk_lds_bytes(nw: int, vec: int) -> int:

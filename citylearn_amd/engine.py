@@ -594,7 +594,16 @@ class StepEngine:
         ``libcitylearn_amd_policy_central_deep.so``): the central kernel's step with a third phase and workgroup barrier for layer 2, in exact
         fp32; same record, noise stream, reward kinds (MARL included) and ``nw`` invariance.  Its refusals are the central tables': the
         library's for a thermal district, more than 32 buildings and a ``kpi=True`` engine, the `ValueError` above for ``chunked=True`` and the
-        central `NotImplementedError` for ``kpi=True``."""
+        central `NotImplementedError` for ``kpi=True``.
+
+        ``policy_tables`` from `policy.CentralStorageMLPPolicy.pack` (a `CentralStoragePolicyTables`: the central agent's MLP with ONE hidden layer
+        of 4 .. 64 units and up to four storage heads per building) sends a THERMAL district of up to 16 buildings to
+        `cl_rollout_full_policy_central_kernel` (`clpfca_rollout_mlp_f32`, ``libcitylearn_amd_policy_full_central.so``): the steps, record
+        ``[k_steps, CLPF_NT, n_bldg, n_env]`` and noise stream of `cl_rollout_full_policy_kernel` at one env per lane and one building per wave,
+        every reward kind of the thermal kernel, MARL included, with the central kernel's two workgroup barriers per step.  A battery + PV
+        district, more than 16 buildings and a ``kpi=True`` engine are the library's refusals; ``chunked=True`` is the `ValueError` above and
+        ``kpi=True`` the central `NotImplementedError`, which names the heads' action planes: record, then replay ``policy.CLPF_T_ACTION + head``
+        into the columns of `policy.head_columns` on a ``kpi=True`` engine."""
         kind = policy_tables.kind          # (`policy._Kind`: the libraries, the trajectory's plane count and what a build without KPIs raises)
         ext_chunk = kind.ext_chunk or kind.ext_chunk_pair
         if chunked and (ext_chunk is None or (kind.ext_chunk is None and not self.dims.flags & abi.CLD_LEAN)):
@@ -606,8 +615,10 @@ class StepEngine:
                                       'building-chunked battery + PV policy launch keeps no streaming KPI accumulators.  Record the rollout (traj) and feed '
                                       'its action plane through step_many() on a second engine built with kpi=True')
         if kpi and kind.ext_kpi is None and kind.central:
+            planes = ('its action plane (policy.CLPOL_T_ACTION)' if not kind.head_shape else
+                      "its action planes (policy.CLPF_T_ACTION + head, each head's plane into its action column: policy.head_columns)")
             raise NotImplementedError(f'rollout_policy(kpi=True) with {type(policy_tables).__name__}: a central-agent policy has no KPI kernel.  Record '
-                                      'the rollout (traj) and replay its action plane (policy.CLPOL_T_ACTION) through rollout(actions=..., fused=True) '
+                                      f'the rollout (traj) and replay {planes} through rollout(actions=..., fused=True) '
                                       'on a second engine built with kpi=True')
         if kpi and kind.ext_kpi is None:
             planes = ('its action plane (policy.CLPOL_T_ACTION)' if not kind.head_shape else

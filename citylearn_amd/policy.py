@@ -126,10 +126,25 @@ include/citylearn_amd_policy_central_deep.h), whose step has a third phase and b
 
 Its refusals are the central policy's.
 
+On a THERMAL district of up to 16 buildings (the 2020 / 2021 schemas) the central actor is a `CentralStorageMLPPolicy`: the same hidden layer over
+the central-agent vector, H in 4, 8, .. 64, with `StorageMLPPolicy`'s four heads per building, bounds, sigma, noise stream and record
+``[k_steps, CLPF_NT, n_bldg, n_envs]``; the env-dependent inputs are EVERY building's four storage socs and previous net.  One launch of
+`cl_rollout_full_policy_central_kernel` (csrc/cl_policy_full_central.h, ``libcitylearn_amd_policy_full_central.so``,
+include/citylearn_amd_policy_full_central.h), one building per wave and one env per lane, every reward kind of the thermal kernel (MARL included):
+
+    tenv = VectorCityLearnEnv(schema_2020, n_envs, observations='tensor', normalize_observations=True, central_agent=True)
+    scentral = CentralStorageMLPPolicy(w1, b1, w2, b2, sigma=0.1)     # w1 [n_sets, H, n_cols], b1 [n_sets, H], w2 [n_sets, n_bldg, 4, H], b2 [n_sets, n_bldg, 4]
+    ret, traj = tenv.rollout_policy(scentral, 24, seed=3, record=True)
+
+An env built with ``central_agent=False`` raises `ValueError`; ``kpi=True`` raises `NotImplementedError` (record, then replay the heads' action
+planes ``CLPF_T_ACTION + head`` into the columns of `head_columns` on a ``kpi=True`` env); more than 16 buildings and a battery + PV district are
+the library's refusals.  No local fixture has a heating tank: the heating-storage term and head are exercised by the packer test only.
+
 Open: device-action heads, streaming KPIs in the chunked battery + PV launch, MARL in chunked launches (the libraries' refusal); for the deep
 policy a KPI twin, a chunked twin, MARL, hidden layers wider than 32 or deeper than two; for the deep thermal policy a KPI twin, more than 16
-buildings, device-action heads, two envs per lane, hidden layers wider than 32 or deeper than two; for both central policies a KPI twin, more
-than 32 buildings, thermal districts; for the deep central policy a matrix-core family of layer 2, hidden layers deeper than two.
+buildings, device-action heads, two envs per lane, hidden layers wider than 32 or deeper than two; for both battery + PV central policies a KPI
+twin, more than 32 buildings; for the deep central policy a matrix-core family of layer 2, thermal districts, hidden layers deeper than two; for
+the central thermal policy a KPI twin, more than 16 buildings, two hidden layers, device-action heads.
 """
 from __future__ import annotations
 
@@ -179,6 +194,10 @@ CLPCA_MAX_HIDDEN, CLPCA_MAX_BLDG = CENTRAL_CONSTANTS['CLPCA_MAX_HIDDEN'], CENTRA
 # ... with two hidden layers (csrc/cl_policy_central_deep.h, libcitylearn_amd_policy_central_deep.so)
 CENTRAL_DEEP_CONSTANTS = _header_constants(_lib.POLICY_CENTRAL_DEEP.header, 'CLPCD_')
 CLPCD_MAX_HIDDEN, CLPCD_MAX_BLDG = CENTRAL_DEEP_CONSTANTS['CLPCD_MAX_HIDDEN'], CENTRAL_DEEP_CONSTANTS['CLPCD_MAX_BLDG']
+# a central agent on a thermal district (csrc/cl_policy_full_central.h, libcitylearn_amd_policy_full_central.so): the record and the noise stream
+# are the thermal kernel's
+FULL_CENTRAL_CONSTANTS = _header_constants(_lib.POLICY_FULL_CENTRAL.header, 'CLPFCA_')
+CLPFCA_MAX_HIDDEN, CLPFCA_MAX_BLDG = FULL_CENTRAL_CONSTANTS['CLPFCA_MAX_HIDDEN'], FULL_CENTRAL_CONSTANTS['CLPFCA_MAX_BLDG']
 HEAD_NAMES = ('electrical_storage', 'cooling_storage', 'heating_storage', 'dhw_storage')                  # heads in CLPF_A_* order
 
 
@@ -353,6 +372,25 @@ class DeepCentralPolicyTables(CentralPolicyTables):
                                 p(self.act_low), p(self.act_high), p(self.sigma), int(seed) & (2 ** 64 - 1), self.n_hidden2, 0, p(self.l2))
 
 
+class CentralStoragePolicyTables(CentralPolicyTables):
+    """`CentralStorageMLPPolicy.pack`'s result.  ``pre [n_sets, n_rows, H]`` has NO building axis; ``dep [n_sets, H / 4, n_bldg, CLPF_ND, 4]`` holds,
+    per group of four hidden units and building, the four weights of each of the five terms in `CLPF_D_*` order (``ACT_SCALE * W1[j][c] *
+    col_scale[c]``, 0 where the building has no such column or storage) -- the order the kernel walks them in; ``out = [w2 | b2]``
+    ``[n_sets, n_bldg, CLPF_NA, H + 1]``.  The host side is `StoragePolicyTables`': ``[n_bldg, CLPF_NA]`` each, ``cols`` = every head's action
+    column (-1: none)."""
+
+    def __init__(self, pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, cols, low_bldg, high_bldg, sigma_bldg, version):
+        super().__init__(pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, cols, low_bldg, high_bldg, sigma_bldg, version)
+        self.n_device_cols = 0                                           # (the struct's third word: refused by `pack` otherwise)
+
+    es_cols = property(lambda self: self.cols[:, CLPF_A_ES])
+
+    def dep_terms(self) -> torch.Tensor:
+        """``dep`` as ``[n_sets, n_bldg, CLPF_ND, H]`` (building, term, hidden unit): `StoragePolicyTables.dep`'s axes."""
+        S, G, B = self.n_sets, self.n_hidden // 4, self.n_bldg
+        return self.dep.reshape(S, G, B, CLPF_ND, 4).permute(0, 2, 3, 1, 4).reshape(S, B, CLPF_ND, G * 4)
+
+
 def _l2_fragments(w2s: np.ndarray, b2s: np.ndarray) -> np.ndarray:
     """The matrix-core layout of layer 2 (`DeepPolicyTables`) from the scaled weights ``[S, B, H2, H1]`` and biases ``[S, B, H2]`` (float64):
     float32 ``[S, B, 1024 + 32 + 4]``."""
@@ -437,6 +475,12 @@ _CENTRAL_DEEP = _Kind(terms=_LEAN.terms, head_slots=_LEAN.head_slots, head_shape
                       tables=DeepCentralPolicyTables, struct=_lib.PolicyDeepMLP, constants=CENTRAL_DEEP_CONSTANTS, max_hidden=CLPCD_MAX_HIDDEN,
                       n_planes=CLPOL_NT, ext=_lib.POLICY_CENTRAL_DEEP, ext_kpi=None, no_kpi_error=NotImplementedError, one_row_max=CLPCD_MAX_BLDG,
                       central=True)
+# a central agent on a thermal district: the thermal kind's inputs (of EVERY building), heads, record and one-row geometry; a library of its own and
+# neither a KPI nor a chunked twin
+_CENTRAL_THERMAL = _Kind(terms=_THERMAL.terms, head_slots=_THERMAL.head_slots, head_shape=(CLPF_NA,), refuse_device_actions=True, only=_THERMAL.only,
+                         tables=CentralStoragePolicyTables, struct=_lib.PolicyFullMLP, constants=FULL_CENTRAL_CONSTANTS, max_hidden=CLPFCA_MAX_HIDDEN,
+                         n_planes=CLPF_NT, ext=_lib.POLICY_FULL_CENTRAL, ext_kpi=None, no_kpi_error=NotImplementedError, one_row_max=CLPFCA_MAX_BLDG,
+                         central=True)
 # (terms and heads above are written in the header's order)
 assert (CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET) == tuple(range(CLPF_ND)) and (CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS) == tuple(range(CLPF_NA))
 
@@ -1218,3 +1262,118 @@ class DeepCentralMLPPolicy:
         l2 = (torch.cat([f64(w2).transpose(1, 2), f64(b2)[:, None, :]], dim=1) * ACT_SCALE).to(torch.float32)
         out = torch.cat([f64(w3), f64(b3)[..., None]], dim=-1)
         return DeepCentralPolicyTables(pre, dep, l2.contiguous(), out.to(torch.float32).contiguous(), *rest, self.version)
+
+
+class CentralStorageMLPPolicy:
+    """CityLearn's ``central_agent=True`` actor on a THERMAL district: ONE tanh MLP with one hidden layer over the district's observation vector
+    returns every building's storage actions, up to four heads per building in the fixed order electrical, cooling, heating, DHW storage
+    (`HEAD_NAMES`, `CLPF_A_*`),
+
+        h = tanh(W1 obs + b1),   act[b][a] = clamp(mid + half tanh(w2[b][a] . h + b2[b][a]) + sigma z, low, high)
+
+    for every head whose building has that action column (the others are ignored).  `obs` = the central-agent observation vector as the env
+    defines it (``ObservationLayout(..., central_agent=True).columns``); the bounds, sigma, z and the noise stream -- Philox keyed by the head's
+    action column -- are `StorageMLPPolicy`'s.  The env-dependent inputs are EVERY building's own ``electrical_storage_soc`` /
+    ``cooling_storage_soc`` / ``heating_storage_soc`` / ``dhw_storage_soc`` and ``net_electricity_consumption``.  Thermal districts without the LSTM
+    stage and without device actions (the 2020 / 2021 schemas) of up to 16 buildings: one launch of `cl_rollout_full_policy_central_kernel`
+    (csrc/cl_policy_full_central.h, ``libcitylearn_amd_policy_full_central.so``).
+
+    ``w1 [n_sets, H, n_cols]``, ``b1 [n_sets, H]``, ``w2 [n_sets, n_bldg, 4, H]``, ``b2 [n_sets, n_bldg, 4]`` (anything array-like; kept in
+    float64); a leading dimension of 1 broadcasts.  ``H``: 4, 8, .. 64.  ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
+
+    The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
+    kind = _CENTRAL_THERMAL
+    _NAMES = ('w1', 'b1', 'w2', 'b2')
+
+    def __init__(self, w1, b1, w2, b2, sigma=None):
+        self.w1, self.b1, self.w2, self.b2 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2))
+        if [getattr(self, n).ndim for n in self._NAMES] != [3, 2, 4, 3]:
+            raise ValueError(f'w1 [n_sets, H, n_cols], b1 [n_sets, H], w2 [n_sets, n_bldg, {CLPF_NA}, H], b2 [n_sets, n_bldg, {CLPF_NA}]')
+        self.n_hidden, self.n_obs, self.n_bldg = int(self.w1.shape[1]), int(self.w1.shape[2]), int(self.w2.shape[1])
+        if self.n_hidden % 4 or not 4 <= self.n_hidden <= CLPFCA_MAX_HIDDEN:
+            raise ValueError(f'H={self.n_hidden}: the central thermal policy kernel takes 4, 8, .. {CLPFCA_MAX_HIDDEN} hidden units')
+        if self.b1.shape[1] != self.n_hidden or self.w2.shape[2:] != (CLPF_NA, self.n_hidden) or self.b2.shape[1:] != (self.n_bldg, CLPF_NA):
+            raise ValueError(f'b1 / w2 disagree with w1 about H, b2 with w2 about n_bldg, or w2 / b2 do not have {CLPF_NA} heads')
+        self.n_sets = max(getattr(self, n).shape[0] for n in self._NAMES)
+        self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
+        self.version = 0
+
+    invalidate = _MLPBase.invalidate
+    update = _MLPBase.update
+    _check_layout = CentralMLPPolicy._check_layout
+    _pack_front = CentralMLPPolicy._pack_front
+
+    def _full(self, n_bldg: Optional[int] = None):
+        S, H, B = self.n_sets, self.n_hidden, self.n_bldg
+        if n_bldg is not None and n_bldg != B:
+            raise ValueError(f'w2 has heads for {B} buildings, the district has {n_bldg}')
+        shapes = ((S, H, self.n_obs), (S, H), (S, B, CLPF_NA, H), (S, B, CLPF_NA))
+        try:
+            return tuple(np.broadcast_to(getattr(self, n), sh) for n, sh in zip(self._NAMES, shapes))
+        except ValueError as e:
+            raise ValueError(f'the weights do not broadcast to {S} sets: {e}') from None
+
+    # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
+    def actions_host(self, obs, tables: CentralStoragePolicyTables, noise=None, set_index: int = 0) -> np.ndarray:
+        """float64 numpy evaluation of the plain MLP: ``obs [..., n_cols]`` (the central-agent vector) -> actions ``[..., n_bldg, 4]`` (0 for a
+        head whose column the building lacks).  ``noise``: the standard normals z (same shape as the result; `noise_host` replays the kernel's),
+        scaled by each head's sigma.  The heads' columns, bounds and sigmas come from ``tables`` (a `pack` result)."""
+        x = np.asarray(obs, dtype=np.float64)
+        w1, b1, w2, b2 = (v[set_index] for v in self._full())
+        h = np.tanh(np.einsum('jc,...c->...j', w1, x) + b1)
+        lo, hi = tables.low_bldg, tables.high_bldg
+        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('baj,...j->...ba', w2, h) + b2)
+        if noise is not None:
+            a = a + tables.sigma_bldg * np.asarray(noise, dtype=np.float64)
+        return np.where(tables.cols >= 0, np.clip(a, lo, hi), 0.0)
+
+    def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
+        """The same MLP (no noise) written in torch over the env's observation TENSOR of a ``central_agent=True`` env: a
+        `VectorCityLearnEnv.capture_rollout` policy ``f(obs [n_envs, n_cols], i=None) -> actions [n_act_cols, n_envs]``."""
+        self._check_layout(layout)
+        w1, b1, w2, b2 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(len(layout.building_names)))
+        hc = _head_columns(tab, self.kind)
+        low, high = layout.spec.action_limits()
+        sel = np.nonzero(hc >= 0)                                                # the heads that have a column
+        rows = torch.as_tensor(hc[sel], device=device)
+        lo = torch.as_tensor(np.asarray(low)[hc[sel]], dtype=dtype, device=device)
+        hi = torch.as_tensor(np.asarray(high)[hc[sel]], dtype=dtype, device=device)
+        flat = torch.as_tensor(np.ravel_multi_index(sel, hc.shape), device=device)
+        w2f, b2f = w2.reshape(-1, w2.shape[-1])[flat], b2.reshape(-1)[flat]     # [present heads, H], [present heads]
+        n_act = len(low)
+
+        def f(obs, i=None):
+            h = torch.tanh(obs.to(dtype) @ w1.t() + b1)                          # [E, H]
+            o = torch.tanh(h @ w2f.t() + b2f)                                    # [E, present heads]
+            a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
+            out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
+            out[rows] = a.t().to(torch.float32)
+            return out
+        return f
+
+    # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
+    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None) -> CentralStoragePolicyTables:
+        """Split the first layer as `CentralMLPPolicy.pack` splits it (the same function), over the central-agent vector of `layout` (built with
+        ``central_agent=True``) and the thermal kind's FIVE terms: the env-independent columns of every table row go into ``pre
+        [n_sets, n_rows, H]``, ``W1[j][c] * col_scale[c]`` of the env-dependent columns (every building's own storage socs and
+        ``net_electricity_consumption``) into ``dep`` in the kernel's order (`CentralStoragePolicyTables`; the rows of a storage the building
+        lacks stay 0), their table offsets into ``pre``; ``ACT_SCALE`` is folded into both.  Refused with `StorageMLPPolicy.pack`'s messages: a
+        column fed by any other device plane (the LSTM stage's indoor temperature among them), a reset value its table row does not hold, a
+        building with a cooling / heating device ACTION column; with `CentralMLPPolicy.pack`'s: a layout built with ``central_agent=False``, a
+        vector of another length."""
+        self._check_layout(layout)
+        kind = self.kind
+        w1, b1, w2, b2 = self._full(len(layout.building_names))
+        pre, dep, rest = self._pack_front(layout, tab, w1, b1, device, set_of_block)
+        params_i = np.ascontiguousarray(tab.params).view(np.int32)
+        bflags = np.ascontiguousarray(tab.params).view(np.uint32)[:, abi.CLP_FLAGS]
+        for i in range(len(layout.building_names)):
+            for dname, slot in _DEVICE_SLOTS:
+                if params_i[i, slot] >= 0:
+                    raise ValueError(f'action {dname!r} of building {i} (column {int(params_i[i, slot])}): the thermal policy kernel has storage heads '
+                                     f'only {HEAD_NAMES}; a district with device actions runs through capture_rollout')
+        # a storage the building lacks: its plane stays 0 in the kernel, its weights are 0 here
+        has = np.array([[flag is None or bool(int(bflags[i]) & flag) for _, flag in kind.terms] for i in range(len(layout.building_names))])
+        dep = dep * torch.from_numpy(has.astype(np.float32)).to(dep.device)[None, None, :, :, None]
+        out = torch.cat([torch.from_numpy(np.array(v, dtype=np.float64)).to(pre.device) for v in (w2, b2[..., None])], dim=-1)
+        return CentralStoragePolicyTables(pre, dep.contiguous(), out.to(torch.float32).contiguous(), *rest, self.version)

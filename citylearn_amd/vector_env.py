@@ -462,14 +462,23 @@ class VectorCityLearnEnv:
 
         A `policy.DeepCentralMLPPolicy` (the central agent's MLP with TWO hidden layers of 4 .. 64 units each) drives the same districts of an
         env built with ``central_agent=True`` through `cl_rollout_policy_central_deep_kernel`; record, noise stream, MARL and every refusal are
-        the `CentralMLPPolicy`'s."""
+        the `CentralMLPPolicy`'s.
+
+        A `policy.CentralStorageMLPPolicy` (ONE MLP over the central-agent observation vector, up to four storage heads per building) drives a
+        THERMAL district of up to 16 buildings of an env built with ``central_agent=True`` through `cl_rollout_full_policy_central_kernel`, same
+        record (`policy.CLPF_NT` planes) and noise stream as a `StorageMLPPolicy`, MARL included; on an env built with ``central_agent=False`` it
+        is a `ValueError`.  More than 16 buildings (no chunked launch is asked for: the hidden layer cannot be cut into building chunks) and a
+        battery + PV district are the library's refusals; ``kpi=True`` raises `NotImplementedError` (record, then replay the heads' action planes
+        on a ``kpi=True`` env)."""
         chunked =(policy.kind.ext_chunk or policy.kind.ext_chunk_pair) is not None and self.engine.n_bldg > policy.kind.one_row_max
         if policy.kind.central and not self.central_agent:
             raise ValueError(f'a {type(policy).__name__} needs an env built with central_agent=True: this env hands out one observation vector per '
                              'building, which is not the vector the policy\'s weights are defined over')
         if kpi and policy.kind.ext_kpi is None and policy.kind.central:
+            planes = ('its action plane (policy.CLPOL_T_ACTION)' if not policy.kind.head_shape else
+                      "its action planes (policy.CLPF_T_ACTION + head, each head's plane into its action column: policy.head_columns)")
             raise NotImplementedError(f'rollout_policy(kpi=True) with a {type(policy).__name__}: a central-agent policy has no KPI kernel -- record the '
-                                      'rollout (record=True) and replay its action plane (policy.CLPOL_T_ACTION) through '
+                                      f'rollout (record=True) and replay {planes} through '
                                       'rollout(actions=..., fused=True) on an env built with kpi=True')
         if kpi and policy.kind.ext_kpi is None:
             planes = ('its action plane (policy.CLPOL_T_ACTION)' if not policy.kind.head_shape else

@@ -13,6 +13,9 @@
 #ifndef CL_LEAN_NT_LOADS
 #define CL_LEAN_NT_LOADS true          // A/B build flag: false = no non-temporal hint on any plane load of the latency-ordered lean kernels (lean_step_body's note)
 #endif
+#ifndef CL_LEAN_ONE_EACH
+#define CL_LEAN_ONE_EACH true          // A/B build flag: false = the headline's district sums through the reducer's general loop (district_reduce, STRIPS)
+#endif
 #include "cl_philox.h"
 
 #include <type_traits>
@@ -287,6 +290,24 @@ CL_DEV void district_reduce(const StepArgs& a, float* lds, int w, int lane, int 
         vstore<VEC>(mine + 3 * TILE, q_rw);
     }
     const int tile_env0 = bx * TILE;
+    // (STRIPS: the uniform body at four envs per lane, default reward) One workgroup row of sixteen waves -- the headline -- has exactly one district
+    // sum per thread.  Its LDS column and its out_env address are worked out in FRONT of the barrier; behind it stand the strip row's read, sixteen
+    // wave-row reads issued back to back, the adds in the loop's order (strip row first, then rows 0 .. 15: the same bits) and one store.  The loop
+    // below spends about a hundred instructions behind the barrier on that one sum: it fetches the block-size argument (a scalar round trip), sets up
+    // two nested loops for a trip count of one, and waits after every pair of reads.  Sixteen waves are known from a.nw, which the wave holds already.
+    // Any other geometry takes the loop.  (The two values are made opaque in front of the barrier: left alone, the compiler sinks their arithmetic
+    // behind it.  The address as an index into out_env -- a pointer would come out of the asm statement as a generic one, a flat store.  -1: an env
+    // beyond the batch.)
+    [[maybe_unused]] bool one_each = false;
+    [[maybe_unused]] long long one_out = -1;
+    [[maybe_unused]] uint32_t one_i = 0;
+    if constexpr (STRIPS) {
+        one_each = CL_LEAN_ONE_EACH && a.n_chunks == 1 && a.nw * 64 == NQ * TILE;
+        one_i = threadIdx.x;
+        const uint32_t q = one_i / TILE, e = one_i % TILE;
+        one_out = tile_env0 + (int)e < a.n_env ? (long long)q * a.n_env + tile_env0 + e : -1;
+        asm volatile("" : "+v"(one_out), "+v"(one_i));
+    }
     // (KPIS) the control series' accumulators of the env whose district net this thread is about to write: in flight across the barrier
     [[maybe_unused]] KpiSeries pre;
     if constexpr (KPIS) {
@@ -294,6 +315,21 @@ CL_DEV void district_reduce(const StepArgs& a, float* lds, int w, int lane, int 
     }
     __syncthreads();
     const bool coupled = rkind == CLR_MARL || (FLEX && rkind == CLR_EV);   // rewards that need the district net
+    if constexpr (STRIPS) {
+        if (one_each && !coupled) {
+            const float* col = lds + one_i;
+            const float x = col[strip_row ? (size_t)16 * NQ * TILE : 0];       // (without a strip row: row 0 once more, not used)
+            float r[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) r[k] = col[(size_t)k * NQ * TILE];
+            __builtin_amdgcn_sched_barrier(0);                                 // every read is issued before the first add
+            float s = strip_row ? x : 0.0f;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) s += r[k];
+            if (one_out >= 0) a.out_env[one_out] = s;
+            return;
+        }
+    }
     if (a.n_chunks > 1) {
         // Large districts: this workgroup only saw buildings [y*b_chunk, (y+1)*b_chunk).  Its partial sums go to the scratch rows of
         // out_bldg's reserved plane; cl_finish_kernel (a second launch, 4.8 us of pure latency) adds the chunks in a fixed order.

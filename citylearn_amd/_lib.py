@@ -289,7 +289,7 @@ build_policy_chunk, load_policy_chunk, check_policy_chunk = POLICY_CHUNK.build, 
 
 
 def policy_kpi_lds_bytes(nw: int, vec: int) -> int:
-    """Dynamic LDS of one `cl_rollout_policy_kpi_kernel` workgroup of ``nw`` waves at ``vec`` envs per lane: csrc/cl_policy_kpi.h's
+    """Dynamic LDS of one `cl_rollout_policy_kpi_kernel` workgroup of ``nw`` waves at ``vec`` envs per lane: csrc/cl_policy.h's
     `rollout_policy_kpi_lds_floats` -- the KPI kernel's ring [8][nw][tile], series [12][tile] + [16], baseline rows [8][4][32] + [5][32], then the
     policy's staged rows [nw][2][3 x 32 + 8] (tests/test_policy_kpi_host.py holds it against the header's formula)."""
     tile = 64 * vec
@@ -332,7 +332,7 @@ def policy_central_lds_bytes(nw: int, n_bldg: int, h: int) -> int:
 
 def policy_central_deep_lds_bytes(nw: int, n_bldg: int, h1: int, h2: int) -> int:
     """Dynamic LDS of one `cl_rollout_policy_central_deep_kernel` workgroup of ``nw`` waves over ``n_bldg`` buildings at ``h1`` x ``h2`` hidden
-    units: include/citylearn_amd_policy_central_deep.h's formula (csrc/cl_policy_central_deep.h's `rollout_policy_central_deep_lds_floats`) --
+    units: include/citylearn_amd_policy_central_deep.h's formula (csrc/cl_policy_central.h's `rollout_policy_central_deep_lds_floats`) --
     `policy_central_lds_bytes`' regions at ``h1`` units, plus the second hidden layer Hh2 [h2][64] and the staged ``l2`` [h1 + 1][h2] -- 107 776
     bytes at sixteen waves, 32 buildings and 64 x 64 units (tests/test_policy_central_deep_host.py holds it against the header's formula)."""
     return 4 * (nw * 4 * 64 + 2 * n_bldg * 64 + h1 * 64 + h2 * 64 + 2 * h1 * n_bldg + (h1 + 1) * h2 + nw * 2 * (64 + 8))
@@ -349,7 +349,7 @@ def policy_full_central_lds_bytes(n_bldg: int, h: int) -> int:
 
 def policy_chunk_lds_bytes(nw: int, vec: int) -> int:
     """Dynamic LDS of one `cl_rollout_policy_chunk_kernel` workgroup of ``nw`` waves (two buildings each) at ``vec`` envs per lane:
-    csrc/cl_policy_chunk.h's `rollout_policy_chunk_lds_floats`, which is `cl_rollout_policy_kernel`'s formula -- the chunk's reduction rows
+    csrc/cl_policy_chunk.h's `rollout_policy_chunk_lds_floats`, which is the one-row launch's formula (csrc/cl_policy.h) -- the chunk's reduction rows
     [nw][4][tile], then the staged policy rows [nw][2][3 x 32 + 8] -- 29 696 bytes at sixteen waves and one env per lane, 46 080 at two
     (tests/test_policy_chunk_host.py holds it against the header's formula)."""
     return 4 * (nw * 4 * 64 * vec + nw * 2 * (3 * 32 + 8))

@@ -1,5 +1,5 @@
 // cl_policy.hip -- the translation unit of libcitylearn_amd_policy.so (include/citylearn_amd_policy.h): cl_kernels.hip reduced to the helpers the
-// fused rollout kernels share (CL_TU_NOSLP's cut, minus its launchers: CL_TU_POLICY) + cl_policy.h's closed-loop kernel, its launcher and the
+// fused rollout kernels share (CL_TU_NOSLP's cut, minus its launchers: CL_TU_POLICY) + cl_policy.h's closed-loop kernel at KPI = false, its launcher and the
 // `clpol_*` entry points.  Compiled with -fno-slp-vectorize like the other rollout kernels (citylearn_amd/_lib.py): same arithmetic, same loss to
 // packed fp32.
 #define CL_TU_NOSLP
@@ -12,7 +12,7 @@ namespace {
 
 // the launcher of this unit (the main library's cl_tu_launch_* stay what they are); key = 10 * envs per lane + PREC
 int launch_policy(int vec, int prec, unsigned grid, unsigned block, size_t lds, hipStream_t s, const PolicyArgs& p) {
-#define CL_POL(V, P) CL_POLICY_LAUNCH(cl_rollout_policy_kernel<V, P>)
+#define CL_POL(V, P) CL_POLICY_LAUNCH(cl_rollout_policy_kernel<V, P, false, false>)
     switch (vec * 10 + prec) {
     case 10: CL_POL(1, 0); break;
     case 20: CL_POL(2, 0); break;

@@ -1,6 +1,6 @@
 // cl_policy_central.hip -- the translation unit of libcitylearn_amd_policy_central.so (include/citylearn_amd_policy_central.h): cl_kernels.hip reduced
 // to the helpers the fused rollout kernels share (CL_TU_POLICY, as in cl_policy.hip) + cl_policy_central.h's closed-loop kernel under a central-agent
-// policy, its launcher and the `clpca_*` entry points.  Compiled with -fno-slp-vectorize like cl_policy.hip (citylearn_amd/_lib.py).
+// policy at DEEP = false (one hidden layer), its launcher and the `clpca_*` entry points.  Compiled with -fno-slp-vectorize like cl_policy.hip (citylearn_amd/_lib.py).
 #define CL_TU_NOSLP
 #define CL_TU_POLICY
 #include "cl_kernels.hip"
@@ -9,11 +9,13 @@
 
 namespace {
 
+static_assert(CLPCA_MAX_HIDDEN == CLPC_MAX_HIDDEN, "the staged out row is sized for the public header's limit");
+
 // the launcher of this unit; key = PREC
 int launch_policy_central(int prec, unsigned grid, unsigned block, size_t lds, hipStream_t s, const PolicyArgs& p) {
     switch (prec) {
-    case 0: CL_POLICY_LAUNCH(cl_rollout_policy_central_kernel<0>); break;
-    case 2: CL_POLICY_LAUNCH(cl_rollout_policy_central_kernel<2>); break;
+    case 0: CL_POLICY_LAUNCH(cl_rollout_policy_central_kernel<0, false>); break;
+    case 2: CL_POLICY_LAUNCH(cl_rollout_policy_central_kernel<2, false>); break;
     default: return (int)hipErrorInvalidValue;
     }
     return (int)hipGetLastError();
@@ -48,7 +50,7 @@ int clpca_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const flo
     const cl_tuning& tun = dims->tuning ? *dims->tuning : cl_tuning{};
     PolicyArgs p;
     fill_policy_args(p, dims, *mlp, CLPOL_NOISE_KEY, call);
-    if (int rc = central_policy_geometry(dims, tun, p.r.s.nw)) return rc;
+    if (int rc = central_policy_geometry(dims, tun, "central policy", p.r.s.nw)) return rc;
     const int nw = p.r.s.nw;
     const size_t lds = rollout_policy_central_lds_floats(nw, dims->n_bldg, mlp->n_hidden) * sizeof(float);
     if (int rc = check_policy_lds(lds, "central policy", nw, 1)) return rc;

@@ -1,20 +1,22 @@
 // cl_policy_central_deep.hip -- the translation unit of libcitylearn_amd_policy_central_deep.so (include/citylearn_amd_policy_central_deep.h):
-// cl_kernels.hip reduced to the helpers the fused rollout kernels share (CL_TU_POLICY, as in cl_policy.hip) + cl_policy_central_deep.h's closed-loop
-// kernel under a central-agent policy with two hidden layers, its launcher and the `clpcd_*` entry points.  Compiled with -fno-slp-vectorize like
+// cl_kernels.hip reduced to the helpers the fused rollout kernels share (CL_TU_POLICY, as in cl_policy.hip) + cl_policy_central.h's closed-loop
+// kernel under a central-agent policy at DEEP = true (two hidden layers), its launcher and the `clpcd_*` entry points.  Compiled with -fno-slp-vectorize like
 // cl_policy.hip (citylearn_amd/_lib.py).
 #define CL_TU_NOSLP
 #define CL_TU_POLICY
 #include "cl_kernels.hip"
 #include "../../include/citylearn_amd_policy_central_deep.h"
-#include "cl_policy_central_deep.h"
+#include "cl_policy_central.h"
 
 namespace {
+
+static_assert(CLPCD_MAX_HIDDEN == CLPC_MAX_HIDDEN, "the staged out row is sized for the public header's limit");
 
 // the launcher of this unit; key = PREC
 int launch_policy_central_deep(int prec, unsigned grid, unsigned block, size_t lds, hipStream_t s, const CentralDeepPolicyArgs& p) {
     switch (prec) {
-    case 0: CL_POLICY_LAUNCH(cl_rollout_policy_central_deep_kernel<0>); break;
-    case 2: CL_POLICY_LAUNCH(cl_rollout_policy_central_deep_kernel<2>); break;
+    case 0: CL_POLICY_LAUNCH(cl_rollout_policy_central_kernel<0, true>); break;
+    case 2: CL_POLICY_LAUNCH(cl_rollout_policy_central_kernel<2, true>); break;
     default: return (int)hipErrorInvalidValue;
     }
     return (int)hipGetLastError();
@@ -51,7 +53,7 @@ int clpcd_rollout_mlp_f32(const cl_dims* dims, const uint32_t* params, const flo
     CentralDeepPolicyArgs p;
     fill_policy_args(p.p, dims, *mlp, CLPOL_NOISE_KEY, call);
     p.l2 = mlp->l2; p.n_hidden2 = mlp->n_hidden2;
-    if (int rc = central_deep_policy_geometry(dims, tun, p.p.r.s.nw)) return rc;
+    if (int rc = central_policy_geometry(dims, tun, "deep central policy", p.p.r.s.nw)) return rc;
     const int nw = p.p.r.s.nw;
     const size_t lds = rollout_policy_central_deep_lds_floats(nw, dims->n_bldg, mlp->n_hidden, mlp->n_hidden2) * sizeof(float);
     if (int rc = check_policy_lds(lds, "deep central policy", nw, 1)) return rc;

@@ -1,7 +1,7 @@
 // cl_policy_chunk.hip -- the translation unit of libcitylearn_amd_policy_chunk.so (include/citylearn_amd_policy_chunk.h): cl_kernels.hip reduced as
 // for cl_policy.hip (CL_TU_NOSLP, CL_TU_POLICY) but WITH cl_finish_kernel (CL_TU_FINISH: the fold of the chunk partial sums, which a
-// building-chunked launch needs behind it), cl_policy.h for the staged-row layout (its kernel template is never instantiated here),
-// cl_policy_chunk.h's kernel, its launcher and the `clpc_*` entry points.  Compiled with -fno-slp-vectorize like cl_policy.hip.
+// building-chunked launch needs behind it), cl_policy.h's closed-loop kernel at CHUNK = true (cl_policy_chunk.h says what that switches; reported
+// as cl_rollout_policy_chunk_kernel<VEC, PREC>; no other variant is instantiated here), its launcher and the `clpc_*` entry points.  Compiled with -fno-slp-vectorize like cl_policy.hip.
 #define CL_TU_NOSLP
 #define CL_TU_POLICY
 #define CL_TU_FINISH
@@ -13,7 +13,7 @@ namespace {
 
 // the launcher of this unit; key = 10 * envs per lane + PREC
 int launch_policy_chunk(int vec, int prec, dim3 grid, unsigned block, size_t lds, hipStream_t s, const PolicyArgs& p) {
-#define CL_POLC(V, P) CL_POLICY_LAUNCH(cl_rollout_policy_chunk_kernel<V, P>)
+#define CL_POLC(V, P) CL_POLICY_LAUNCH(cl_rollout_policy_kernel<V, P, false, true>)
     switch (vec * 10 + prec) {
     case 10: CL_POLC(1, 0); break;
     case 20: CL_POLC(2, 0); break;

@@ -1,4 +1,4 @@
-// cl_policy_common.h -- what the eight closed-loop policy units share (cl_policy.hip, cl_policy_kpi.hip, cl_policy_chunk.hip, cl_policy_deep.hip
+// cl_policy_common.h -- what the closed-loop policy units share (cl_policy.hip, cl_policy_kpi.hip, cl_policy_chunk.hip, cl_policy_deep.hip
 // for battery + PV districts; cl_policy_full.hip, cl_policy_full_kpi.hip, cl_policy_full_chunk.hip, cl_policy_full_chunk_kpi.hip for thermal ones;
 // each behind cl_kernels.hip's helpers and cl_rollout.h).  The ONE copy of each:
 //   device  PolicyArgs, the hidden unit's activation (clpol_unit), the Box-Muller draw (clpol_gauss);
@@ -12,8 +12,10 @@
 //           chunk_partials_fit / check_chunk_partials, launch_rollout_finish;
 //           the launch macro (CL_POLICY_LAUNCH).
 // What is an entry's own stays written out in it: the CLD_LEAN and CLD_KPI redirects, n_bldg > 16 / 32, its nw and envs-per-lane lines, its launcher.
-// The larger pieces of a step that the kernels have in common (row staging, the action, the record, the write-back, the return reduction) stay
-// written out in each kernel: as functions they change the generated code of the instantiations that call them (profiles/policy_refactor_isa.md).
+// The larger pieces of a step that the kernels have in common (row staging, the action, the record, the write-back, the return reduction) are not
+// here: as functions they change the generated code of the instantiations that call them (profiles/policy_refactor_isa.md).  As ONE template source
+// whose variant-only statements sit under `if constexpr` they do not (profiles/policy_one_source_isa.md) -- that is how the three lean kernels
+// (cl_policy.h) and the central-agent pair (cl_policy_central.h) share them; in the kernels still written out they wait for the same treatment.
 #pragma once
 
 #ifdef __HIPCC__

@@ -4,7 +4,8 @@
 //     h2_i = tanh(l2[s][b][H1][i] + sum_j l2[s][b][j][i] h1_j)                                        i < H2
 //     a    = clamp(mid + half tanh(out[s][b][H2] + sum_i out[s][b][i] h2_i) + sigma z, low, high)
 // Included by cl_policy_deep.hip (libcitylearn_amd_policy_deep.so, include/citylearn_amd_policy_deep.h) behind cl_kernels.hip's helpers and
-// cl_policy_common.h.  The body is cl_rollout_policy_kernel's written out again (profiles/policy_refactor_isa.md says why): the prologue, the
+// cl_policy_common.h.  The body is cl_rollout_policy_kernel's written out again (as functions the shared pieces change the generated code,
+// profiles/policy_refactor_isa.md; one template source with cl_policy.h, profiles/policy_one_source_isa.md, has not been tried): the prologue, the
 // Philox cache, the lean unit, the record, the write-back, district_reduce and the return rows are its statements; MARL's exchange is left out
 // (the host refuses CLR_MARL: no barrier in this K loop), the row staging and the policy block are this file's.
 //

@@ -7,7 +7,8 @@
 // Included by cl_policy_full_central.hip only (libcitylearn_amd_policy_full_central.so, include/citylearn_amd_policy_full_central.h) behind
 // cl_kernels.hip's helpers and cl_policy_common.h.  The geometry is the thermal policy kernel's: ONE building per wave (nw == n_bldg <= 16), lane =
 // env, one env per lane only; the prologue, the packed unit with its outage branch and per-step parameter re-read, the record, the write-back,
-// district_reduce and the return rows are cl_rollout_full_policy_kernel's statements written out again (profiles/policy_refactor_isa.md says why),
+// district_reduce and the return rows are cl_rollout_full_policy_kernel's statements written out again (as functions they change the generated code,
+// profiles/policy_refactor_isa.md; one template source with cl_policy_full.h, profiles/policy_one_source_isa.md, is not attempted),
 // the two-phase hidden layer is cl_rollout_policy_central_kernel's (cl_policy_central.h) over five terms instead of two:
 //   publish   (prologue, then the end of every action phase) every wave writes its building's soc, cs, hs, ds and previous net into
 //             X[5][n_bldg][64]; 0 where the building has no such storage -- the values the record's planes CLPF_T_SOC + d / CLPF_T_NET hold.

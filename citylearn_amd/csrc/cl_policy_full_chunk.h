@@ -15,7 +15,8 @@
 //  * no barrier inside the K loop, hence no MARL instantiation (a chunked launch cannot couple the buildings inside a step anyway): the
 //    wave-uniform table reads stay scalar (cl_rollout_full_kernel's note on its MARL instantiations).
 // The policy block is written out again (as cl_policy_full_kpi.h does): shared functions changed the parents' generated code before
-// (profiles/policy_refactor_isa.md).  LDS per workgroup: cl_policy_full.h's formula, [nw][NQ][tile] reduction rows (the return rows alias them) +
+// (profiles/policy_refactor_isa.md), and one template source for the thermal kernels (profiles/policy_one_source_isa.md has the rule) is not
+// attempted.  LDS per workgroup: cl_policy_full.h's formula, [nw][NQ][tile] reduction rows (the return rows alias them) +
 // nw x CLPF_ROW floats -- 26 KiB at the default eight waves and two envs per lane, 52 KiB at sixteen.
 #pragma once
 #include "cl_policy_full.h"

@@ -5,7 +5,8 @@
 //     act_a  = clamp(mid_a + half_a tanh(out[s][b][a][H2] + sum_i out[s][b][a][i] h2_i) + sigma_a z_a, low_a, high_a)      a over the heads (es, cs, hs, ds)
 // Included by cl_policy_full_deep.hip only (libcitylearn_amd_policy_full_deep.so, include/citylearn_amd_policy_full_deep.h) behind cl_kernels.hip's
 // helpers and cl_policy_common.h.  One env per lane, one building per wave (host: nw == n_bldg <= 16).  Everything outside the policy block is
-// cl_rollout_full_policy_kernel<1, PREC, MARL>'s statements written out again (profiles/policy_refactor_isa.md says why): the prologue, the
+// cl_rollout_full_policy_kernel<1, PREC, MARL>'s statements written out again (as functions they change the generated code,
+// profiles/policy_refactor_isa.md; one template source with cl_policy_full.h, profiles/policy_one_source_isa.md, is not attempted): the prologue, the
 // packed unit with its outage branch, the record, MARL's exchange, the write-back, district_reduce and the return rows; the row staging and the
 // policy block are this file's.  The policy block runs BEFORE the unit step, so its registers are free again when unit_step starts.
 //

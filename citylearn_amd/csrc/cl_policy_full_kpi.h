@@ -5,7 +5,7 @@
 //
 // Nothing here is new arithmetic, and every accumulation keeps the order of the code tests/test_gpu_policy_full_kpi_rollout.py compares it with.
 //  * From cl_rollout_full_policy_kernel, written out again (the policy block as a shared device function is not tried here: the parent's five
-//    instantiations are pinned to their register counts, cl_policy_kpi.h's note): state load / store, the staged `dep` / `out` / bounds row, the
+//    instantiations are pinned to their register counts, cl_policy.h's clpk_pins): state load / store, the staged `dep` / `out` / bounds row, the
 //    hidden groups, the head loop, the per-step re-read of the parameter block, reward, record, district_reduce and the return rows.
 //  * From full_step_body<.., KPI>: the twelve CL_NKB sums per (env, building), its `kv[CLK_*] +=` statements in its order, on the values of
 //    clv::unit_step<F, OUT, DETAIL = true, PREC>.  They live in the wave's own LDS rows (the lane's own column: read - add - written per step, as

@@ -1,20 +1,18 @@
 // cl_policy_kpi.hip -- the translation unit of libcitylearn_amd_policy_kpi.so (include/citylearn_amd_policy_kpi.h): cl_kernels.hip reduced to the
-// helpers the fused rollout kernels share (CL_TU_NOSLP's cut, minus its launchers: CL_TU_POLICY), cl_policy.h for the staged-row layout
-// and the lean entry points' shared checks (its kernel template is never instantiated here), cl_policy_kpi.h's kernel, its launcher and the
-// `clpk_*` entry points.  Compiled with
-// -fno-slp-vectorize like the other rollout kernels (citylearn_amd/_lib.py): same arithmetic, same loss to packed fp32.
+// helpers the fused rollout kernels share (CL_TU_NOSLP's cut, minus its launchers: CL_TU_POLICY), cl_policy.h's closed-loop kernel at KPI = true
+// (reported as cl_rollout_policy_kpi_kernel<VEC, PREC>; its KPI = false variant is never instantiated here), its launcher and the `clpk_*` entry
+// points.  Compiled with -fno-slp-vectorize like the other rollout kernels (citylearn_amd/_lib.py): same arithmetic, same loss to packed fp32.
 #define CL_TU_NOSLP
 #define CL_TU_POLICY
 #include "cl_kernels.hip"
 #include "../../include/citylearn_amd_policy_kpi.h"
 #include "cl_policy.h"
-#include "cl_policy_kpi.h"
 
 namespace {
 
 // the launcher of this unit (the other libraries' launchers stay what they are); key = 10 * envs per lane + PREC
 int launch_policy(int vec, int prec, unsigned grid, unsigned block, size_t lds, hipStream_t s, const PolicyArgs& p) {
-#define CL_POL(V, P) CL_POLICY_LAUNCH(cl_rollout_policy_kpi_kernel<V, P>)
+#define CL_POL(V, P) CL_POLICY_LAUNCH(cl_rollout_policy_kernel<V, P, true, false>)
     switch (vec * 10 + prec) {
     case 10: CL_POL(1, 0); break;
     case 20: CL_POL(2, 0); break;

@@ -10,7 +10,7 @@ scores a population of controllers by return: one parameter set per block of ``a
     ret, traj = env.rollout_policy(policy, 24, seed=3, record=True)    # ONE launch; traj [24, CLPOL_NT, n_bldg, n_envs]
 
 To score the controllers with CityLearn's KPIs, build the env with ``kpi=True`` and ask for them in the same call: ONE launch of
-`cl_rollout_policy_kpi_kernel` (csrc/cl_policy_kpi.h, ``libcitylearn_amd_policy_kpi.so``, include/citylearn_amd_policy_kpi.h) keeps the streaming
+`cl_rollout_policy_kpi_kernel` (csrc/cl_policy.h at KPI = true, ``libcitylearn_amd_policy_kpi.so``, include/citylearn_amd_policy_kpi.h) keeps the streaming
 accumulators next to the policy, and `evaluate()` works afterwards as after any other rollout -- no second env, no trajectory through memory:
 
     kenv = VectorCityLearnEnv(schema, n_envs, observations='tensor', normalize_observations=True, kpi=True)
@@ -64,7 +64,7 @@ follows as before.  `evaluate()` then scores the 1024-building district's contro
     building_kpis, district_kpis = kenv.evaluate()
 
 A battery + PV district of MORE than 32 buildings -- the 1024-building tiling of the 2022 schema -- takes the `MLPPolicy` through a
-building-chunked launch as well: `cl_rollout_policy_chunk_kernel` (csrc/cl_policy_chunk.h, ``libcitylearn_amd_policy_chunk.so``,
+building-chunked launch as well: `cl_rollout_policy_chunk_kernel` (csrc/cl_policy.h at CHUNK = true, csrc/cl_policy_chunk.h, ``libcitylearn_amd_policy_chunk.so``,
 include/citylearn_amd_policy_chunk.h) with two buildings per wave and the blind chunked rollout's 32-building workgroups, balanced (33 -> 17 + 16,
 1024 -> 32 x 32), then one `cl_finish_kernel` launch.  `VectorCityLearnEnv.rollout_policy` routes there by itself (`_Kind.one_row_max`); on the
 engine it is ``rollout_policy(..., chunked=True)`` with `PolicyTables`, chunk size and waves from ``tuning=dict(b_chunk=..., nw=...)``.  Same
@@ -118,7 +118,7 @@ plane on a ``kpi=True`` env); more than 32 buildings and a thermal district are 
 A central actor with TWO hidden layers -- a SAC / PPO actor trained with ``central_agent=True`` -- is a `DeepCentralMLPPolicy`: ``h1 = tanh(W1 obs
 + b1)``, ``h2 = tanh(W2 h1 + b2)``, ``a_b = clamp(mid_b + half_b tanh(w3[b] . h2 + b3[b]) + sigma_b z, low_b, high_b)`` with H1, H2 in 4, 8, .. 64
 independently, same districts, reward kinds, record and noise stream as the `CentralMLPPolicy`: one launch of
-`cl_rollout_policy_central_deep_kernel` (csrc/cl_policy_central_deep.h, ``libcitylearn_amd_policy_central_deep.so``,
+`cl_rollout_policy_central_deep_kernel` (csrc/cl_policy_central.h at DEEP = true, ``libcitylearn_amd_policy_central_deep.so``,
 include/citylearn_amd_policy_central_deep.h), whose step has a third phase and barrier for layer 2 -- one H1 x H2 product per ENV, in exact fp32:
 
     dcentral = DeepCentralMLPPolicy(w1, b1, w2, b2, w3, b3, sigma=0.1)    # w2 [n_sets, H2, H1], b2 [n_sets, H2], w3 [n_sets, n_bldg, H2], b3 [n_sets, n_bldg]
@@ -191,7 +191,7 @@ CLPFD_MAX_HIDDEN, CLPFD_MATRIX_CORES = FULL_DEEP_CONSTANTS['CLPFD_MAX_HIDDEN'], 
 # a central agent (csrc/cl_policy_central.h, libcitylearn_amd_policy_central.so): the record and the noise stream are the lean kernel's
 CENTRAL_CONSTANTS = _header_constants(_lib.POLICY_CENTRAL.header, 'CLPCA_')
 CLPCA_MAX_HIDDEN, CLPCA_MAX_BLDG = CENTRAL_CONSTANTS['CLPCA_MAX_HIDDEN'], CENTRAL_CONSTANTS['CLPCA_MAX_BLDG']
-# ... with two hidden layers (csrc/cl_policy_central_deep.h, libcitylearn_amd_policy_central_deep.so)
+# ... with two hidden layers (csrc/cl_policy_central.h at DEEP = true, libcitylearn_amd_policy_central_deep.so)
 CENTRAL_DEEP_CONSTANTS = _header_constants(_lib.POLICY_CENTRAL_DEEP.header, 'CLPCD_')
 CLPCD_MAX_HIDDEN, CLPCD_MAX_BLDG = CENTRAL_DEEP_CONSTANTS['CLPCD_MAX_HIDDEN'], CENTRAL_DEEP_CONSTANTS['CLPCD_MAX_BLDG']
 # a central agent on a thermal district (csrc/cl_policy_full_central.h, libcitylearn_amd_policy_full_central.so): the record and the noise stream
@@ -1168,7 +1168,7 @@ class DeepCentralMLPPolicy:
 
     `obs`, the bounds, sigma, z, the noise stream and the env-dependent inputs (EVERY building's own ``electrical_storage_soc`` and
     ``net_electricity_consumption``) are `CentralMLPPolicy`'s.  Battery + PV districts of up to 32 buildings: one launch of
-    `cl_rollout_policy_central_deep_kernel` (csrc/cl_policy_central_deep.h, ``libcitylearn_amd_policy_central_deep.so``), layer 2 in exact fp32.
+    `cl_rollout_policy_central_deep_kernel` (csrc/cl_policy_central.h at DEEP = true, ``libcitylearn_amd_policy_central_deep.so``), layer 2 in exact fp32.
 
     ``w1 [n_sets, H1, n_cols]``, ``b1 [n_sets, H1]``, ``w2 [n_sets, H2, H1]``, ``b2 [n_sets, H2]``, ``w3 [n_sets, n_bldg, H2]``,
     ``b3 [n_sets, n_bldg]`` (anything array-like; kept in float64); a leading dimension of 1 broadcasts.  ``H1``, ``H2``: 4, 8, .. 64, independent of

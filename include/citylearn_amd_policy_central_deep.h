@@ -1,7 +1,7 @@
 /* citylearn_amd_policy_central_deep.h -- C interface of libcitylearn_amd_policy_central_deep.so: the fused K-step rollout of a battery + PV district
  * driven by a CLOSED-LOOP CENTRAL-AGENT policy with TWO hidden layers -- ONE tanh MLP over the district's observation vector that returns every
  * building's storage action, the shape of a SAC / PPO actor trained with central_agent=True -- evaluated inside the rollout kernel
- * (csrc/cl_policy_central_deep.h).
+ * (csrc/cl_policy_central.h at DEEP = true).
  *
  * A library of its own beside libcitylearn_amd.so and the other policy libraries (whose symbol lists, structs and flag sets it leaves untouched);
  * it shares cl_dims / cl_tuning, the plane layouts and the error codes with citylearn_amd.h, and the record's planes (CLPOL_NT, CLPOL_T_*) and
@@ -61,7 +61,7 @@ const char* clpcd_last_error(void);
  * included: the kernel's third barrier of a step carries it), env_row0 / env_offset as in cl_rollout_f32; no CLD_F64_MAPS, CLD_KPI,
  * CLD_WRITE_DETAIL, no env_pitch.  One env per lane (cl_tuning.vec: 0 or 1); cl_tuning.nw overrides the waves (two buildings per wave:
  * (n_bldg + 1) / 2 <= nw <= min(n_bldg, 16)) and changes no action, net or soc: every sum that feeds them has a fixed order.
- * Dynamic LDS per workgroup, in floats (csrc/cl_policy_central_deep.h; the launch opts in above 64 KiB, a CU's 160 KiB are never reached):
+ * Dynamic LDS per workgroup, in floats (csrc/cl_policy_central.h; the launch opts in above 64 KiB, a CU's 160 KiB are never reached):
  *     nw x 4 x 64  +  2 x n_bldg x 64  +  n_hidden x 64  +  n_hidden2 x 64  +  2 x n_hidden x n_bldg  +  (n_hidden + 1) x n_hidden2  +  nw x 2 x (CLPCD_MAX_HIDDEN + 8)
  *     reduction rows  X (soc, net)       Hh1                Hh2                 staged dep                staged l2                      staged out rows
  * Buffers, ret_env and traj ([k_steps][CLPOL_NT][n_bldg][n_env]) as clpol_rollout_mlp_f32.  Returns CL_OK or a CL_E* code (message:

@@ -1,5 +1,5 @@
 /* citylearn_amd_policy_kpi.h -- C interface of libcitylearn_amd_policy_kpi.so: the closed-loop policy rollout of citylearn_amd_policy.h that also
- * keeps the streaming KPI accumulators of a CLD_KPI district inside the launch (csrc/cl_policy_kpi.h).
+ * keeps the streaming KPI accumulators of a CLD_KPI district inside the launch (csrc/cl_policy.h at KPI = true).
  *
  * A library of its own beside libcitylearn_amd.so and libcitylearn_amd_policy.so, whose symbol lists, structs and kernels it leaves untouched; it
  * shares cl_dims / cl_tuning, the plane layouts and the error codes with citylearn_amd.h and `clpol_mlp`, the trajectory planes and

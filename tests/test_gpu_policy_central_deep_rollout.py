@@ -1,6 +1,6 @@
 """The closed-loop rollout under a central-agent policy with TWO hidden layers on the GPU (`StepEngine.rollout_policy` /
 `VectorCityLearnEnv.rollout_policy` with a `policy.DeepCentralMLPPolicy`: one launch of `cl_rollout_policy_central_deep_kernel`,
-csrc/cl_policy_central_deep.h), in tests/test_gpu_policy_central_rollout.py's six groups: (1) its actions teacher-forced against the float64 MLP
+csrc/cl_policy_central.h at DEEP = true), in tests/test_gpu_policy_central_rollout.py's six groups: (1) its actions teacher-forced against the float64 MLP
 over the recorded planes of ALL buildings, (2) its record replayed through `step()`, MARL included, (3) free-running against the CPU oracle,
 (4) launch splitting, checkpoints, episode windows x parameter sets x env offsets and the wave count bit for bit, (5) the env-level call against
 `capture_rollout` with the same MLP in torch, (6) the refusals.  Weights: tests/policy_central_deep_util.py (their scale fixed by

@@ -1,5 +1,5 @@
 """The closed-loop policy rollout that keeps the streaming KPIs (`StepEngine.rollout_policy(kpi=True)` / `VectorCityLearnEnv.rollout_policy(kpi=True)`:
-one launch of `cl_rollout_policy_kpi_kernel`, csrc/cl_policy_kpi.h, ``libcitylearn_amd_policy_kpi.so``).
+one launch of `cl_rollout_policy_kpi_kernel`, csrc/cl_policy.h at KPI = true, ``libcitylearn_amd_policy_kpi.so``).
 
 Nothing here compares the kernel with itself, except where two launches of it must agree (split launches, env blocks).  The references are the
 ones the two kernels it is made of are held to: the SINGLE-STEP path with `kpi=True` fed the recorded actions (tests/test_gpu_rollout_kpi.py's

@@ -1,5 +1,5 @@
 """The closed-loop rollout under a CENTRAL-AGENT policy with TWO hidden layers (`clpcd_rollout_mlp_f32`, kernel
-`cl_rollout_policy_central_deep_kernel` in csrc/cl_policy_central_deep.h, library ``libcitylearn_amd_policy_central_deep.so``) as far as it can be
+`cl_rollout_policy_central_kernel<PREC, DEEP = true>` of csrc/cl_policy_central.h, library ``libcitylearn_amd_policy_central_deep.so``) as far as it can be
 checked without a GPU: the library's symbol list and struct, every refusal of the host entry (before any HIP call), the LDS formula, the packer
 against the unsplit MLP in float64, the conditioning of the closed loop the GPU tests run (tests/test_gpu_policy_central_deep_rollout.py), and
 the resource figures of every instantiation."""
@@ -35,10 +35,10 @@ def test_library_exports_exactly_the_header(entry):
     assert policy.CENTRAL_DEEP_CONSTANTS == {'CLPCD_ABI_VERSION': 1, 'CLPCD_MAX_HIDDEN': 64, 'CLPCD_MAX_BLDG': 32}
     (src, flags), = EXT.sources
     assert flags == ['-fno-slp-vectorize'] and src.name == 'cl_policy_central_deep.hip'
-    assert (_lib.CSRC / 'cl_policy_central_deep.h').exists() and EXT.path.name == 'libcitylearn_amd_policy_central_deep.so'
-    # the kernel header is this unit's alone, and the unit does not pull in the one-hidden-layer central header
-    users = [p.name for p in _lib.CSRC.glob('*.hip') if 'cl_policy_central_deep.h' in p.read_text()]
-    assert users == ['cl_policy_central_deep.hip'] and '#include "cl_policy_central.h"' not in src.read_text()
+    assert EXT.path.name == 'libcitylearn_amd_policy_central_deep.so'
+    # the kernel source is the central pair's one header, which the two central units include and nobody else
+    users = sorted(p.name for p in _lib.CSRC.glob('*.hip') if '#include "cl_policy_central.h"' in p.read_text())
+    assert users == ['cl_policy_central.hip', 'cl_policy_central_deep.hip'] and not (_lib.CSRC / 'cl_policy_central_deep.h').exists()
 
 
 def test_struct_is_the_deep_policy_struct():
@@ -168,10 +168,12 @@ def test_lds_formula():
                         == _lib.policy_central_lds_bytes(nw, n_bldg, h1) + 4 * (h2 * 64 + (h1 + 1) * h2))
     assert _lib.policy_central_deep_lds_bytes(16, 32, 64, 64) == 107776 > 64 * 1024 and 107776 < _lib.LDS_PER_CU == 163840
     assert _lib.policy_central_deep_lds_bytes(9, 17, 32, 16) == 4 * (9 * 256 + 34 * 64 + 32 * 64 + 16 * 64 + 64 * 17 + 33 * 16 + 18 * 72) == 41856
-    head, unit = (_lib.CSRC / 'cl_policy_central_deep.h').read_text(), (_lib.CSRC / 'cl_policy_central_deep.hip').read_text()
+    head, unit = (_lib.CSRC / 'cl_policy_central.h').read_text(), (_lib.CSRC / 'cl_policy_central_deep.hip').read_text()
     assert ('return (size_t)nw * NQ * 64 + (size_t)2 * n_bldg * 64 + (size_t)h1 * 64 + (size_t)h2 * 64 + (size_t)2 * h1 * n_bldg + (size_t)(h1 + 1) * h2\n'
-            '           + (size_t)nw * 2 * CLPCD_ROW;' in head and 'CLPCD_ROW = CLPCD_MAX_HIDDEN + 8;' in head and abi.CL_NQ == 4)
-    assert 'check_policy_lds(lds, "deep central policy", nw, 1)' in unit and 'CL_POLICY_LAUNCH(cl_rollout_policy_central_deep_kernel<0>)' in unit
+            '           + (size_t)nw * 2 * CLPC_ROW;' in head and 'CLPC_ROW = CLPC_MAX_HIDDEN + 8;' in head and 'CLPC_MAX_HIDDEN = 64;' in head
+            and abi.CL_NQ == 4)
+    assert 'static_assert(CLPCD_MAX_HIDDEN == CLPC_MAX_HIDDEN' in unit and policy.CLPCD_MAX_HIDDEN == 64
+    assert 'check_policy_lds(lds, "deep central policy", nw, 1)' in unit and 'CL_POLICY_LAUNCH(cl_rollout_policy_central_kernel<0, true>)' in unit
     shared = (_lib.CSRC / 'cl_policy_common.h').read_text()
     assert 'if (lds > 64 * 1024) if (hipError_t e = ensure_dynamic_lds(' in shared and 'if (lds > CL_LDS_PER_CU) return fail(' in shared
 
@@ -383,14 +385,13 @@ def central_deep_unit(tmp_path_factory):
 
 
 def test_central_deep_kernel_resources(central_deep_unit):
-    """Every instantiation of cl_rollout_policy_central_deep_kernel<PREC> -- the fp32 map and the float64 chain: no scratch memory and at most
-    128 registers, a 1024-thread workgroup's limit.  The unit holds its own kernel only."""
+    """Every instantiation of cl_rollout_policy_central_kernel<PREC, DEEP = true> -- the fp32 map and the float64 chain: no scratch memory and
+    at most 128 registers, a 1024-thread workgroup's limit.  The unit holds its own kernel only: no DEEP = false instantiation of the template."""
     kernels, meta = central_deep_unit
-    names = [k for k in kernels if 'cl_rollout_policy_central_deep_kernel' in k]
-    by = {int(re.search(r'cl_rollout_policy_central_deep_kernelILi(\d)EE', k).group(1)): k for k in names}
+    names = [k for k in kernels if 'cl_rollout_policy_central_kernel' in k]
+    by = {int(re.search(r'cl_rollout_policy_central_kernelILi(\d)ELb1EE', k).group(1)): k for k in names}
     assert sorted(by) == [0, 2] and len(names) == 2
-    assert not [k for k in kernels if 'cl_rollout_kernel' in k or 'cl_rollout_policy_kernel' in k or 'cl_rollout_policy_central_kernel' in k
-                or 'cl_step' in k]
+    assert not [k for k in kernels if 'cl_rollout_kernel' in k or 'cl_rollout_policy_kernel' in k or 'cl_step' in k]
     for prec, k in by.items():
         assert meta[k]['private_seg_size'] == 0, k
         assert meta[k]['num_vgpr'] <= 128, (k, meta[k])

@@ -139,9 +139,10 @@ def test_lds_formula():
     assert _lib.policy_central_lds_bytes(16, 32, 64) == 74752 > 64 * 1024 and 74752 < _lib.LDS_PER_CU == 163840
     assert _lib.policy_central_lds_bytes(9, 17, 32) == 4 * (9 * 256 + 34 * 64 + 32 * 64 + 64 * 17 + 18 * 72) == 35648
     head, unit = (_lib.CSRC / 'cl_policy_central.h').read_text(), (_lib.CSRC / 'cl_policy_central.hip').read_text()
-    assert ('return (size_t)nw * NQ * 64 + (size_t)2 * n_bldg * 64 + (size_t)h * 64 + (size_t)2 * h * n_bldg + (size_t)nw * 2 * CLPCA_ROW;' in head
-            and 'CLPCA_ROW = CLPCA_MAX_HIDDEN + 8;' in head and abi.CL_NQ == 4)
-    assert 'check_policy_lds(lds, "central policy", nw, 1)' in unit and 'CL_POLICY_LAUNCH(cl_rollout_policy_central_kernel<0>)' in unit
+    assert ('return (size_t)nw * NQ * 64 + (size_t)2 * n_bldg * 64 + (size_t)h * 64 + (size_t)2 * h * n_bldg + (size_t)nw * 2 * CLPC_ROW;' in head
+            and 'CLPC_ROW = CLPC_MAX_HIDDEN + 8;' in head and 'CLPC_MAX_HIDDEN = 64;' in head and abi.CL_NQ == 4)
+    assert 'static_assert(CLPCA_MAX_HIDDEN == CLPC_MAX_HIDDEN' in unit and policy.CLPCA_MAX_HIDDEN == 64
+    assert 'check_policy_lds(lds, "central policy", nw, 1)' in unit and 'CL_POLICY_LAUNCH(cl_rollout_policy_central_kernel<0, false>)' in unit
     shared = (_lib.CSRC / 'cl_policy_common.h').read_text()
     assert 'if (lds > 64 * 1024) if (hipError_t e = ensure_dynamic_lds(' in shared and 'if (lds > CL_LDS_PER_CU) return fail(' in shared
 
@@ -337,11 +338,11 @@ def central_unit(tmp_path_factory):
 
 
 def test_central_kernel_resources(central_unit):
-    """Every instantiation of cl_rollout_policy_central_kernel<PREC> -- the fp32 map and the float64 chain: no scratch memory and at most 128
-    registers, a 1024-thread workgroup's limit.  The unit holds its own kernel only."""
+    """Every instantiation of cl_rollout_policy_central_kernel<PREC, DEEP = false> -- the fp32 map and the float64 chain: no scratch memory and at
+    most 128 registers, a 1024-thread workgroup's limit.  The unit holds its own kernel only: no DEEP = true instantiation of the template."""
     kernels, meta = central_unit
     names = [k for k in kernels if 'cl_rollout_policy_central_kernel' in k]
-    by = {int(re.search(r'cl_rollout_policy_central_kernelILi(\d)EE', k).group(1)): k for k in names}
+    by = {int(re.search(r'cl_rollout_policy_central_kernelILi(\d)ELb0EE', k).group(1)): k for k in names}
     assert sorted(by) == [0, 2] and len(names) == 2
     assert not [k for k in kernels if 'cl_rollout_kernel' in k or 'cl_rollout_policy_kernel' in k or 'cl_step' in k]
     for prec, k in by.items():

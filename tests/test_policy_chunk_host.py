@@ -173,17 +173,17 @@ def _blocks(ins):
 
 
 def test_kernel_isa(tmp_path_factory):
-    """Exactly the four instantiations of cl_rollout_policy_chunk_kernel<VEC, PREC> and no instantiation of the one-row or the blind kernel in
-    this unit; one cl_finish_kernel; at most 128 VGPRs (a 1024-thread workgroup's cap), no scratch memory, no static LDS in the rollout kernel.
+    """Exactly the four instantiations of cl_rollout_policy_kernel<VEC, PREC, KPI = false, CHUNK = true> (csrc/cl_policy.h) and no CHUNK = false
+    instantiation of it -- the one-row kernel -- or of the blind kernel in this unit; one cl_finish_kernel; at most 128 VGPRs (a 1024-thread workgroup's cap), no scratch memory, no static LDS in the rollout kernel.
     The policy tables are not fetched per lane inside the K loop: the two hidden-layer loops (one per seat, not unrolled: blocks that branch back
     to their own label) each hold one s_load_dwordx4 of `pre` and three broadcast ds_read_b128 -- six in the kernel -- and no barrier sits between
     them: the K loop holds none.  The vector loads that remain: per seat the three state planes, the previous net and the three staging reads."""
     (src, flags), = _lib.POLICY_CHUNK_SOURCES
     kernels, meta = _asm(src, flags, tmp_path_factory)
-    names = [k for k in kernels if 'cl_rollout_policy_chunk_kernel' in k]
-    by = {tuple(int(x) for x in re.search(r'cl_rollout_policy_chunk_kernelILi(\d)ELi(\d)EE', k).groups()): k for k in names}
+    names = [k for k in kernels if 'cl_rollout_policy_kernel' in k]
+    by = {tuple(int(x) for x in re.search(r'cl_rollout_policy_kernelILi(\d)ELi(\d)ELb0ELb1EE', k).groups()): k for k in names}
     assert sorted(by) == [(1, 0), (1, 2), (2, 0), (2, 2)] and len(names) == 4
-    assert not [k for k in kernels if 'cl_rollout_policy_kernel' in k or 'cl_rollout_kernel' in k or 'cl_rollout_kpi_kernel' in k or 'cl_step' in k]
+    assert not [k for k in kernels if 'cl_rollout_kernel' in k or 'cl_rollout_kpi_kernel' in k or 'cl_step' in k]
     assert len([k for k in kernels if 'cl_finish_kernel' in k]) == 1
     for (vec, prec), k in by.items():
         ins = kernels[k]

@@ -131,7 +131,7 @@ def policy_unit(tmp_path_factory):
 
 
 def test_policy_kernel_isa(policy_unit):
-    """Every instantiation of cl_rollout_policy_kernel<VEC, PREC>: no scratch, no buffer instructions, no packed fp32, at most 128 registers (a
+    """Every instantiation of cl_rollout_policy_kernel<VEC, PREC, KPI = false, CHUNK = false>: no scratch, no buffer instructions, no packed fp32, at most 128 registers (a
     1024-thread workgroup's cap), the float64 chain only under PREC = 2, the activation as v_exp_f32 / v_rcp_f32 -- and the policy tables not
     fetched per lane: inside the K loop `pre` comes through s_load_dwordx4 and `dep` / `out` through broadcast ds_read_b128 (three per building
     and group of four hidden units: six in the code, the loop is not unrolled).  The vector loads that remain, pinned as generated -- 17 in
@@ -144,8 +144,9 @@ def test_policy_kernel_isa(policy_unit):
     add to this count."""
     kernels, meta = policy_unit
     names = [k for k in kernels if 'cl_rollout_policy_kernel' in k]
-    by = {tuple(int(x) for x in re.search(r'cl_rollout_policy_kernelILi(\d)ELi(\d)EE', k).groups()): k for k in names}
+    by = {tuple(int(x) for x in re.search(r'cl_rollout_policy_kernelILi(\d)ELi(\d)ELb0ELb0EE', k).groups()): k for k in names}
     assert sorted(by) == [(1, 0), (1, 2), (2, 0), (2, 2)] and len(names) == 4
+    assert not [k for k in kernels if re.search(r'cl_rollout_policy_kernelILi\dELi\dELb\dELb\dEE', k) and 'ELb0ELb0EE' not in k]     # no KPI / CHUNK = true one here
     assert not [k for k in kernels if 'cl_rollout_kernel' in k or 'cl_rollout_kpi_kernel' in k or 'cl_step' in k]      # the unit holds its own kernel only
     for (vec, prec), k in by.items():
         ins = kernels[k]

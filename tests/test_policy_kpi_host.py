@@ -1,5 +1,6 @@
-"""The closed-loop policy rollout that keeps the streaming KPIs (`clpk_rollout_mlp_kpi_f32`, kernel `cl_rollout_policy_kpi_kernel` in
-csrc/cl_policy_kpi.h, library ``libcitylearn_amd_policy_kpi.so``) as far as it can be checked without a GPU: the three libraries' symbol lists, the
+"""The closed-loop policy rollout that keeps the streaming KPIs (`clpk_rollout_mlp_kpi_f32`, kernel `cl_rollout_policy_kernel<VEC, PREC, KPI = true, CHUNK = false>`
+of csrc/cl_policy.h, reported as `cl_rollout_policy_kpi_kernel<VEC, PREC>`; library ``libcitylearn_amd_policy_kpi.so``) as far as it can be
+checked without a GPU: the three libraries' symbol lists, the
 argument validation (before any HIP call), the generated gfx950 code of every instantiation the host can select, and the LDS formula."""
 import ctypes
 import re
@@ -111,17 +112,17 @@ def test_policy_kpi_kernel_isa(unit):
     (three per building and group of four hidden units, the loop not unrolled: six; three more behind the loop, where the head workgroup's
     last thread reads the baseline series' twelve contiguous accumulators back from LDS: nine).  The unit holds no other rollout or step
     kernel: beside the four, only cl_flex_reset_kernel, which cl_kernels.hip's helper cut carries into every unit that includes it (the policy
-    unit too)."""
+    unit too) -- and no other instantiation of its own kernel template (KPI = false, or CHUNK = true)."""
     kernels, meta = unit
     launcher = (_lib.CSRC / 'cl_policy_kpi.hip').read_text()
     selectable = sorted((int(v), int(p)) for v, p in re.findall(r'case \d+: CL_POL\((\d), (\d)\); break;', launcher))
     assert selectable == [(1, 0), (1, 2), (2, 0), (2, 2)]
     names = [k for k in meta if 'private_seg_size' in meta[k]]
-    mine = [k for k in names if 'cl_rollout_policy_kpi_kernel' in k]
-    by = {tuple(int(x) for x in re.search(r'cl_rollout_policy_kpi_kernelILi(\d)ELi(\d)EE', k).groups()): k for k in mine}
+    mine = [k for k in names if 'cl_rollout_policy_kernel' in k]
+    by = {tuple(int(x) for x in re.search(r'cl_rollout_policy_kernelILi(\d)ELi(\d)ELb1ELb0EE', k).groups()): k for k in mine}
     assert sorted(by) == selectable and len(mine) == 4
     assert [k for k in names if k not in mine and 'cl_flex_reset_kernel' not in k] == []
-    assert not [k for k in kernels if re.search(r'cl_rollout_kernel|cl_rollout_kpi_kernel|cl_rollout_policy_kernel|cl_step', k)]
+    assert not [k for k in kernels if re.search(r'cl_rollout_kernel|cl_rollout_kpi_kernel|cl_rollout_policy_kernelILi\dELi\dELb(0ELb\d|1ELb1)EE|cl_step', k)]
     for (vec, prec), k in by.items():
         ins = kernels[k]
         print(f'cl_rollout_policy_kpi_kernel<{vec}, {prec}>: {meta[k]["num_vgpr"]} VGPRs, {meta[k]["private_seg_size"]} bytes of scratch')
@@ -137,12 +138,12 @@ def test_policy_kpi_kernel_isa(unit):
 # ---- 4. the LDS formula ---------------------------------------------------------------------------------------------------------------
 def _header_lds_floats(nw, tile):
     """`rollout_policy_kpi_lds_floats` / `rollout_kpi_lds_floats` / CLPOL_ROW evaluated from the headers' own text."""
-    rollout, pol, polk = ((_lib.CSRC / n).read_text() for n in ('cl_rollout.h', 'cl_policy.h', 'cl_policy_kpi.h'))
+    rollout, pol = ((_lib.CSRC / n).read_text() for n in ('cl_rollout.h', 'cl_policy.h'))
     const = {k: int(v) for src in (rollout, pol) for k, v in re.findall(r'constexpr int (\w+) = (\d+);', src)}
     const['CLPOL_ROW'] = eval(re.search(r'constexpr int CLPOL_ROW = ([^;]+);', pol).group(1), {}, const)
     const['CLKE_PER_COND'] = abi.CLKE_PER_COND
     kpi = re.search(r'constexpr size_t rollout_kpi_lds_floats\(int nw, int tile\) \{\s*return ([^;]+);', rollout).group(1)
-    mine = re.search(r'constexpr size_t rollout_policy_kpi_lds_floats\(int nw, int tile\) \{ return ([^;]+); \}', polk).group(1)
+    mine = re.search(r'constexpr size_t rollout_policy_kpi_lds_floats\(int nw, int tile\) \{ return ([^;]+); \}', pol).group(1)
     strip = lambda e: e.replace('(size_t)', '')
     env = dict(const, nw=nw, tile=tile)
     env['rollout_kpi_lds_floats'] = lambda nw_, tile_: eval(strip(kpi), {}, dict(const, nw=nw_, tile=tile_))
@@ -162,4 +163,4 @@ def test_lds_formula():
     # the launcher opts in above 64 KiB and the entry point refuses above the CU's LDS: both through cl_policy_common.h's one copy
     shared, unit = (_lib.CSRC / 'cl_policy_common.h').read_text(), (_lib.CSRC / 'cl_policy_kpi.hip').read_text()
     assert 'if (lds > 64 * 1024) if (hipError_t e = ensure_dynamic_lds(' in shared and 'if (lds > CL_LDS_PER_CU) return fail(' in shared
-    assert 'CL_POLICY_LAUNCH(cl_rollout_policy_kpi_kernel<V, P>)' in unit and 'check_policy_lds(lds, "policy KPI", nw, vec)' in unit
+    assert 'CL_POLICY_LAUNCH(cl_rollout_policy_kernel<V, P, true, false>)' in unit and 'check_policy_lds(lds, "policy KPI", nw, vec)' in unit

@@ -363,13 +363,13 @@ def policy_full_lds_bytes(nw: int, vec: int) -> int:
 
 def policy_full_chunk_lds_bytes(nw: int, vec: int) -> int:
     """Dynamic LDS of one `cl_rollout_full_policy_chunk_kernel` workgroup of ``nw`` waves (= buildings of a chunk) at ``vec`` envs per lane:
-    csrc/cl_policy_full_chunk.h's `rollout_full_policy_chunk_lds_floats`, which is `policy_full_lds_bytes`'s formula (the chunk's reduction rows
+    csrc/cl_policy_full.h's `rollout_full_policy_chunk_lds_floats`, which is `policy_full_lds_bytes`'s formula (the chunk's reduction rows
     [nw][4][tile], then the staged policy rows) -- 26 624 bytes at the default eight waves and two envs per lane."""
     return 4 * (nw * 4 * 64 * vec + nw * ((5 + 4) * 32 + 4 * 8))
 
 
 def policy_full_kpi_lds_bytes(nw: int) -> int:
-    """Dynamic LDS of one `cl_rollout_full_policy_kpi_kernel` workgroup of ``nw`` waves (one env per lane): csrc/cl_policy_full_kpi.h's
+    """Dynamic LDS of one `cl_rollout_full_policy_kpi_kernel` workgroup of ``nw`` waves (one env per lane): csrc/cl_policy_full.h's
     `rollout_full_policy_kpi_lds_floats` -- the ring of both district series [8][2][nw][64], the two series [2][12][64], the staged policy rows
     [nw][(5 + 4) x 32 + 4 x 8], the units' twelve sums [nw][12][64] (tests/test_policy_full_kpi_host.py holds it against the header's formula)."""
     return 4 * (8 * 2 * nw * 64 + 2 * 12 * 64 + nw * ((5 + 4) * 32 + 4 * 8) + nw * 12 * 64)
@@ -377,7 +377,7 @@ def policy_full_kpi_lds_bytes(nw: int) -> int:
 
 def policy_full_chunk_kpi_lds_bytes(nw: int) -> int:
     """Dynamic LDS of one `cl_rollout_full_policy_chunk_kpi_kernel` workgroup of ``nw`` waves (= buildings of a chunk; one env per lane):
-    csrc/cl_policy_full_chunk_kpi.h's `rollout_full_policy_chunk_kpi_lds_floats` -- the ring of both district series [8][2][nw][64], then the staged
+    csrc/cl_policy_full.h's `rollout_full_policy_chunk_kpi_lds_floats` -- the ring of both district series [8][2][nw][64], then the staged
     policy rows [nw][(5 + 4) x 32 + 4 x 8] (the units' twelve sums live in registers) -- 43 008 bytes at the default eight waves, 86 016 at sixteen
     (tests/test_policy_full_chunk_kpi_host.py holds it against the header's formula)."""
     return 4 * (8 * 2 * nw * 64 + nw * ((5 + 4) * 32 + 4 * 8))

@@ -137,7 +137,7 @@ __global__ void __launch_bounds__(1024) cl_rollout_policy_kernel(const PolicyArg
         // as scratch memory that no instruction touches.  With b_hi as a value of its own <2, 0> reserved those 20 bytes; see also the pointers
         // behind the barrier and the arguments re-read behind the K loop.)
         own[m] = CHUNK ? (w + m * a.nw < a.b_chunk) && b < a.n_bldg : b < a.n_bldg;
-        // a seat without a building reads a valid parameter row, for its flag words only (CHUNK: ONE min, cl_policy_full_chunk.h's note)
+        // a seat without a building reads a valid parameter row, for its flag words only (CHUNK: ONE min, cl_policy_full.h's note)
         const int bc = CHUNK ? min(b, a.n_bldg - 1) : own[m] ? b : w;
         off[m] = (long long)bc * a.n_env + env0;
         cl::load_bp<false>(B[m], a.params + (long long)bc * CL_NP);

@@ -13,7 +13,7 @@
 //    so a chunk geometry does not change a draw;
 //  * a SEAT without a building (own[m] = b < min(n_bldg, (y + 1) b_chunk), wave-uniform) loads, stages, computes, records and stores nothing and
 //    adds zeros to the reductions.  A wave with NEITHER seat filled (the tail of the last chunk: 33 buildings cut 32 + 1 leave fifteen) reads the
-//    parameter row of one clamped, valid building -- ONE min, cl_policy_full_chunk.h's note -- and touches nothing else; it meets the barrier behind
+//    parameter row of one clamped, valid building -- ONE min, cl_policy_full.h's note -- and touches nothing else; it meets the barrier behind
 //    the row staging, district_reduce's and the return rows';
 //  * the last step's district sums go through district_reduce's n_chunks > 1 path, the return rows behind them (cl_rollout_kernel<CHUNK>'s place);
 //    ret_env is cl_finish_kernel's to add to;

@@ -15,7 +15,8 @@
 // The larger pieces of a step that the kernels have in common (row staging, the action, the record, the write-back, the return reduction) are not
 // here: as functions they change the generated code of the instantiations that call them (profiles/policy_refactor_isa.md).  As ONE template source
 // whose variant-only statements sit under `if constexpr` they do not (profiles/policy_one_source_isa.md) -- that is how the three lean kernels
-// (cl_policy.h) and the central-agent pair (cl_policy_central.h) share them; in the kernels still written out they wait for the same treatment.
+// (cl_policy.h), the central-agent pair (cl_policy_central.h) and the four per-building thermal kernels (cl_policy_full.h:
+// profiles/policy_full_one_source_isa.md) share them; in the kernels still written out they wait for the same treatment.
 #pragma once
 
 #ifdef __HIPCC__

@@ -1,6 +1,6 @@
 // cl_policy_full.hip -- the translation unit of libcitylearn_amd_policy_full.so (include/citylearn_amd_policy_full.h): cl_kernels.hip reduced to the
 // helpers the fused rollout kernels share and the packed thermal unit of cl_full.h (CL_TU_POLICY cuts the launchers and entry points,
-// CL_TU_POLICY_FULL the main library's small passes) + cl_policy_full.h's closed-loop kernel, its launcher and the `clpf_*` entry points.  NOT under
+// CL_TU_POLICY_FULL the main library's small passes) + cl_policy_full.h's closed-loop kernel template without its KPI and CHUNK switches, its launcher and the `clpf_*` entry points.  NOT under
 // CL_TU_NOSLP and compiled WITH SLP vectorisation, like the main translation unit: the packed unit wants v_pk_*_f32.
 #define CL_TU_POLICY
 #define CL_TU_POLICY_FULL
@@ -12,7 +12,7 @@ namespace {
 
 // the launcher of this unit; key = 100 * envs per lane + 10 * PREC + MARL
 int launch_policy_full(int vec, int prec, bool marl, unsigned grid, unsigned block, size_t lds, hipStream_t s, const PolicyArgs& p) {
-#define CL_POLF(V, P, M) CL_POLICY_LAUNCH(cl_rollout_full_policy_kernel<V, P, M>)
+#define CL_POLF(V, P, M) CL_POLICY_LAUNCH(cl_rollout_full_policy_kernel<V, P, M, false, false>)
     switch (vec * 100 + prec * 10 + (marl ? 1 : 0)) {
     case 200: CL_POLF(2, 0, false); break;
     case 100: CL_POLF(1, 0, false); break;

@@ -1,20 +1,20 @@
 // cl_policy_full_chunk.hip -- the translation unit of libcitylearn_amd_policy_full_chunk.so (include/citylearn_amd_policy_full_chunk.h):
 // cl_kernels.hip reduced as for cl_policy_full.hip (CL_TU_POLICY, CL_TU_POLICY_FULL) but WITH cl_finish_kernel (CL_TU_FINISH: the fold of the chunk
-// partial sums, which a building-chunked launch needs behind it), cl_policy_full.h for the staged-row layout (its kernel template is never
-// instantiated here), cl_policy_full_chunk.h's kernel, its launcher and the `clpfc_*` entry points.  Compiled WITH SLP vectorisation like
+// partial sums, which a building-chunked launch needs behind it), cl_policy_full.h's kernel template under its CHUNK switch, its
+// launcher and the `clpfc_*` entry points.  Compiled WITH SLP vectorisation like
 // cl_policy_full.hip.
 #define CL_TU_POLICY
 #define CL_TU_POLICY_FULL
 #define CL_TU_FINISH
 #include "cl_kernels.hip"
 #include "../../include/citylearn_amd_policy_full_chunk.h"
-#include "cl_policy_full_chunk.h"
+#include "cl_policy_full.h"
 
 namespace {
 
 // the launcher of this unit; key = 100 * envs per lane + 10 * PREC
 int launch_policy_full_chunk(int vec, int prec, dim3 grid, unsigned block, size_t lds, hipStream_t s, const PolicyArgs& p) {
-#define CL_POLFC(V, P) CL_POLICY_LAUNCH(cl_rollout_full_policy_chunk_kernel<V, P>)
+#define CL_POLFC(V, P) CL_POLICY_LAUNCH(cl_rollout_full_policy_kernel<V, P, false, false, true>)
     switch (vec * 100 + prec * 10) {
     case 200: CL_POLFC(2, 0); break;
     case 100: CL_POLFC(1, 0); break;

@@ -1,7 +1,7 @@
 // cl_policy_full_chunk_kpi.hip -- the translation unit of libcitylearn_amd_policy_full_chunk_kpi.so (include/citylearn_amd_policy_full_chunk_kpi.h):
 // cl_kernels.hip reduced as for cl_policy_full_chunk.hip (CL_TU_POLICY, CL_TU_POLICY_FULL, and CL_TU_FINISH for cl_finish_kernel) with the table
-// reads of cl_policy_full_kpi.hip (CL_TU_CONST_TABLES: the K loop holds barriers), cl_policy_full.h for the staged-row layout (its kernel template is
-// never instantiated here), cl_policy_full_chunk_kpi.h's two kernels, their launcher and the `clpfck_*` entry points.  Compiled WITH SLP
+// reads of cl_policy_full_kpi.hip (CL_TU_CONST_TABLES: the K loop holds barriers), cl_policy_full.h's kernel template under its KPI and CHUNK switches (one env
+// per lane), cl_policy_full_chunk_kpi.h's series kernel, their launcher and the `clpfck_*` entry points.  Compiled WITH SLP
 // vectorisation like the other thermal units.
 #define CL_TU_POLICY
 #define CL_TU_CONST_TABLES     /* cl_unit.h: the parameter / time-series reads as scalar loads inside a K loop that holds barriers */
@@ -14,10 +14,8 @@
 namespace {
 
 // the launcher of the rollout kernel; key = PREC
-int launch_policy_full_chunk_kpi(int prec, dim3 grid, unsigned block, size_t lds, hipStream_t s, const PolicyArgs& p, float* series_scratch) {
-#define CL_POLFCK(P) do { \
-        if (lds > 64 * 1024) if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(cl_rollout_full_policy_chunk_kpi_kernel<P>), lds); e != hipSuccess) return (int)e; \
-        hipLaunchKernelGGL((cl_rollout_full_policy_chunk_kpi_kernel<P>), grid, dim3(block), lds, s, p, series_scratch); } while (0)
+int launch_policy_full_chunk_kpi(int prec, dim3 grid, unsigned block, size_t lds, hipStream_t s, const FullPolicyChunkKpiArgs& p) {
+#define CL_POLFCK(P) CL_POLICY_LAUNCH(cl_rollout_full_policy_kernel<1, P, false, true, true>)
     switch (prec) {
     case 0: CL_POLFCK(0); break;
     case 2: CL_POLFCK(2); break;
@@ -91,7 +89,7 @@ int clpfck_rollout_mlp_kpi_f32(const cl_dims* dims, const uint32_t* params, cons
     name_reset(tun);
     name_add(tun, "cl_rollout_full_policy_chunk_kpi_kernel<%d>", prec);
     const dim3 grid((unsigned)((dims->n_env + 63) / 64), (unsigned)a.n_chunks);
-    const int rc = launch_policy_full_chunk_kpi(prec, grid, 64u * a.nw, lds, s, p, series_scratch);
+    const int rc = launch_policy_full_chunk_kpi(prec, grid, 64u * a.nw, lds, s, {p, series_scratch});
     if (rc) return hip_fail((hipError_t)rc, "cl_rollout_full_policy_chunk_kpi_kernel launch");
     if (k_steps > 0) {
         // the two district series of every env from the chunks' partial samples

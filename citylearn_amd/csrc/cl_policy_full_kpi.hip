@@ -1,6 +1,6 @@
 // cl_policy_full_kpi.hip -- the translation unit of libcitylearn_amd_policy_full_kpi.so (include/citylearn_amd_policy_full_kpi.h): cl_kernels.hip
-// reduced as for cl_policy_full.hip (CL_TU_POLICY, CL_TU_POLICY_FULL), cl_policy_full.h for the staged-row layout (its kernel template is never
-// instantiated here), cl_policy_full_kpi.h's kernel, its launcher and the `clpfk_*` entry points.  Compiled WITH SLP vectorisation like
+// reduced as for cl_policy_full.hip (CL_TU_POLICY, CL_TU_POLICY_FULL), cl_policy_full.h's kernel template under its KPI switch (one env per lane), its
+// launcher and the `clpfk_*` entry points.  Compiled WITH SLP vectorisation like
 // cl_policy_full.hip.
 #define CL_TU_POLICY
 #define CL_TU_CONST_TABLES     /* cl_unit.h: the parameter / time-series reads as scalar loads inside a K loop that holds barriers */
@@ -8,13 +8,12 @@
 #include "cl_kernels.hip"
 #include "../../include/citylearn_amd_policy_full_kpi.h"
 #include "cl_policy_full.h"
-#include "cl_policy_full_kpi.h"
 
 namespace {
 
 // the launcher of this unit; key = 10 * PREC + MARL
 int launch_policy_full_kpi(int prec, bool marl, unsigned grid, unsigned block, size_t lds, hipStream_t s, const PolicyArgs& p) {
-#define CL_POLFK(P, M) CL_POLICY_LAUNCH(cl_rollout_full_policy_kpi_kernel<P, M>)
+#define CL_POLFK(P, M) CL_POLICY_LAUNCH(cl_rollout_full_policy_kernel<1, P, M, true, false>)
     switch (prec * 10 + (marl ? 1 : 0)) {
     case 0: CL_POLFK(0, false); break;
     case 1: CL_POLFK(0, true); break;

@@ -34,7 +34,7 @@ of `cl_rollout_full_policy_kernel` (csrc/cl_policy_full.h, ``libcitylearn_amd_po
     ret, traj = env.rollout_policy(spolicy, 24, seed=3, record=True)   # traj [24, CLPF_NT, n_bldg, n_envs]: policy.CLPF_T_ACTION + head, ..
 
 On an env built with ``kpi=True`` the same call with ``kpi=True`` is ONE launch of `cl_rollout_full_policy_kpi_kernel`
-(csrc/cl_policy_full_kpi.h, ``libcitylearn_amd_policy_full_kpi.so``, include/citylearn_amd_policy_full_kpi.h) that also keeps every env's
+(csrc/cl_policy_full.h at KPI = true, ``libcitylearn_amd_policy_full_kpi.so``, include/citylearn_amd_policy_full_kpi.h) that also keeps every env's
 streaming KPI accumulators, so `evaluate()` scores the controllers afterwards -- no record, no second env:
 
     kenv = VectorCityLearnEnv(schema, n_envs, kpi=True)
@@ -46,7 +46,7 @@ outages goes through the same two kernels (their outage branch is tested on g202
 `outage_district`).
 
 A thermal district of MORE than 16 buildings -- BASELINE config 4's 1024 -- takes the same `StorageMLPPolicy` through a building-chunked launch:
-`cl_rollout_full_policy_chunk_kernel` (csrc/cl_policy_full_chunk.h, ``libcitylearn_amd_policy_full_chunk.so``,
+`cl_rollout_full_policy_chunk_kernel` (csrc/cl_policy_full.h at CHUNK = true, ``libcitylearn_amd_policy_full_chunk.so``,
 include/citylearn_amd_policy_full_chunk.h) with one building per wave and balanced chunks of at most eight buildings along the grid's second
 axis, then one `cl_finish_kernel` launch that adds the chunks' district sums and returns.  `VectorCityLearnEnv.rollout_policy` routes there by
 itself; on the engine it is ``rollout_policy(..., chunked=True)``, the chunk size from ``tuning=dict(b_chunk=...)``.  Same policy, same noise
@@ -55,7 +55,7 @@ stream (keyed by global env, column and step: chunking does not change a draw), 
 fixture.
 
 On an env built with ``kpi=True`` the chunked call takes ``kpi=True`` as well: `cl_rollout_full_policy_chunk_kpi_kernel`
-(csrc/cl_policy_full_chunk_kpi.h, ``libcitylearn_amd_policy_full_chunk_kpi.so``, include/citylearn_amd_policy_full_chunk_kpi.h) keeps every unit's
+(csrc/cl_policy_full.h at KPI = CHUNK = true and csrc/cl_policy_full_chunk_kpi.h, ``libcitylearn_amd_policy_full_chunk_kpi.so``, include/citylearn_amd_policy_full_chunk_kpi.h) keeps every unit's
 twelve sums inside the launch and hands the chunks' partial samples of the two district series to `cl_kpi_series_chunk_kernel`; `cl_finish_kernel`
 follows as before.  `evaluate()` then scores the 1024-building district's controllers without a record, a second env or a replay:
 

@@ -1,5 +1,5 @@
 /* citylearn_amd_policy_full_chunk.h -- C interface of libcitylearn_amd_policy_full_chunk.so: the closed-loop policy rollout of a THERMAL district
- * (citylearn_amd_policy_full.h) of MORE THAN 16 buildings, as a building-chunked launch (csrc/cl_policy_full_chunk.h) -- BASELINE config 4's
+ * (citylearn_amd_policy_full.h) of MORE THAN 16 buildings, as a building-chunked launch (csrc/cl_policy_full.h, its CHUNK switch) -- BASELINE config 4's
  * 1024-building district with a controller in the loop.
  *
  * A library of its own beside libcitylearn_amd.so and the four other policy libraries, whose symbol lists, structs and kernels it leaves

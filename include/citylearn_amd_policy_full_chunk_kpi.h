@@ -1,6 +1,6 @@
 /* citylearn_amd_policy_full_chunk_kpi.h -- C interface of libcitylearn_amd_policy_full_chunk_kpi.so: the building-chunked closed-loop policy rollout
  * of a THERMAL district of MORE THAN 16 buildings (citylearn_amd_policy_full_chunk.h) that also keeps the streaming KPI accumulators of a CLD_KPI
- * district inside the call (csrc/cl_policy_full_chunk_kpi.h) -- BASELINE config 4's 1024-building district scored by CityLearn's KPIs without a
+ * district inside the call (csrc/cl_policy_full.h, its KPI and CHUNK switches; csrc/cl_policy_full_chunk_kpi.h) -- BASELINE config 4's 1024-building district scored by CityLearn's KPIs without a
  * record, a second env or a replay.
  *
  * A library of its own beside libcitylearn_amd.so and the five other policy libraries, whose symbol lists, structs and kernels it leaves

@@ -1,6 +1,6 @@
 /* citylearn_amd_policy_full_kpi.h -- C interface of libcitylearn_amd_policy_full_kpi.so: the closed-loop policy rollout of a THERMAL district
  * (citylearn_amd_policy_full.h) that also keeps the streaming KPI accumulators of a CLD_KPI district inside the launch
- * (csrc/cl_policy_full_kpi.h).
+ * (csrc/cl_policy_full.h, its KPI switch).
  *
  * A library of its own beside libcitylearn_amd.so and the three other policy libraries, whose symbol lists, structs and kernels it leaves
  * untouched; it shares cl_dims / cl_tuning, the plane layouts and the error codes with citylearn_amd.h and `clpf_mlp`, the trajectory planes and

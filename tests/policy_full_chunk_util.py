@@ -1,5 +1,5 @@
 """Shared by tests/test_policy_full_chunk_host.py and tests/test_gpu_policy_full_chunk_rollout.py: the thermal districts of MORE than 16 buildings the
-building-chunked policy rollout is tested on (`clpfc_rollout_mlp_f32`, csrc/cl_policy_full_chunk.h).  Test policies and their weight scale:
+building-chunked policy rollout is tested on (`clpfc_rollout_mlp_f32`, csrc/cl_policy_full.h at CHUNK = true).  Test policies and their weight scale:
 tests/policy_full_util.py (`make_storage_policy`).
 
 The loop's conditioning on these districts (tests/test_policy_full_host.py::_conditioning: K = 48, E = 4, worst of soc / cs / ds / net in units of

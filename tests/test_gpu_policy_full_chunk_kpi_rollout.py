@@ -1,6 +1,6 @@
 """The building-chunked closed-loop policy rollout of thermal districts that keeps the streaming KPIs (`StepEngine.rollout_policy(chunked=True,
 kpi=True)` / `VectorCityLearnEnv(kpi=True).rollout_policy(kpi=True)` with a `StorageMLPPolicy` on a district of more than 16 buildings: per call
-`cl_rollout_full_policy_chunk_kpi_kernel`, `cl_kpi_series_chunk_kernel` and `cl_finish_kernel`, csrc/cl_policy_full_chunk_kpi.h,
+`cl_rollout_full_policy_chunk_kpi_kernel`, `cl_kpi_series_chunk_kernel` and `cl_finish_kernel`, csrc/cl_policy_full.h at KPI = CHUNK = true and csrc/cl_policy_full_chunk_kpi.h,
 ``libcitylearn_amd_policy_full_chunk_kpi.so``).
 
 The references: (1) the one-row KPI kernel on the sixteen-building district; (2, 3, 6, 8) the SINGLE-STEP path with `kpi=True` fed the recorded

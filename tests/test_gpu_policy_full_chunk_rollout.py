@@ -1,6 +1,6 @@
 """The building-chunked closed-loop policy rollout of thermal districts on the GPU (`StepEngine.rollout_policy(chunked=True)` /
 `VectorCityLearnEnv.rollout_policy` with a `StorageMLPPolicy` on a district of more than 16 buildings: one launch of
-`cl_rollout_full_policy_chunk_kernel`, csrc/cl_policy_full_chunk.h, and one of `cl_finish_kernel`): (1) against the one-row kernel on the
+`cl_rollout_full_policy_chunk_kernel`, csrc/cl_policy_full.h at CHUNK = true, and one of `cl_finish_kernel`): (1) against the one-row kernel on the
 sixteen-building district, (2) its trajectory replayed through `step()`, (3) its actions teacher-forced against the float64 MLP, (4) free-running
 against the CPU oracle, (5) launch splitting and checkpoints bit for bit, (6) episode windows x parameter sets x env offsets bit for bit, (7) the
 accumulated return, (8) the env-level call against `capture_rollout`, (9) refusals.  Helpers and tolerances: tests/test_gpu_policy_full_rollout.py

@@ -1,6 +1,6 @@
 """The closed-loop policy rollout of THERMAL districts that keeps the streaming KPIs (`StepEngine.rollout_policy(kpi=True)` /
 `VectorCityLearnEnv.rollout_policy(kpi=True)` with a `StorageMLPPolicy`: one launch of `cl_rollout_full_policy_kpi_kernel`,
-csrc/cl_policy_full_kpi.h, ``libcitylearn_amd_policy_full_kpi.so``).
+csrc/cl_policy_full.h at KPI = true, ``libcitylearn_amd_policy_full_kpi.so``).
 
 Nothing here compares the kernel with itself, except where two launches of it must agree (split launches, env blocks).  The references: the
 SINGLE-STEP path with `kpi=True` fed the recorded actions (`cl_step_full_kpi_kernel` in fp32; under the float64 chain the step with the

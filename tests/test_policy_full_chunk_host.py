@@ -1,5 +1,5 @@
-"""The building-chunked closed-loop policy rollout of thermal districts (`clpfc_rollout_mlp_f32`, kernel `cl_rollout_full_policy_chunk_kernel` in
-csrc/cl_policy_full_chunk.h, library ``libcitylearn_amd_policy_full_chunk.so``) as far as it can be checked without a GPU: the library's symbol list,
+"""The building-chunked closed-loop policy rollout of thermal districts (`clpfc_rollout_mlp_f32`, kernel `cl_rollout_full_policy_chunk_kernel`:
+csrc/cl_policy_full.h at CHUNK = true, library ``libcitylearn_amd_policy_full_chunk.so``) as far as it can be checked without a GPU: the library's symbol list,
 the argument validation (before any HIP call), registers / scratch / LDS of every instantiation, and the conditioning of the closed loop on the
 districts of more than 16 buildings the GPU tests run (tests/test_gpu_policy_full_chunk_rollout.py)."""
 import ctypes
@@ -133,15 +133,15 @@ def test_refusals_name_their_cause_before_any_hip_call(lib):
 
 # ---- 3. generated code ----------------------------------------------------------------------------------------------------------------
 def test_kernel_isa(tmp_path_factory):
-    """Exactly the three instantiations of cl_rollout_full_policy_chunk_kernel<VEC, PREC> (no MARL: no barrier inside the K loop) and no
-    instantiation of the one-row kernel in this unit; at most 128 VGPRs (a 1024-thread workgroup's cap), no scratch memory, no static LDS in the
+    """Exactly the three instantiations of cl_rollout_full_policy_kernel<VEC, PREC, false, KPI = false, CHUNK = true> (csrc/cl_policy_full.h: reported
+    as `cl_rollout_full_policy_chunk_kernel<VEC, PREC>`; no MARL: no barrier inside the K loop) and no instantiation of the one-row or a KPI variant in this unit; at most 128 VGPRs (a 1024-thread workgroup's cap), no scratch memory, no static LDS in the
     rollout kernel (it is all dynamic: `_lib.policy_full_chunk_lds_bytes`); cl_finish_kernel, the fold, is in the unit with its [16][64] floats."""
     (src,) = _lib.POLICY_FULL_CHUNK_SOURCES
     kernels, meta = _asm(src, [], tmp_path_factory)
-    names = [k for k in kernels if 'cl_rollout_full_policy_chunk_kernel' in k]
-    by = {tuple(int(x) for x in re.search(r'cl_rollout_full_policy_chunk_kernelILi(\d)ELi(\d)EE', k).groups()): k for k in names}
+    names = [k for k in kernels if 'cl_rollout_full_policy_kernel' in k]
+    by = {tuple(int(x) for x in re.search(r'cl_rollout_full_policy_kernelILi(\d)ELi(\d)ELb0ELb0ELb1EE', k).groups()): k for k in names}
     assert sorted(by) == [(1, 0), (1, 2), (2, 0)] and len(names) == 3
-    assert not [k for k in kernels if 'cl_rollout_full_policy_kernel' in k or 'cl_rollout_full_kernel' in k]
+    assert not [k for k in kernels if (re.search(r'cl_rollout_full_policy_kernelILi\dELi\dELb\dELb\dELb\dEE', k) and 'ELb0ELb0ELb1EE' not in k) or 'cl_rollout_full_kernel' in k]
     assert len([k for k in kernels if 'cl_finish_kernel' in k]) == 1
     for key, k in by.items():
         assert meta[k]['private_seg_size'] == 0, (k, meta[k])
@@ -151,7 +151,7 @@ def test_kernel_isa(tmp_path_factory):
     sizes = re.findall(r'\.group_segment_fixed_size:\s*(\d+)', text)
     assert sorted(set(sizes)) == ['0', '4096'] and sizes.count('4096') == 1, sizes          # (cl_finish_kernel's part[16][64])
     # the header's formula: rollout_full_policy_chunk_lds_floats(nw, tile) = nw NQ tile + nw CLPF_ROW, CLPF_ROW = 4 (5 + 4) (32 / 4) + 8 x 4
-    head = (_lib.CSRC / 'cl_policy_full_chunk.h').read_text()
+    head = (_lib.CSRC / 'cl_policy_full.h').read_text()
     assert re.search(r'rollout_full_policy_chunk_lds_floats\(int nw, int tile\) \{ return \(size_t\)nw \* NQ \* tile \+ \(size_t\)nw \* CLPF_ROW; \}', head)
     row = 4 * (policy.CLPF_ND + policy.CLPF_NA) * (policy.CLPF_MAX_HIDDEN // 4) + 8 * policy.CLPF_NA
     for nw in (1, 5, 6, 7, 8, 16):

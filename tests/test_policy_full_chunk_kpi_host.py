@@ -1,5 +1,5 @@
 """The building-chunked closed-loop policy rollout of thermal districts that keeps the streaming KPIs (`clpfck_rollout_mlp_kpi_f32`, kernels
-`cl_rollout_full_policy_chunk_kpi_kernel` and `cl_kpi_series_chunk_kernel` in csrc/cl_policy_full_chunk_kpi.h, library
+`cl_rollout_full_policy_chunk_kpi_kernel`: csrc/cl_policy_full.h at KPI = CHUNK = true, and `cl_kpi_series_chunk_kernel` in csrc/cl_policy_full_chunk_kpi.h, library
 ``libcitylearn_amd_policy_full_chunk_kpi.so``) as far as it can be checked without a GPU: the library's symbol list, the argument validation (before
 any HIP call), the scratch size, registers / scratch memory / LDS of both instantiations.  The conditioning of the closed loop on the districts the
 GPU tests run (tests/test_gpu_policy_full_chunk_kpi_rollout.py, H = 16) is held by tests/test_policy_full_chunk_host.py."""
@@ -159,16 +159,16 @@ def test_series_scratch_floats(lib):
 
 # ---- 3. generated code ----------------------------------------------------------------------------------------------------------------
 def test_kernel_isa(tmp_path_factory):
-    """Exactly the two instantiations of cl_rollout_full_policy_chunk_kpi_kernel<PREC>, one cl_kpi_series_chunk_kernel and one cl_finish_kernel, and
-    no instantiation of the blind chunk kernel or the one-row kernels in this unit; the rollout kernel at most 128 VGPRs (a 1024-thread
+    """Exactly the two instantiations of cl_rollout_full_policy_kernel<1, PREC, false, KPI = true, CHUNK = true> (csrc/cl_policy_full.h: reported as
+    `cl_rollout_full_policy_chunk_kpi_kernel<PREC>`), one cl_kpi_series_chunk_kernel and one cl_finish_kernel, and no instantiation of the blind chunk
+    kernel, the chunked kernel without KPIs or the one-row kernels in this unit; the rollout kernel at most 128 VGPRs (a 1024-thread
     workgroup's cap), no scratch memory, no static LDS (it is all dynamic: `_lib.policy_full_chunk_kpi_lds_bytes`)."""
     (src,) = _lib.POLICY_FULL_CHUNK_KPI_SOURCES
     kernels, meta = _asm(src, [], tmp_path_factory)
-    names = [k for k in kernels if 'cl_rollout_full_policy_chunk_kpi_kernel' in k]
-    by = {int(re.search(r'cl_rollout_full_policy_chunk_kpi_kernelILi(\d)EE', k).group(1)): k for k in names}
+    names = [k for k in kernels if 'cl_rollout_full_policy_kernel' in k]
+    by = {int(re.search(r'cl_rollout_full_policy_kernelILi1ELi(\d)ELb0ELb1ELb1EE', k).group(1)): k for k in names}
     assert sorted(by) == [0, 2] and len(names) == 2
-    assert not [k for k in kernels if 'cl_rollout_full_policy_kernel' in k or 'cl_rollout_full_kernel' in k or 'cl_rollout_full_policy_chunk_kernel' in k
-                or 'cl_rollout_full_policy_kpi_kernel' in k]
+    assert not [k for k in kernels if (re.search(r'cl_rollout_full_policy_kernelILi\dELi\dELb\dELb\dELb\dEE', k) and 'ELb0ELb1ELb1EE' not in k) or 'cl_rollout_full_kernel' in k]
     (series,) = [k for k in kernels if 'cl_kpi_series_chunk_kernel' in k]
     assert len([k for k in kernels if 'cl_finish_kernel' in k]) == 1
     text = next(tmp_path_factory.getbasetemp().glob('isa*/' + src.stem + '.s')).read_text()
@@ -183,8 +183,8 @@ def test_kernel_isa(tmp_path_factory):
 
 
 def test_lds_formula():
-    """`_lib.policy_full_chunk_kpi_lds_bytes` is the header's `rollout_full_policy_chunk_kpi_lds_floats`: ring [S][2][nw][64] + rows [nw][CLPF_ROW]."""
-    head = (_lib.CSRC / 'cl_policy_full_chunk_kpi.h').read_text()
+    """`_lib.policy_full_chunk_kpi_lds_bytes` is the header's `rollout_full_policy_chunk_kpi_lds_floats` (csrc/cl_policy_full.h): ring [S][2][nw][64] + rows [nw][CLPF_ROW]."""
+    head = (_lib.CSRC / 'cl_policy_full.h').read_text()
     assert re.search(r'rollout_full_policy_chunk_kpi_lds_floats\(int nw\) \{ return \(size_t\)CL_RKPI_S \* 2 \* nw \* 64 \+ \(size_t\)nw \* CLPF_ROW; \}', head)
     assert re.search(r'constexpr int CL_RKPI_S = 8;', (_lib.CSRC / 'cl_rollout.h').read_text())
     row = 4 * (policy.CLPF_ND + policy.CLPF_NA) * (policy.CLPF_MAX_HIDDEN // 4) + 8 * policy.CLPF_NA

@@ -118,13 +118,15 @@ def test_refusals_name_their_cause_before_any_hip_call(lib):
 
 # ---- 3. generated code ----------------------------------------------------------------------------------------------------------------
 def test_kernel_isa(tmp_path_factory):
-    """Every instantiation of cl_rollout_full_policy_kernel<VEC, PREC, MARL>: at most 128 VGPRs (a 1024-thread workgroup's cap), no scratch
+    """Exactly the five instantiations of cl_rollout_full_policy_kernel<VEC, PREC, MARL, KPI = false, CHUNK = false> (csrc/cl_policy_full.h: reported
+    as `cl_rollout_full_policy_kernel<VEC, PREC, MARL>`) and none of another variant in this unit: at most 128 VGPRs (a 1024-thread workgroup's cap), no scratch
     memory, no static LDS (it is all dynamic: `_lib.policy_full_lds_bytes`, within the CU's 160 KiB at the largest geometry)."""
     (src,) = _lib.POLICY_FULL_SOURCES
     kernels, meta = _asm(src, [], tmp_path_factory)
     names = [k for k in kernels if 'cl_rollout_full_policy_kernel' in k]
-    by = {tuple(int(x) for x in re.search(r'cl_rollout_full_policy_kernelILi(\d)ELi(\d)ELb(\d)EE', k).groups()): k for k in names}
+    by = {tuple(int(x) for x in re.search(r'cl_rollout_full_policy_kernelILi(\d)ELi(\d)ELb(\d)ELb0ELb0EE', k).groups()): k for k in names}
     assert sorted(by) == [(1, 0, 0), (1, 0, 1), (1, 2, 0), (1, 2, 1), (2, 0, 0)] and len(names) == 5
+    assert not [k for k in kernels if re.search(r'cl_rollout_full_policy_kernelILi\dELi\dELb\dELb\dELb\dEE', k) and 'ELb0ELb0EE' not in k]     # no KPI / CHUNK = true one here
     for key, k in by.items():
         assert meta[k]['private_seg_size'] == 0, (k, meta[k])
         assert meta[k]['num_vgpr'] <= 128, (k, meta[k])

@@ -1,5 +1,5 @@
 """The closed-loop policy rollout of thermal districts that keeps the streaming KPIs (`clpfk_rollout_mlp_kpi_f32`, kernel
-`cl_rollout_full_policy_kpi_kernel` in csrc/cl_policy_full_kpi.h, library ``libcitylearn_amd_policy_full_kpi.so``) as far as it can be checked
+`cl_rollout_full_policy_kpi_kernel`: csrc/cl_policy_full.h at KPI = true, library ``libcitylearn_amd_policy_full_kpi.so``) as far as it can be checked
 without a GPU: the library's symbol list, the argument validation (before any HIP call), registers / scratch / LDS of every instantiation -- and
 that the thermal policy library without KPIs is what it was."""
 import ctypes
@@ -95,14 +95,15 @@ def test_refusals_name_their_cause_before_any_hip_call(lib):
 
 
 def test_kernel_isa(tmp_path_factory):
-    """The four instantiations of cl_rollout_full_policy_kpi_kernel<PREC, MARL>: at most 128 VGPRs (a 1024-thread workgroup's cap), no scratch
+    """Exactly the four instantiations of cl_rollout_full_policy_kernel<1, PREC, MARL, KPI = true, CHUNK = false> (csrc/cl_policy_full.h: reported as
+    `cl_rollout_full_policy_kpi_kernel<PREC, MARL>`) and none of another variant in this unit: at most 128 VGPRs (a 1024-thread workgroup's cap), no scratch
     memory, no static LDS (all dynamic: `_lib.policy_full_kpi_lds_bytes`, the header's formula, within the CU's 160 KiB at nw = 16)."""
     (src,) = _lib.POLICY_FULL_KPI_SOURCES
     kernels, meta = _asm(src, [], tmp_path_factory)
-    names = [k for k in kernels if 'cl_rollout_full_policy_kpi_kernel' in k]
-    by = {tuple(int(x) for x in re.search(r'cl_rollout_full_policy_kpi_kernelILi(\d)ELb(\d)EE', k).groups()): k for k in names}
+    names = [k for k in kernels if 'cl_rollout_full_policy_kernel' in k]
+    by = {tuple(int(x) for x in re.search(r'cl_rollout_full_policy_kernelILi1ELi(\d)ELb(\d)ELb1ELb0EE', k).groups()): k for k in names}
     assert sorted(by) == [(0, 0), (0, 1), (2, 0), (2, 1)] and len(names) == 4
-    assert not [k for k in kernels if 'cl_rollout_full_policy_kernel' in k]              # the parent's template is not instantiated here
+    assert not [k for k in kernels if re.search(r'cl_rollout_full_policy_kernelILi\dELi\dELb\dELb\dELb\dEE', k) and 'ELb1ELb0EE' not in k]     # no plain or CHUNK = true one here
     for key, k in by.items():
         assert meta[k]['private_seg_size'] == 0, (k, meta[k])
         assert meta[k]['num_vgpr'] <= 128, (k, meta[k])
@@ -110,7 +111,7 @@ def test_kernel_isa(tmp_path_factory):
     static = re.findall(r'\.group_segment_fixed_size:\s*(\d+)', next(tmp_path_factory.getbasetemp().glob('isa*/' + src.stem + '.s')).read_text())
     assert static and set(static) == {'0'}, static
     # the header's constexpr formula, evaluated from its text
-    text = (_lib.CSRC / 'cl_policy_full_kpi.h').read_text()
+    text = (_lib.CSRC / 'cl_policy_full.h').read_text()
     body = re.search(r'constexpr size_t rollout_full_policy_kpi_lds_floats\(int nw\) \{\s*return (.*?);\s*\}', text, flags=re.S).group(1)
     body = re.sub(r'\(size_t\)', '', body)
     full = abi._strip_comments(_lib.POLICY_FULL_HEADER.read_text())

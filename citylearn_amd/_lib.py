@@ -262,6 +262,12 @@ CENTRAL_DEEP_EXTENSIONS = (POLICY_CENTRAL_DEEP,)
 POLICY_FULL_CENTRAL = _Extension('policy_full_central', 'clpfca', 'central thermal policy', [], 'rollout_mlp_f32', PolicyFullMLP,
                                  headers=[POLICY_FULL.header])
 CENTRAL_THERMAL_EXTENSIONS = (POLICY_FULL_CENTRAL,)
+# ... and the THERMAL central-agent one whose MLP has TWO hidden layers (cl_policy_full_central_deep.hip; `clpfcd_mlp` is `clpfca_mlp` + `clpfd_mlp`'s
+# tail, so `PolicyFullDeepMLP` serves it).  With SLP vectorisation like cl_policy_full_central.hip (the translation unit says why).  A tuple of its
+# own: the tuples above stay what they are; `__graft_entry__.build()` builds it behind CENTRAL_THERMAL_EXTENSIONS.
+POLICY_FULL_CENTRAL_DEEP = _Extension('policy_full_central_deep', 'clpfcd', 'deep central thermal policy', [], 'rollout_mlp_f32', PolicyFullDeepMLP,
+                                      headers=[POLICY_FULL.header])
+CENTRAL_DEEP_THERMAL_EXTENSIONS = (POLICY_FULL_CENTRAL_DEEP,)
 
 # The names other code and the tests use: read-only views of the descriptions above (build / load / check read the description, so rebinding one
 # of these changes nothing -- change the description's attribute instead)
@@ -345,6 +351,15 @@ def policy_full_central_lds_bytes(n_bldg: int, h: int) -> int:
     [h / 4][n_bldg][5][4], the staged head rows [n_bldg][4 x 64 + 4 x 8] -- 92 160 bytes at sixteen buildings and 64 units
     (tests/test_policy_full_central_host.py holds it against the header's formula)."""
     return 4 * (n_bldg * 4 * 64 + 5 * n_bldg * 64 + h * 64 + 5 * h * n_bldg + n_bldg * (4 * 64 + 4 * 8))
+
+
+def policy_full_central_deep_lds_bytes(n_bldg: int, h1: int, h2: int) -> int:
+    """Dynamic LDS of one `cl_rollout_full_policy_central_deep_kernel` workgroup over ``n_bldg`` buildings (one wave each, one env per lane) at
+    ``h1`` x ``h2`` hidden units: include/citylearn_amd_policy_full_central_deep.h's formula (csrc/cl_policy_full_central_deep.h's
+    `rollout_full_policy_central_deep_lds_floats`) -- `policy_full_central_lds_bytes`' regions at ``h1`` units, plus the second hidden layer Hh2
+    [h2][64] and the staged ``l2`` [h1 + 1][h2] -- 125 184 bytes at sixteen buildings and 64 x 64 units
+    (tests/test_policy_full_central_deep_host.py holds it against the header's formula)."""
+    return 4 * (n_bldg * 4 * 64 + 5 * n_bldg * 64 + h1 * 64 + h2 * 64 + 5 * h1 * n_bldg + (h1 + 1) * h2 + n_bldg * (4 * 64 + 4 * 8))
 
 
 def policy_chunk_lds_bytes(nw: int, vec: int) -> int:

@@ -603,7 +603,14 @@ class StepEngine:
         every reward kind of the thermal kernel, MARL included, with the central kernel's two workgroup barriers per step.  A battery + PV
         district, more than 16 buildings and a ``kpi=True`` engine are the library's refusals; ``chunked=True`` is the `ValueError` above and
         ``kpi=True`` the central `NotImplementedError`, which names the heads' action planes: record, then replay ``policy.CLPF_T_ACTION + head``
-        into the columns of `policy.head_columns` on a ``kpi=True`` engine."""
+        into the columns of `policy.head_columns` on a ``kpi=True`` engine.
+
+        ``policy_tables`` from `policy.DeepCentralStorageMLPPolicy.pack` (a `DeepCentralStoragePolicyTables`: the central agent's MLP with TWO
+        hidden layers of 4 .. 64 units each and up to four storage heads per building) sends the same thermal districts to
+        `cl_rollout_full_policy_central_deep_kernel` (`clpfcd_rollout_mlp_f32`, ``libcitylearn_amd_policy_full_central_deep.so``): the central
+        thermal kernel's step with a third phase and workgroup barrier for layer 2, in exact fp32; same record, noise stream and reward kinds
+        (MARL included).  Its refusals are the central thermal tables': the library's for a battery + PV district, more than 16 buildings and a
+        ``kpi=True`` engine, the `ValueError` above for ``chunked=True`` and the central `NotImplementedError` for ``kpi=True``."""
         kind = policy_tables.kind          # (`policy._Kind`: the libraries, the trajectory's plane count and what a build without KPIs raises)
         ext_chunk = kind.ext_chunk or kind.ext_chunk_pair
         if chunked and (ext_chunk is None or (kind.ext_chunk is None and not self.dims.flags & abi.CLD_LEAN)):

@@ -198,6 +198,9 @@ CLPCD_MAX_HIDDEN, CLPCD_MAX_BLDG = CENTRAL_DEEP_CONSTANTS['CLPCD_MAX_HIDDEN'], C
 # are the thermal kernel's
 FULL_CENTRAL_CONSTANTS = _header_constants(_lib.POLICY_FULL_CENTRAL.header, 'CLPFCA_')
 CLPFCA_MAX_HIDDEN, CLPFCA_MAX_BLDG = FULL_CENTRAL_CONSTANTS['CLPFCA_MAX_HIDDEN'], FULL_CENTRAL_CONSTANTS['CLPFCA_MAX_BLDG']
+# ... with two hidden layers (csrc/cl_policy_full_central_deep.h, libcitylearn_amd_policy_full_central_deep.so)
+FULL_CENTRAL_DEEP_CONSTANTS = _header_constants(_lib.POLICY_FULL_CENTRAL_DEEP.header, 'CLPFCD_')
+CLPFCD_MAX_HIDDEN, CLPFCD_MAX_BLDG = FULL_CENTRAL_DEEP_CONSTANTS['CLPFCD_MAX_HIDDEN'], FULL_CENTRAL_DEEP_CONSTANTS['CLPFCD_MAX_BLDG']
 HEAD_NAMES = ('electrical_storage', 'cooling_storage', 'heating_storage', 'dhw_storage')                  # heads in CLPF_A_* order
 
 
@@ -391,6 +394,23 @@ class CentralStoragePolicyTables(CentralPolicyTables):
         return self.dep.reshape(S, G, B, CLPF_ND, 4).permute(0, 2, 3, 1, 4).reshape(S, B, CLPF_ND, G * 4)
 
 
+class DeepCentralStoragePolicyTables(CentralStoragePolicyTables):
+    """`DeepCentralStorageMLPPolicy.pack`'s result: `CentralStoragePolicyTables`' members for the first layer (``pre [n_sets, n_rows, H1]``, ``dep
+    [n_sets, H1 / 4, n_bldg, CLPF_ND, 4]``) and the host side ``[n_bldg, CLPF_NA]``, then the second layer ``l2 [n_sets, H1 + 1, H2]`` --
+    ``ACT_SCALE * W2`` TRANSPOSED (one row per first-layer unit), ``ACT_SCALE * b2`` as the last row: `DeepCentralPolicyTables`' layout -- and
+    ``out = [w3 | b3]`` ``[n_sets, n_bldg, CLPF_NA, H2 + 1]``.  ``n_hidden`` is H1, ``n_hidden2`` H2."""
+
+    def __init__(self, pre, dep, l2, out, net_reset, act_low, act_high, sigma, set_of_block, cols, low_bldg, high_bldg, sigma_bldg, version):
+        super().__init__(pre, dep, out, net_reset, act_low, act_high, sigma, set_of_block, cols, low_bldg, high_bldg, sigma_bldg, version)
+        self.l2, self.n_hidden2 = l2, int(out.shape[-1]) - 1
+
+    def struct(self, seed: int):
+        p = lambda t: None if t is None else t.data_ptr()
+        return self.kind.struct(self.n_hidden, self.n_sets, self.n_device_cols, 0, p(self.pre), p(self.dep), p(self.out), p(self.set_of_block),
+                                p(self.net_reset), p(self.act_low), p(self.act_high), p(self.sigma), int(seed) & (2 ** 64 - 1), self.n_hidden2, 0,
+                                p(self.l2))
+
+
 def _l2_fragments(w2s: np.ndarray, b2s: np.ndarray) -> np.ndarray:
     """The matrix-core layout of layer 2 (`DeepPolicyTables`) from the scaled weights ``[S, B, H2, H1]`` and biases ``[S, B, H2]`` (float64):
     float32 ``[S, B, 1024 + 32 + 4]``."""
@@ -481,6 +501,12 @@ _CENTRAL_THERMAL = _Kind(terms=_THERMAL.terms, head_slots=_THERMAL.head_slots, h
                          tables=CentralStoragePolicyTables, struct=_lib.PolicyFullMLP, constants=FULL_CENTRAL_CONSTANTS, max_hidden=CLPFCA_MAX_HIDDEN,
                          n_planes=CLPF_NT, ext=_lib.POLICY_FULL_CENTRAL, ext_kpi=None, no_kpi_error=NotImplementedError, one_row_max=CLPFCA_MAX_BLDG,
                          central=True)
+# a central agent with two hidden layers on a thermal district: the central thermal kind's inputs, heads, record and geometry; a library of its own
+# once more
+_CENTRAL_DEEP_THERMAL = _Kind(terms=_THERMAL.terms, head_slots=_THERMAL.head_slots, head_shape=(CLPF_NA,), refuse_device_actions=True, only=_THERMAL.only,
+                              tables=DeepCentralStoragePolicyTables, struct=_lib.PolicyFullDeepMLP, constants=FULL_CENTRAL_DEEP_CONSTANTS,
+                              max_hidden=CLPFCD_MAX_HIDDEN, n_planes=CLPF_NT, ext=_lib.POLICY_FULL_CENTRAL_DEEP, ext_kpi=None,
+                              no_kpi_error=NotImplementedError, one_row_max=CLPFCD_MAX_BLDG, central=True)
 # (terms and heads above are written in the header's order)
 assert (CLPF_D_SOC, CLPF_D_CS, CLPF_D_HS, CLPF_D_DS, CLPF_D_NET) == tuple(range(CLPF_ND)) and (CLPF_A_ES, CLPF_A_CS, CLPF_A_HS, CLPF_A_DS) == tuple(range(CLPF_NA))
 
@@ -1362,8 +1388,15 @@ class CentralStorageMLPPolicy:
         building with a cooling / heating device ACTION column; with `CentralMLPPolicy.pack`'s: a layout built with ``central_agent=False``, a
         vector of another length."""
         self._check_layout(layout)
-        kind = self.kind
         w1, b1, w2, b2 = self._full(len(layout.building_names))
+        pre, dep, rest = self._pack_thermal_front(layout, tab, w1, b1, device, set_of_block)
+        out = torch.cat([torch.from_numpy(np.array(v, dtype=np.float64)).to(pre.device) for v in (w2, b2[..., None])], dim=-1)
+        return CentralStoragePolicyTables(pre, dep, out.to(torch.float32).contiguous(), *rest, self.version)
+
+    def _pack_thermal_front(self, layout: ObservationLayout, tab, w1, b1, device, set_of_block):
+        """`_pack_front` over the thermal kind's five terms, with what a thermal district adds: the refusal of device ACTION columns, and zero
+        weights for the terms of a storage a building lacks.  What `CentralStorageMLPPolicy.pack` and `DeepCentralStorageMLPPolicy.pack` share."""
+        kind = self.kind
         pre, dep, rest = self._pack_front(layout, tab, w1, b1, device, set_of_block)
         params_i = np.ascontiguousarray(tab.params).view(np.int32)
         bflags = np.ascontiguousarray(tab.params).view(np.uint32)[:, abi.CLP_FLAGS]
@@ -1375,5 +1408,110 @@ class CentralStorageMLPPolicy:
         # a storage the building lacks: its plane stays 0 in the kernel, its weights are 0 here
         has = np.array([[flag is None or bool(int(bflags[i]) & flag) for _, flag in kind.terms] for i in range(len(layout.building_names))])
         dep = dep * torch.from_numpy(has.astype(np.float32)).to(dep.device)[None, None, :, :, None]
-        out = torch.cat([torch.from_numpy(np.array(v, dtype=np.float64)).to(pre.device) for v in (w2, b2[..., None])], dim=-1)
-        return CentralStoragePolicyTables(pre, dep.contiguous(), out.to(torch.float32).contiguous(), *rest, self.version)
+        return pre, dep.contiguous(), rest
+
+
+class DeepCentralStorageMLPPolicy:
+    """`CentralStorageMLPPolicy` with TWO hidden layers -- a SAC / PPO actor trained with ``central_agent=True`` on a THERMAL district:
+
+        h1 = tanh(W1 obs + b1),   h2 = tanh(W2 h1 + b2),   act[b][a] = clamp(mid + half tanh(w3[b][a] . h2 + b3[b][a]) + sigma z, low, high)
+
+    for every head (`HEAD_NAMES`, `CLPF_A_*` order) whose building has that action column.  `obs`, the bounds, sigma, z, the noise stream -- Philox
+    keyed by the head's action column -- and the env-dependent inputs (EVERY building's own storage socs and ``net_electricity_consumption``) are
+    `CentralStorageMLPPolicy`'s.  Thermal districts without the LSTM stage and without device actions (the 2020 / 2021 schemas) of up to 16
+    buildings: one launch of `cl_rollout_full_policy_central_deep_kernel` (csrc/cl_policy_full_central_deep.h,
+    ``libcitylearn_amd_policy_full_central_deep.so``), layer 2 in exact fp32.
+
+    ``w1 [n_sets, H1, n_cols]``, ``b1 [n_sets, H1]``, ``w2 [n_sets, H2, H1]``, ``b2 [n_sets, H2]``, ``w3 [n_sets, n_bldg, 4, H2]``,
+    ``b3 [n_sets, n_bldg, 4]`` (anything array-like; kept in float64); a leading dimension of 1 broadcasts.  ``H1``, ``H2``: 4, 8, .. 64, independent
+    of each other.  ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
+
+    The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
+    kind = _CENTRAL_DEEP_THERMAL
+    _NAMES = ('w1', 'b1', 'w2', 'b2', 'w3', 'b3')
+
+    def __init__(self, w1, b1, w2, b2, w3, b3, sigma=None):
+        self.w1, self.b1, self.w2, self.b2, self.w3, self.b3 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2, w3, b3))
+        if [getattr(self, n).ndim for n in self._NAMES] != [3, 2, 3, 2, 4, 3]:
+            raise ValueError(f'w1 [n_sets, H1, n_cols], b1 [n_sets, H1], w2 [n_sets, H2, H1], b2 [n_sets, H2], w3 [n_sets, n_bldg, {CLPF_NA}, H2], '
+                             f'b3 [n_sets, n_bldg, {CLPF_NA}]')
+        self.n_hidden, self.n_obs, self.n_hidden2, self.n_bldg = (int(self.w1.shape[1]), int(self.w1.shape[2]), int(self.w2.shape[1]),
+                                                                  int(self.w3.shape[1]))
+        for name, h in (('H1', self.n_hidden), ('H2', self.n_hidden2)):
+            if h % 4 or not 4 <= h <= CLPFCD_MAX_HIDDEN:
+                raise ValueError(f'{name}={h}: the deep central thermal policy kernel takes 4, 8, .. {CLPFCD_MAX_HIDDEN} units per hidden layer')
+        if self.b1.shape[1] != self.n_hidden or self.w2.shape[2] != self.n_hidden:
+            raise ValueError('b1 / w2 disagree with w1 about H1')
+        if self.b2.shape[1] != self.n_hidden2 or self.w3.shape[2:] != (CLPF_NA, self.n_hidden2) or self.b3.shape[1:] != (self.n_bldg, CLPF_NA):
+            raise ValueError(f'b2 / w3 disagree with w2 about H2, b3 with w3 about n_bldg, or w3 / b3 do not have {CLPF_NA} heads')
+        self.n_sets = max(getattr(self, n).shape[0] for n in self._NAMES)
+        self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
+        self.version = 0
+
+    invalidate = DeepMLPPolicy.invalidate
+    update = DeepMLPPolicy.update
+    _check_layout = CentralMLPPolicy._check_layout
+    _pack_front = CentralMLPPolicy._pack_front
+    _pack_thermal_front = CentralStorageMLPPolicy._pack_thermal_front
+
+    def _full(self, n_bldg: Optional[int] = None):
+        S, H1, H2, B = self.n_sets, self.n_hidden, self.n_hidden2, self.n_bldg
+        if n_bldg is not None and n_bldg != B:
+            raise ValueError(f'w3 has heads for {B} buildings, the district has {n_bldg}')
+        shapes = ((S, H1, self.n_obs), (S, H1), (S, H2, H1), (S, H2), (S, B, CLPF_NA, H2), (S, B, CLPF_NA))
+        try:
+            return tuple(np.broadcast_to(getattr(self, n), sh) for n, sh in zip(self._NAMES, shapes))
+        except ValueError as e:
+            raise ValueError(f'the weights do not broadcast to {S} sets: {e}') from None
+
+    # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
+    def actions_host(self, obs, tables: DeepCentralStoragePolicyTables, noise=None, set_index: int = 0) -> np.ndarray:
+        """float64 numpy evaluation of the plain MLP: ``obs [..., n_cols]`` (the central-agent vector) -> actions ``[..., n_bldg, 4]`` (0 for a
+        head whose column the building lacks); the other arguments are `CentralStorageMLPPolicy.actions_host`'s."""
+        x = np.asarray(obs, dtype=np.float64)
+        w1, b1, w2, b2, w3, b3 = (v[set_index] for v in self._full())
+        h1 = np.tanh(np.einsum('jc,...c->...j', w1, x) + b1)
+        h2 = np.tanh(np.einsum('ij,...j->...i', w2, h1) + b2)
+        lo, hi = tables.low_bldg, tables.high_bldg
+        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('bai,...i->...ba', w3, h2) + b3)
+        if noise is not None:
+            a = a + tables.sigma_bldg * np.asarray(noise, dtype=np.float64)
+        return np.where(tables.cols >= 0, np.clip(a, lo, hi), 0.0)
+
+    def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
+        """The same MLP (no noise) written in torch over the env's observation TENSOR of a ``central_agent=True`` env: a
+        `VectorCityLearnEnv.capture_rollout` policy ``f(obs [n_envs, n_cols], i=None) -> actions [n_act_cols, n_envs]``."""
+        self._check_layout(layout)
+        w1, b1, w2, b2, w3, b3 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(len(layout.building_names)))
+        hc = _head_columns(tab, self.kind)
+        low, high = layout.spec.action_limits()
+        sel = np.nonzero(hc >= 0)                                                # the heads that have a column
+        rows = torch.as_tensor(hc[sel], device=device)
+        lo = torch.as_tensor(np.asarray(low)[hc[sel]], dtype=dtype, device=device)
+        hi = torch.as_tensor(np.asarray(high)[hc[sel]], dtype=dtype, device=device)
+        flat = torch.as_tensor(np.ravel_multi_index(sel, hc.shape), device=device)
+        w3f, b3f = w3.reshape(-1, w3.shape[-1])[flat], b3.reshape(-1)[flat]     # [present heads, H2], [present heads]
+        n_act = len(low)
+
+        def f(obs, i=None):
+            h1 = torch.tanh(obs.to(dtype) @ w1.t() + b1)                         # [E, H1]
+            h2 = torch.tanh(h1 @ w2.t() + b2)                                    # [E, H2]
+            o = torch.tanh(h2 @ w3f.t() + b3f)                                   # [E, present heads]
+            a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
+            out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
+            out[rows] = a.t().to(torch.float32)
+            return out
+        return f
+
+    # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
+    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None) -> DeepCentralStoragePolicyTables:
+        """The first layer split exactly as `CentralStorageMLPPolicy.pack` splits it (the same function: the same refusals of device actions and
+        the LSTM stage, the same zero rows for a storage a building lacks), then ``l2`` as `DeepCentralMLPPolicy.pack` builds it and ``out``
+        as `DeepCentralStoragePolicyTables` describes it, in float64 rounded once."""
+        self._check_layout(layout)
+        w1, b1, w2, b2, w3, b3 = self._full(len(layout.building_names))
+        pre, dep, rest = self._pack_thermal_front(layout, tab, w1, b1, device, set_of_block)
+        f64 = lambda v: torch.from_numpy(np.array(v, dtype=np.float64)).to(pre.device)
+        l2 = (torch.cat([f64(w2).transpose(1, 2), f64(b2)[:, None, :]], dim=1) * ACT_SCALE).to(torch.float32)
+        out = torch.cat([f64(w3), f64(b3)[..., None]], dim=-1)
+        return DeepCentralStoragePolicyTables(pre, dep, l2.contiguous(), out.to(torch.float32).contiguous(), *rest, self.version)

@@ -469,7 +469,11 @@ class VectorCityLearnEnv:
         record (`policy.CLPF_NT` planes) and noise stream as a `StorageMLPPolicy`, MARL included; on an env built with ``central_agent=False`` it
         is a `ValueError`.  More than 16 buildings (no chunked launch is asked for: the hidden layer cannot be cut into building chunks) and a
         battery + PV district are the library's refusals; ``kpi=True`` raises `NotImplementedError` (record, then replay the heads' action planes
-        on a ``kpi=True`` env)."""
+        on a ``kpi=True`` env).
+
+        A `policy.DeepCentralStorageMLPPolicy` (the central agent's MLP with TWO hidden layers of 4 .. 64 units each, up to four storage heads
+        per building) drives the same thermal districts of an env built with ``central_agent=True`` through
+        `cl_rollout_full_policy_central_deep_kernel`; record, noise stream, MARL and every refusal are the `CentralStorageMLPPolicy`'s."""
         chunked =(policy.kind.ext_chunk or policy.kind.ext_chunk_pair) is not None and self.engine.n_bldg > policy.kind.one_row_max
         if policy.kind.central and not self.central_agent:
             raise ValueError(f'a {type(policy).__name__} needs an env built with central_agent=True: this env hands out one observation vector per '

@@ -263,7 +263,7 @@ POLICY_FULL_CENTRAL = _Extension('policy_full_central', 'clpfca', 'central therm
                                  headers=[POLICY_FULL.header])
 CENTRAL_THERMAL_EXTENSIONS = (POLICY_FULL_CENTRAL,)
 # ... and the THERMAL central-agent one whose MLP has TWO hidden layers (cl_policy_full_central_deep.hip; `clpfcd_mlp` is `clpfca_mlp` + `clpfd_mlp`'s
-# tail, so `PolicyFullDeepMLP` serves it).  With SLP vectorisation like cl_policy_full_central.hip (the translation unit says why).  A tuple of its
+# tail, so `PolicyFullDeepMLP` serves it): cl_policy_full_central.h's template at DEEP = true.  With SLP vectorisation like cl_policy_full_central.hip (the translation unit says why).  A tuple of its
 # own: the tuples above stay what they are; `__graft_entry__.build()` builds it behind CENTRAL_THERMAL_EXTENSIONS.
 POLICY_FULL_CENTRAL_DEEP = _Extension('policy_full_central_deep', 'clpfcd', 'deep central thermal policy', [], 'rollout_mlp_f32', PolicyFullDeepMLP,
                                       headers=[POLICY_FULL.header])
@@ -355,7 +355,7 @@ def policy_full_central_lds_bytes(n_bldg: int, h: int) -> int:
 
 def policy_full_central_deep_lds_bytes(n_bldg: int, h1: int, h2: int) -> int:
     """Dynamic LDS of one `cl_rollout_full_policy_central_deep_kernel` workgroup over ``n_bldg`` buildings (one wave each, one env per lane) at
-    ``h1`` x ``h2`` hidden units: include/citylearn_amd_policy_full_central_deep.h's formula (csrc/cl_policy_full_central_deep.h's
+    ``h1`` x ``h2`` hidden units: include/citylearn_amd_policy_full_central_deep.h's formula (csrc/cl_policy_full_central.h's
     `rollout_full_policy_central_deep_lds_floats`) -- `policy_full_central_lds_bytes`' regions at ``h1`` units, plus the second hidden layer Hh2
     [h2][64] and the staged ``l2`` [h1 + 1][h2] -- 125 184 bytes at sixteen buildings and 64 x 64 units
     (tests/test_policy_full_central_deep_host.py holds it against the header's formula)."""

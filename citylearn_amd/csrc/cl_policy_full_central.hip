@@ -1,7 +1,7 @@
 // cl_policy_full_central.hip -- the translation unit of libcitylearn_amd_policy_full_central.so (include/citylearn_amd_policy_full_central.h):
 // cl_kernels.hip reduced to the helpers the fused rollout kernels share and the packed thermal unit of cl_full.h (CL_TU_POLICY + CL_TU_POLICY_FULL,
-// as in cl_policy_full.hip) + cl_policy_full_central.h's closed-loop kernel under a central-agent policy, its launcher and the `clpfca_*` entry
-// points.  Compile flags: the library's common ones and nothing else -- NOT under CL_TU_NOSLP and compiled WITH SLP vectorisation, like
+// as in cl_policy_full.hip) + cl_policy_full_central.h's closed-loop kernel under a central-agent policy at DEEP = false (one hidden layer), its
+// launcher and the `clpfca_*` entry points.  Compile flags: the library's common ones and nothing else -- NOT under CL_TU_NOSLP and compiled WITH SLP vectorisation, like
 // cl_policy_full.hip.  Decided from the generated code of both builds: the four instantiations take the same registers either way (70 / 106 / 106 /
 // 121 VGPRs, no scratch memory -- unlike cl_policy_full_deep.hip, whose layer 2 spills under SLP), and with SLP the hidden phase's inner loop pairs
 // its four fused-multiply-add chains into v_pk_fma_f32 with the plane value broadcast (op_sel_hi): 10 VALU instructions per (group, building)
@@ -15,9 +15,11 @@
 
 namespace {
 
+static_assert(CLPFCA_MAX_HIDDEN == CLPFC_MAX_HIDDEN, "the staged head row is sized for the public header's limit");
+
 // the launcher of this unit; key = 10 * PREC + MARL
 int launch_policy_full_central(int prec, bool marl, unsigned grid, unsigned block, size_t lds, hipStream_t s, const PolicyArgs& p) {
-#define CL_POLFCA(P, M) CL_POLICY_LAUNCH(cl_rollout_full_policy_central_kernel<P, M>)
+#define CL_POLFCA(P, M) CL_POLICY_LAUNCH(cl_rollout_full_policy_central_kernel<P, M, false>)
     switch (prec * 10 + (marl ? 1 : 0)) {
     case 0: CL_POLFCA(0, false); break;
     case 1: CL_POLFCA(0, true); break;

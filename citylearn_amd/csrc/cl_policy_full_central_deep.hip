@@ -1,22 +1,24 @@
 // cl_policy_full_central_deep.hip -- the translation unit of libcitylearn_amd_policy_full_central_deep.so
 // (include/citylearn_amd_policy_full_central_deep.h): cl_kernels.hip reduced to the helpers the fused rollout kernels share and the packed thermal
-// unit of cl_full.h (CL_TU_POLICY + CL_TU_POLICY_FULL, as in cl_policy_full_central.hip) + cl_policy_full_central_deep.h's closed-loop kernel
-// under a central-agent policy with two hidden layers, its launcher and the `clpfcd_*` entry points.  Compile flags: the library's common ones and
+// unit of cl_full.h (CL_TU_POLICY + CL_TU_POLICY_FULL, as in cl_policy_full_central.hip) + cl_policy_full_central.h's closed-loop kernel
+// under a central-agent policy at DEEP = true (two hidden layers), its launcher and the `clpfcd_*` entry points.  Compile flags: the library's common ones and
 // nothing else -- NOT under CL_TU_NOSLP and compiled WITH SLP vectorisation, like cl_policy_full_central.hip: the first hidden phase and the packed
 // thermal unit are that unit's, and the second hidden phase is ONE loop of four chains over a broadcast ds_read_b128, which SLP pairs into
 // v_pk_fma_f32 as it pairs the first (the same bits: each half is an IEEE fma) -- unlike cl_policy_full_deep.hip's per-building layer 2, whose
-// unrolled H2 variants spill under SLP.  The register figures of the four instantiations are in cl_policy_full_central_deep.h's header.
+// unrolled H2 variants spill under SLP.  The register figures of the four instantiations are in cl_policy_full_central.h's header.
 #define CL_TU_POLICY
 #define CL_TU_POLICY_FULL
 #include "cl_kernels.hip"
 #include "../../include/citylearn_amd_policy_full_central_deep.h"
-#include "cl_policy_full_central_deep.h"
+#include "cl_policy_full_central.h"
 
 namespace {
 
+static_assert(CLPFCD_MAX_HIDDEN == CLPFC_MAX_HIDDEN, "the staged head row is sized for the public header's limit");
+
 // the launcher of this unit; key = 10 * PREC + MARL
 int launch_policy_full_central_deep(int prec, bool marl, unsigned grid, unsigned block, size_t lds, hipStream_t s, const CentralDeepFullPolicyArgs& p) {
-#define CL_POLFCD(P, M) CL_POLICY_LAUNCH(cl_rollout_full_policy_central_deep_kernel<P, M>)
+#define CL_POLFCD(P, M) CL_POLICY_LAUNCH(cl_rollout_full_policy_central_kernel<P, M, true>)
     switch (prec * 10 + (marl ? 1 : 0)) {
     case 0: CL_POLFCD(0, false); break;
     case 1: CL_POLFCD(0, true); break;

@@ -608,7 +608,7 @@ class StepEngine:
         ``policy_tables`` from `policy.DeepCentralStorageMLPPolicy.pack` (a `DeepCentralStoragePolicyTables`: the central agent's MLP with TWO
         hidden layers of 4 .. 64 units each and up to four storage heads per building) sends the same thermal districts to
         `cl_rollout_full_policy_central_deep_kernel` (`clpfcd_rollout_mlp_f32`, ``libcitylearn_amd_policy_full_central_deep.so``): the central
-        thermal kernel's step with a third phase and workgroup barrier for layer 2, in exact fp32; same record, noise stream and reward kinds
+        thermal kernel's template at DEEP = true (csrc/cl_policy_full_central.h), its step with a third phase and workgroup barrier for layer 2, in exact fp32; same record, noise stream and reward kinds
         (MARL included).  Its refusals are the central thermal tables': the library's for a battery + PV district, more than 16 buildings and a
         ``kpi=True`` engine, the `ValueError` above for ``chunked=True`` and the central `NotImplementedError` for ``kpi=True``."""
         kind = policy_tables.kind          # (`policy._Kind`: the libraries, the trajectory's plane count and what a build without KPIs raises)

@@ -198,7 +198,7 @@ CLPCD_MAX_HIDDEN, CLPCD_MAX_BLDG = CENTRAL_DEEP_CONSTANTS['CLPCD_MAX_HIDDEN'], C
 # are the thermal kernel's
 FULL_CENTRAL_CONSTANTS = _header_constants(_lib.POLICY_FULL_CENTRAL.header, 'CLPFCA_')
 CLPFCA_MAX_HIDDEN, CLPFCA_MAX_BLDG = FULL_CENTRAL_CONSTANTS['CLPFCA_MAX_HIDDEN'], FULL_CENTRAL_CONSTANTS['CLPFCA_MAX_BLDG']
-# ... with two hidden layers (csrc/cl_policy_full_central_deep.h, libcitylearn_amd_policy_full_central_deep.so)
+# ... with two hidden layers (csrc/cl_policy_full_central.h at DEEP = true, libcitylearn_amd_policy_full_central_deep.so)
 FULL_CENTRAL_DEEP_CONSTANTS = _header_constants(_lib.POLICY_FULL_CENTRAL_DEEP.header, 'CLPFCD_')
 CLPFCD_MAX_HIDDEN, CLPFCD_MAX_BLDG = FULL_CENTRAL_DEEP_CONSTANTS['CLPFCD_MAX_HIDDEN'], FULL_CENTRAL_DEEP_CONSTANTS['CLPFCD_MAX_BLDG']
 HEAD_NAMES = ('electrical_storage', 'cooling_storage', 'heating_storage', 'dhw_storage')                  # heads in CLPF_A_* order
@@ -1021,83 +1021,127 @@ class DeepStorageMLPPolicy:
                                        matrix_cores=matrix_cores)
 
 
-class CentralMLPPolicy:
-    """CityLearn's ``central_agent=True`` actor: ONE tanh MLP with one hidden layer over the district's observation vector returns every
-    building's electrical-storage action,
-
-        h = tanh(W1 obs + b1),   a_b = clamp(mid_b + half_b tanh(w2[b] . h + b2[b]) + sigma_b z, low_b, high_b)
-
-    `obs` = the central-agent observation vector as the env defines it (``ObservationLayout(..., central_agent=True).columns``: a shared
-    observation once, normalised or not, whatever the env was built with); the bounds, sigma, z and the noise stream are `MLPPolicy`'s.  The
-    env-dependent inputs are EVERY building's own ``electrical_storage_soc`` and ``net_electricity_consumption``; a building without a storage
-    action column feeds the hidden layer like any other and has no head.  Battery + PV districts of up to 32 buildings: one launch of
-    `cl_rollout_policy_central_kernel` (csrc/cl_policy_central.h, ``libcitylearn_amd_policy_central.so``).
-
-    ``w1 [n_sets, H, n_cols]``, ``b1 [n_sets, H]``, ``w2 [n_sets, n_bldg, H]``, ``b2 [n_sets, n_bldg]`` (anything array-like; kept in float64); a
-    leading dimension of 1 broadcasts.  ``H``: 4, 8, .. 64.  ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
-
-    The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
-    kind = _CENTRAL
+class _CentralBase:
+    """What the four central-agent policies share: everything but the class's `kind`, its number of hidden layers (`_NAMES`: the weight arrays
+    in order, the head's last), the texts of its constructor's refusals and the signature of `actions_host` on a thermal district.  The heads
+    are ``[n_bldg]`` or ``[n_bldg, 4]`` by `kind.head_shape`; a thermal kind (`kind.refuse_device_actions`) packs its first layer through
+    `_pack_thermal_front`."""
+    kind: _Kind
     _NAMES = ('w1', 'b1', 'w2', 'b2')
+    _WIDTHS = ('H',)                                         # the hidden layers as the refusals name them
+    _SHAPES_MSG: str                                         # the refusal of arrays of the wrong rank
+    _WIDTH_MSG: str                                          # ... of a hidden width ({name}, {h}, {max})
+    _MISMATCH: tuple                                         # ... of arrays that disagree: ((names, message), ..) in the order they are checked
 
     def __init__(self, w1, b1, w2, b2, sigma=None):
-        self.w1, self.b1, self.w2, self.b2 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2))
-        if [getattr(self, n).ndim for n in self._NAMES] != [3, 2, 3, 2]:
-            raise ValueError('w1 [n_sets, H, n_cols], b1 [n_sets, H], w2 [n_sets, n_bldg, H], b2 [n_sets, n_bldg]')
-        self.n_hidden, self.n_obs, self.n_bldg = int(self.w1.shape[1]), int(self.w1.shape[2]), int(self.w2.shape[1])
-        if self.n_hidden % 4 or not 4 <= self.n_hidden <= CLPCA_MAX_HIDDEN:
-            raise ValueError(f'H={self.n_hidden}: the central policy kernel takes 4, 8, .. {CLPCA_MAX_HIDDEN} hidden units')
-        if self.b1.shape[1] != self.n_hidden or self.w2.shape[2] != self.n_hidden or self.b2.shape[1] != self.n_bldg:
-            raise ValueError('b1 / w2 disagree with w1 about H, or b2 with w2 about n_bldg')
+        self._setup((w1, b1, w2, b2), sigma)
+
+    def _setup(self, arrays, sigma) -> None:
+        for n, x in zip(self._NAMES, arrays):
+            setattr(self, n, np.asarray(x, dtype=np.float64))
+        hs, deep = self.kind.head_shape, len(self._WIDTHS) > 1
+        if [getattr(self, n).ndim for n in self._NAMES] != [3, 2] * len(self._WIDTHS) + [2 + len(hs) + 1, 2 + len(hs)]:
+            raise ValueError(self._SHAPES_MSG)
+        self.n_hidden, self.n_obs, self.n_bldg = int(self.w1.shape[1]), int(self.w1.shape[2]), int(getattr(self, self._NAMES[-2]).shape[1])
+        if deep:
+            self.n_hidden2 = int(self.w2.shape[1])
+        for name, h in zip(self._WIDTHS, self._hidden):
+            if h % 4 or not 4 <= h <= self.kind.max_hidden:
+                raise ValueError(self._WIDTH_MSG.format(name=name, h=h, max=self.kind.max_hidden))
+        want = dict(zip(self._NAMES, self._shapes(None)))
+        for names, msg in self._MISMATCH:
+            if any(getattr(self, n).shape[1:] != want[n][1:] for n in names):
+                raise ValueError(msg)
         self.n_sets = max(getattr(self, n).shape[0] for n in self._NAMES)
         self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
         self.version = 0
 
-    invalidate = _MLPBase.invalidate
-    update = _MLPBase.update
+    @property
+    def _hidden(self) -> tuple:
+        return (self.n_hidden, self.n_hidden2) if len(self._WIDTHS) > 1 else (self.n_hidden,)
+
+    def _shapes(self, S) -> list:
+        """The shape of every array of `_NAMES` at ``S`` parameter sets."""
+        hs, widths = self.kind.head_shape, (self.n_obs,) + self._hidden
+        layers = [sh for i, o in zip(widths, widths[1:]) for sh in ((S, o, i), (S, o))]
+        return layers + [(S, self.n_bldg) + hs + widths[-1:], (S, self.n_bldg) + hs]
+
+    def invalidate(self) -> None:
+        """Tell the caches that the weights changed (see `MLPPolicy`'s docstring)."""
+        self.version += 1
+
+    def update(self, w1=None, b1=None, w2=None, b2=None, sigma=None) -> None:
+        """Replace some of the weight arrays (same shapes) and / or sigma, and bump `version`: the learner's step between two rollouts."""
+        self._replace((w1, b1, w2, b2), sigma)
+
+    def _replace(self, arrays, sigma) -> None:
+        for name, v in zip(self._NAMES, arrays):
+            if v is not None:
+                v = np.asarray(v, dtype=np.float64)
+                if v.shape != getattr(self, name).shape:
+                    raise ValueError(f'{name}: shape {v.shape} != {getattr(self, name).shape}')
+                setattr(self, name, v)
+        if sigma is not None:
+            self.sigma = np.asarray(sigma, dtype=np.float64)
+        self.invalidate()
 
     def _full(self, n_bldg: Optional[int] = None):
-        S, H, B = self.n_sets, self.n_hidden, self.n_bldg
-        if n_bldg is not None and n_bldg != B:
-            raise ValueError(f'w2 has heads for {B} buildings, the district has {n_bldg}')
+        if n_bldg is not None and n_bldg != self.n_bldg:
+            raise ValueError(f'{self._NAMES[-2]} has heads for {self.n_bldg} buildings, the district has {n_bldg}')
         try:
-            return tuple(np.broadcast_to(getattr(self, n), sh) for n, sh in zip(self._NAMES, ((S, H, self.n_obs), (S, H), (S, B, H), (S, B))))
+            return tuple(np.broadcast_to(getattr(self, n), sh) for n, sh in zip(self._NAMES, self._shapes(self.n_sets)))
         except ValueError as e:
-            raise ValueError(f'the weights do not broadcast to {S} sets: {e}') from None
+            raise ValueError(f'the weights do not broadcast to {self.n_sets} sets: {e}') from None
 
     # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
+    def _actions(self, obs, set_index, lo, hi, sigma, noise) -> np.ndarray:
+        """The hidden stack, the heads, the noise and the clamp in float64; ``lo``, ``hi``, ``sigma`` per head."""
+        *hidden, wo, bo = (v[set_index] for v in self._full())
+        h = np.asarray(obs, dtype=np.float64)
+        for w, b in zip(hidden[::2], hidden[1::2]):
+            h = np.tanh(np.einsum('ij,...j->...i', w, h) + b)
+        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('baj,...j->...ba' if self.kind.head_shape else 'bj,...j->...b', wo, h) + bo)
+        if noise is not None:
+            a = a + sigma * np.asarray(noise, dtype=np.float64)
+        return np.clip(a, lo, hi)
+
     def actions_host(self, obs, noise=None, tables: Optional[CentralPolicyTables] = None, low=None, high=None, sigma_bldg=None,
                      set_index: int = 0) -> np.ndarray:
         """float64 numpy evaluation of the plain MLP: ``obs [..., n_cols]`` (the central-agent vector) -> actions ``[..., n_bldg]``; the other
         arguments are `MLPPolicy.actions_host`'s."""
         pick = lambda arg, attr, default: np.asarray(arg if arg is not None else getattr(tables, attr) if tables is not None else default, dtype=np.float64)
-        x = np.asarray(obs, dtype=np.float64)
-        w1, b1, w2, b2 = (v[set_index] for v in self._full())
-        h = np.tanh(np.einsum('jc,...c->...j', w1, x) + b1)
-        lo, hi = pick(low, 'low_bldg', -1.0), pick(high, 'high_bldg', 1.0)
-        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('bj,...j->...b', w2, h) + b2)
+        sigma = None
         if noise is not None:
             if sigma_bldg is None and tables is None and self.sigma is not None and self.sigma.ndim:
                 raise ValueError('a per-column sigma needs `tables` (or `sigma_bldg`): which column drives which building')
-            a = a + pick(sigma_bldg, 'sigma_bldg', 0.0 if self.sigma is None or self.sigma.ndim else float(self.sigma)) * np.asarray(noise, dtype=np.float64)
-        return np.clip(a, lo, hi)
+            sigma = pick(sigma_bldg, 'sigma_bldg', 0.0 if self.sigma is None or self.sigma.ndim else float(self.sigma))
+        return self._actions(obs, set_index, pick(low, 'low_bldg', -1.0), pick(high, 'high_bldg', 1.0), sigma, noise)
+
+    def _actions_thermal(self, obs, tables, noise, set_index) -> np.ndarray:
+        """`actions_host` of a thermal kind: the heads' columns, bounds and sigmas from ``tables``; 0 for a head whose column the building lacks."""
+        return np.where(tables.cols >= 0, self._actions(obs, set_index, tables.low_bldg, tables.high_bldg, tables.sigma_bldg, noise), 0.0)
 
     def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
         """The same MLP (no noise) written in torch over the env's observation TENSOR of a ``central_agent=True`` env: a
         `VectorCityLearnEnv.capture_rollout` policy ``f(obs [n_envs, n_cols], i=None) -> actions [n_act_cols, n_envs]``."""
         self._check_layout(layout)
-        w1, b1, w2, b2 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(len(layout.building_names)))
+        *hidden, wo, bo = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(len(layout.building_names)))
+        layers = tuple(zip(hidden[::2], hidden[1::2]))
         hc = _head_columns(tab, self.kind)
         low, high = layout.spec.action_limits()
-        sel = np.nonzero(hc >= 0)[0]                                             # the buildings that have a storage column
-        rows, bsel = torch.as_tensor(hc[sel], device=device), torch.as_tensor(sel, device=device)
+        sel = np.nonzero(hc >= 0)                                                # the heads that have a column
+        rows = torch.as_tensor(hc[sel], device=device)
         lo = torch.as_tensor(np.asarray(low)[hc[sel]], dtype=dtype, device=device)
         hi = torch.as_tensor(np.asarray(high)[hc[sel]], dtype=dtype, device=device)
+        flat = torch.as_tensor(np.ravel_multi_index(sel, hc.shape), device=device)
+        wf, bf = wo.reshape(-1, wo.shape[-1])[flat], bo.reshape(-1)[flat]       # [present heads, H], [present heads]
         n_act = len(low)
 
         def f(obs, i=None):
-            h = torch.tanh(obs.to(dtype) @ w1.t() + b1)                          # [E, H]
-            o = torch.tanh(h @ w2.t() + b2)[:, bsel]                             # [E, driven buildings]
+            h = obs.to(dtype)
+            for w, b in layers:
+                h = torch.tanh(h @ w.t() + b)                                    # [E, H1], [E, H2]
+            o = torch.tanh(h @ wf.t() + bf)                                      # [E, present heads]
             a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
             out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
             out[rows] = a.t().to(torch.float32)
@@ -1113,21 +1157,29 @@ class CentralMLPPolicy:
 
     # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
     def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None) -> CentralPolicyTables:
-        """Split the first layer as `MLPPolicy.pack` splits it, over the central-agent vector of `layout` (built with ``central_agent=True``):
-        the env-independent columns of every table row go into ``pre [n_sets, n_rows, H]`` (one matmul in float64 on `device`, rounded once) --
-        no building axis --, ``W1[j][c] * col_scale[c]`` of the env-dependent columns (every building's own ``electrical_storage_soc`` and
-        ``net_electricity_consumption``) into ``dep`` in the kernel's order (`CentralPolicyTables`), their table offsets into ``pre``;
-        ``ACT_SCALE`` is folded into both.  A column fed by any other device plane raises `MLPPolicy.pack`'s ``ValueError``."""
+        """Split the first layer as `MLPPolicy.pack` splits it, over the central-agent vector of `layout` (built with ``central_agent=True``)
+        and the kind's terms: the env-independent columns of every table row go into ``pre [n_sets, n_rows, H1]`` (one matmul in float64 on
+        `device`, rounded once) -- no building axis --, ``W1[j][c] * col_scale[c]`` of the env-dependent columns (every building's own storage
+        soc(s) and ``net_electricity_consumption``) into ``dep`` in the kernel's order (the rows of a storage the building lacks stay 0), their
+        table offsets into ``pre``; ``ACT_SCALE`` is folded into both.  Then ``l2`` (two hidden layers) and ``out`` as the kind's tables class
+        describes them, in float64 rounded once.  Refused: a column fed by any other device plane (`MLPPolicy.pack`'s ``ValueError``; on a
+        thermal district `StorageMLPPolicy.pack`'s messages, the LSTM stage's indoor temperature among them), a reset value its table row does
+        not hold, on a thermal district a building with a cooling / heating device ACTION column, a layout built with ``central_agent=False``, a
+        vector of another length."""
         self._check_layout(layout)
-        w1, b1, w2, b2 = self._full(len(layout.building_names))
-        pre, dep, rest = self._pack_front(layout, tab, w1, b1, device, set_of_block)
-        out = torch.cat([torch.from_numpy(np.array(v, dtype=np.float64)).to(pre.device) for v in (w2, b2[..., None])], dim=-1)
-        return CentralPolicyTables(pre, dep, out.to(torch.float32).contiguous(), *rest, self.version)
+        w1, b1, *middle, wo, bo = self._full(len(layout.building_names))
+        front = self._pack_thermal_front if self.kind.refuse_device_actions else self._pack_front
+        pre, dep, rest = front(layout, tab, w1, b1, device, set_of_block)
+        f64 = lambda v: torch.from_numpy(np.array(v, dtype=np.float64)).to(pre.device)
+        l2 = [(torch.cat([f64(w).transpose(1, 2), f64(b)[:, None, :]], dim=1) * ACT_SCALE).to(torch.float32).contiguous()
+              for w, b in zip(middle[::2], middle[1::2])]
+        out = torch.cat([f64(wo), f64(bo)[..., None]], dim=-1)
+        return self.kind.tables(pre, dep, *l2, out.to(torch.float32).contiguous(), *rest, self.version)
 
     def _pack_front(self, layout: ObservationLayout, tab, w1, b1, device, set_of_block):
         """The first layer ``w1 [n_sets, H, n_cols]``, ``b1 [n_sets, H]`` (broadcast) split over the central-agent vector as `pack` describes it:
         ``(pre, dep, rest)`` with ``rest`` the tables' members behind ``out`` -- ``net_reset``, the bounds, sigma, ``set_of_block`` on `device`, the
-        host side.  What `CentralMLPPolicy.pack` and `DeepCentralMLPPolicy.pack` share."""
+        host side."""
         kind = self.kind
         obs = layout.episode(tab, reset_table=True)
         n_bldg, T, N = len(layout.building_names), int(obs.table.shape[0]), layout.n_cols
@@ -1186,8 +1238,60 @@ class CentralMLPPolicy:
                 (f32(net_reset), f32(low), f32(high), f32(sigma), sob, hc, at(low, -1.0), at(high, 1.0),
                  np.zeros(hc.shape) if sigma is None else at(sigma, 0.0)))
 
+    def _pack_thermal_front(self, layout: ObservationLayout, tab, w1, b1, device, set_of_block):
+        """`_pack_front` over the thermal kind's five terms, with what a thermal district adds: the refusal of device ACTION columns, and zero
+        weights for the terms of a storage a building lacks."""
+        kind = self.kind
+        pre, dep, rest = self._pack_front(layout, tab, w1, b1, device, set_of_block)
+        params_i = np.ascontiguousarray(tab.params).view(np.int32)
+        bflags = np.ascontiguousarray(tab.params).view(np.uint32)[:, abi.CLP_FLAGS]
+        for i in range(len(layout.building_names)):
+            for dname, slot in _DEVICE_SLOTS:
+                if params_i[i, slot] >= 0:
+                    raise ValueError(f'action {dname!r} of building {i} (column {int(params_i[i, slot])}): the thermal policy kernel has storage heads '
+                                     f'only {HEAD_NAMES}; a district with device actions runs through capture_rollout')
+        # a storage the building lacks: its plane stays 0 in the kernel, its weights are 0 here
+        has = np.array([[flag is None or bool(int(bflags[i]) & flag) for _, flag in kind.terms] for i in range(len(layout.building_names))])
+        dep = dep * torch.from_numpy(has.astype(np.float32)).to(dep.device)[None, None, :, :, None]
+        return pre, dep.contiguous(), rest
 
-class DeepCentralMLPPolicy:
+
+class _DeepCentralBase(_CentralBase):
+    """`_CentralBase` at two hidden layers."""
+    _NAMES = ('w1', 'b1', 'w2', 'b2', 'w3', 'b3')
+    _WIDTHS = ('H1', 'H2')
+
+    def __init__(self, w1, b1, w2, b2, w3, b3, sigma=None):
+        self._setup((w1, b1, w2, b2, w3, b3), sigma)
+
+    def update(self, w1=None, b1=None, w2=None, b2=None, w3=None, b3=None, sigma=None) -> None:
+        """Replace some of the weight arrays (same shapes) and / or sigma, and bump `version`: the learner's step between two rollouts."""
+        self._replace((w1, b1, w2, b2, w3, b3), sigma)
+
+
+class CentralMLPPolicy(_CentralBase):
+    """CityLearn's ``central_agent=True`` actor: ONE tanh MLP with one hidden layer over the district's observation vector returns every
+    building's electrical-storage action,
+
+        h = tanh(W1 obs + b1),   a_b = clamp(mid_b + half_b tanh(w2[b] . h + b2[b]) + sigma_b z, low_b, high_b)
+
+    `obs` = the central-agent observation vector as the env defines it (``ObservationLayout(..., central_agent=True).columns``: a shared
+    observation once, normalised or not, whatever the env was built with); the bounds, sigma, z and the noise stream are `MLPPolicy`'s.  The
+    env-dependent inputs are EVERY building's own ``electrical_storage_soc`` and ``net_electricity_consumption``; a building without a storage
+    action column feeds the hidden layer like any other and has no head.  Battery + PV districts of up to 32 buildings: one launch of
+    `cl_rollout_policy_central_kernel` (csrc/cl_policy_central.h, ``libcitylearn_amd_policy_central.so``).
+
+    ``w1 [n_sets, H, n_cols]``, ``b1 [n_sets, H]``, ``w2 [n_sets, n_bldg, H]``, ``b2 [n_sets, n_bldg]`` (anything array-like; kept in float64); a
+    leading dimension of 1 broadcasts.  ``H``: 4, 8, .. 64.  ``sigma``: None (deterministic), a scalar or ``[n_act_cols]``.
+
+    The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
+    kind = _CENTRAL
+    _SHAPES_MSG = 'w1 [n_sets, H, n_cols], b1 [n_sets, H], w2 [n_sets, n_bldg, H], b2 [n_sets, n_bldg]'
+    _WIDTH_MSG = '{name}={h}: the central policy kernel takes 4, 8, .. {max} hidden units'
+    _MISMATCH = ((('b1', 'w2', 'b2'), 'b1 / w2 disagree with w1 about H, or b2 with w2 about n_bldg'),)
+
+
+class DeepCentralMLPPolicy(_DeepCentralBase):
     """`CentralMLPPolicy` with TWO hidden layers -- a SAC / PPO actor trained with ``central_agent=True``:
 
         h1 = tanh(W1 obs + b1),   h2 = tanh(W2 h1 + b2),   a_b = clamp(mid_b + half_b tanh(w3[b] . h2 + b3[b]) + sigma_b z, low_b, high_b)
@@ -1202,95 +1306,13 @@ class DeepCentralMLPPolicy:
 
     The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
     kind = _CENTRAL_DEEP
-    _NAMES = ('w1', 'b1', 'w2', 'b2', 'w3', 'b3')
-
-    def __init__(self, w1, b1, w2, b2, w3, b3, sigma=None):
-        self.w1, self.b1, self.w2, self.b2, self.w3, self.b3 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2, w3, b3))
-        if [getattr(self, n).ndim for n in self._NAMES] != [3, 2, 3, 2, 3, 2]:
-            raise ValueError('w1 [n_sets, H1, n_cols], b1 [n_sets, H1], w2 [n_sets, H2, H1], b2 [n_sets, H2], w3 [n_sets, n_bldg, H2], b3 [n_sets, n_bldg]')
-        self.n_hidden, self.n_obs, self.n_hidden2, self.n_bldg = (int(self.w1.shape[1]), int(self.w1.shape[2]), int(self.w2.shape[1]),
-                                                                  int(self.w3.shape[1]))
-        for name, h in (('H1', self.n_hidden), ('H2', self.n_hidden2)):
-            if h % 4 or not 4 <= h <= CLPCD_MAX_HIDDEN:
-                raise ValueError(f'{name}={h}: the deep central policy kernel takes 4, 8, .. {CLPCD_MAX_HIDDEN} units per hidden layer')
-        if self.b1.shape[1] != self.n_hidden or self.w2.shape[2] != self.n_hidden:
-            raise ValueError('b1 / w2 disagree with w1 about H1')
-        if self.b2.shape[1] != self.n_hidden2 or self.w3.shape[2] != self.n_hidden2 or self.b3.shape[1] != self.n_bldg:
-            raise ValueError('b2 / w3 disagree with w2 about H2, or b3 with w3 about n_bldg')
-        self.n_sets = max(getattr(self, n).shape[0] for n in self._NAMES)
-        self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
-        self.version = 0
-
-    invalidate = DeepMLPPolicy.invalidate
-    update = DeepMLPPolicy.update
-    _check_layout = CentralMLPPolicy._check_layout
-    _pack_front = CentralMLPPolicy._pack_front
-
-    def _full(self, n_bldg: Optional[int] = None):
-        S, H1, H2, B = self.n_sets, self.n_hidden, self.n_hidden2, self.n_bldg
-        if n_bldg is not None and n_bldg != B:
-            raise ValueError(f'w3 has heads for {B} buildings, the district has {n_bldg}')
-        shapes = ((S, H1, self.n_obs), (S, H1), (S, H2, H1), (S, H2), (S, B, H2), (S, B))
-        try:
-            return tuple(np.broadcast_to(getattr(self, n), sh) for n, sh in zip(self._NAMES, shapes))
-        except ValueError as e:
-            raise ValueError(f'the weights do not broadcast to {S} sets: {e}') from None
-
-    # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
-    def actions_host(self, obs, noise=None, tables: Optional[DeepCentralPolicyTables] = None, low=None, high=None, sigma_bldg=None,
-                     set_index: int = 0) -> np.ndarray:
-        """float64 numpy evaluation of the plain MLP: ``obs [..., n_cols]`` (the central-agent vector) -> actions ``[..., n_bldg]``; the other
-        arguments are `MLPPolicy.actions_host`'s."""
-        pick = lambda arg, attr, default: np.asarray(arg if arg is not None else getattr(tables, attr) if tables is not None else default, dtype=np.float64)
-        x = np.asarray(obs, dtype=np.float64)
-        w1, b1, w2, b2, w3, b3 = (v[set_index] for v in self._full())
-        h1 = np.tanh(np.einsum('jc,...c->...j', w1, x) + b1)
-        h2 = np.tanh(np.einsum('ij,...j->...i', w2, h1) + b2)
-        lo, hi = pick(low, 'low_bldg', -1.0), pick(high, 'high_bldg', 1.0)
-        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('bi,...i->...b', w3, h2) + b3)
-        if noise is not None:
-            if sigma_bldg is None and tables is None and self.sigma is not None and self.sigma.ndim:
-                raise ValueError('a per-column sigma needs `tables` (or `sigma_bldg`): which column drives which building')
-            a = a + pick(sigma_bldg, 'sigma_bldg', 0.0 if self.sigma is None or self.sigma.ndim else float(self.sigma)) * np.asarray(noise, dtype=np.float64)
-        return np.clip(a, lo, hi)
-
-    def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
-        """The same MLP (no noise) written in torch over the env's observation TENSOR of a ``central_agent=True`` env: a
-        `VectorCityLearnEnv.capture_rollout` policy ``f(obs [n_envs, n_cols], i=None) -> actions [n_act_cols, n_envs]``."""
-        self._check_layout(layout)
-        w1, b1, w2, b2, w3, b3 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(len(layout.building_names)))
-        hc = _head_columns(tab, self.kind)
-        low, high = layout.spec.action_limits()
-        sel = np.nonzero(hc >= 0)[0]                                             # the buildings that have a storage column
-        rows, bsel = torch.as_tensor(hc[sel], device=device), torch.as_tensor(sel, device=device)
-        lo = torch.as_tensor(np.asarray(low)[hc[sel]], dtype=dtype, device=device)
-        hi = torch.as_tensor(np.asarray(high)[hc[sel]], dtype=dtype, device=device)
-        n_act = len(low)
-
-        def f(obs, i=None):
-            h1 = torch.tanh(obs.to(dtype) @ w1.t() + b1)                         # [E, H1]
-            h2 = torch.tanh(h1 @ w2.t() + b2)                                    # [E, H2]
-            o = torch.tanh(h2 @ w3.t() + b3)[:, bsel]                            # [E, driven buildings]
-            a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
-            out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
-            out[rows] = a.t().to(torch.float32)
-            return out
-        return f
-
-    # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
-    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None) -> DeepCentralPolicyTables:
-        """The first layer split exactly as `CentralMLPPolicy.pack` splits it (the same function, the same refusals), then ``l2`` and ``out`` as
-        `DeepCentralPolicyTables` describes them, in float64 rounded once."""
-        self._check_layout(layout)
-        w1, b1, w2, b2, w3, b3 = self._full(len(layout.building_names))
-        pre, dep, rest = self._pack_front(layout, tab, w1, b1, device, set_of_block)
-        f64 = lambda v: torch.from_numpy(np.array(v, dtype=np.float64)).to(pre.device)
-        l2 = (torch.cat([f64(w2).transpose(1, 2), f64(b2)[:, None, :]], dim=1) * ACT_SCALE).to(torch.float32)
-        out = torch.cat([f64(w3), f64(b3)[..., None]], dim=-1)
-        return DeepCentralPolicyTables(pre, dep, l2.contiguous(), out.to(torch.float32).contiguous(), *rest, self.version)
+    _SHAPES_MSG = 'w1 [n_sets, H1, n_cols], b1 [n_sets, H1], w2 [n_sets, H2, H1], b2 [n_sets, H2], w3 [n_sets, n_bldg, H2], b3 [n_sets, n_bldg]'
+    _WIDTH_MSG = '{name}={h}: the deep central policy kernel takes 4, 8, .. {max} units per hidden layer'
+    _MISMATCH = ((('b1', 'w2'), 'b1 / w2 disagree with w1 about H1'),
+                 (('b2', 'w3', 'b3'), 'b2 / w3 disagree with w2 about H2, or b3 with w3 about n_bldg'))
 
 
-class CentralStorageMLPPolicy:
+class CentralStorageMLPPolicy(_CentralBase):
     """CityLearn's ``central_agent=True`` actor on a THERMAL district: ONE tanh MLP with one hidden layer over the district's observation vector
     returns every building's storage actions, up to four heads per building in the fixed order electrical, cooling, heating, DHW storage
     (`HEAD_NAMES`, `CLPF_A_*`),
@@ -1309,109 +1331,18 @@ class CentralStorageMLPPolicy:
 
     The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
     kind = _CENTRAL_THERMAL
-    _NAMES = ('w1', 'b1', 'w2', 'b2')
+    _SHAPES_MSG = f'w1 [n_sets, H, n_cols], b1 [n_sets, H], w2 [n_sets, n_bldg, {CLPF_NA}, H], b2 [n_sets, n_bldg, {CLPF_NA}]'
+    _WIDTH_MSG = '{name}={h}: the central thermal policy kernel takes 4, 8, .. {max} hidden units'
+    _MISMATCH = ((('b1', 'w2', 'b2'), f'b1 / w2 disagree with w1 about H, b2 with w2 about n_bldg, or w2 / b2 do not have {CLPF_NA} heads'),)
 
-    def __init__(self, w1, b1, w2, b2, sigma=None):
-        self.w1, self.b1, self.w2, self.b2 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2))
-        if [getattr(self, n).ndim for n in self._NAMES] != [3, 2, 4, 3]:
-            raise ValueError(f'w1 [n_sets, H, n_cols], b1 [n_sets, H], w2 [n_sets, n_bldg, {CLPF_NA}, H], b2 [n_sets, n_bldg, {CLPF_NA}]')
-        self.n_hidden, self.n_obs, self.n_bldg = int(self.w1.shape[1]), int(self.w1.shape[2]), int(self.w2.shape[1])
-        if self.n_hidden % 4 or not 4 <= self.n_hidden <= CLPFCA_MAX_HIDDEN:
-            raise ValueError(f'H={self.n_hidden}: the central thermal policy kernel takes 4, 8, .. {CLPFCA_MAX_HIDDEN} hidden units')
-        if self.b1.shape[1] != self.n_hidden or self.w2.shape[2:] != (CLPF_NA, self.n_hidden) or self.b2.shape[1:] != (self.n_bldg, CLPF_NA):
-            raise ValueError(f'b1 / w2 disagree with w1 about H, b2 with w2 about n_bldg, or w2 / b2 do not have {CLPF_NA} heads')
-        self.n_sets = max(getattr(self, n).shape[0] for n in self._NAMES)
-        self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
-        self.version = 0
-
-    invalidate = _MLPBase.invalidate
-    update = _MLPBase.update
-    _check_layout = CentralMLPPolicy._check_layout
-    _pack_front = CentralMLPPolicy._pack_front
-
-    def _full(self, n_bldg: Optional[int] = None):
-        S, H, B = self.n_sets, self.n_hidden, self.n_bldg
-        if n_bldg is not None and n_bldg != B:
-            raise ValueError(f'w2 has heads for {B} buildings, the district has {n_bldg}')
-        shapes = ((S, H, self.n_obs), (S, H), (S, B, CLPF_NA, H), (S, B, CLPF_NA))
-        try:
-            return tuple(np.broadcast_to(getattr(self, n), sh) for n, sh in zip(self._NAMES, shapes))
-        except ValueError as e:
-            raise ValueError(f'the weights do not broadcast to {S} sets: {e}') from None
-
-    # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
     def actions_host(self, obs, tables: CentralStoragePolicyTables, noise=None, set_index: int = 0) -> np.ndarray:
         """float64 numpy evaluation of the plain MLP: ``obs [..., n_cols]`` (the central-agent vector) -> actions ``[..., n_bldg, 4]`` (0 for a
         head whose column the building lacks).  ``noise``: the standard normals z (same shape as the result; `noise_host` replays the kernel's),
         scaled by each head's sigma.  The heads' columns, bounds and sigmas come from ``tables`` (a `pack` result)."""
-        x = np.asarray(obs, dtype=np.float64)
-        w1, b1, w2, b2 = (v[set_index] for v in self._full())
-        h = np.tanh(np.einsum('jc,...c->...j', w1, x) + b1)
-        lo, hi = tables.low_bldg, tables.high_bldg
-        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('baj,...j->...ba', w2, h) + b2)
-        if noise is not None:
-            a = a + tables.sigma_bldg * np.asarray(noise, dtype=np.float64)
-        return np.where(tables.cols >= 0, np.clip(a, lo, hi), 0.0)
-
-    def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
-        """The same MLP (no noise) written in torch over the env's observation TENSOR of a ``central_agent=True`` env: a
-        `VectorCityLearnEnv.capture_rollout` policy ``f(obs [n_envs, n_cols], i=None) -> actions [n_act_cols, n_envs]``."""
-        self._check_layout(layout)
-        w1, b1, w2, b2 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(len(layout.building_names)))
-        hc = _head_columns(tab, self.kind)
-        low, high = layout.spec.action_limits()
-        sel = np.nonzero(hc >= 0)                                                # the heads that have a column
-        rows = torch.as_tensor(hc[sel], device=device)
-        lo = torch.as_tensor(np.asarray(low)[hc[sel]], dtype=dtype, device=device)
-        hi = torch.as_tensor(np.asarray(high)[hc[sel]], dtype=dtype, device=device)
-        flat = torch.as_tensor(np.ravel_multi_index(sel, hc.shape), device=device)
-        w2f, b2f = w2.reshape(-1, w2.shape[-1])[flat], b2.reshape(-1)[flat]     # [present heads, H], [present heads]
-        n_act = len(low)
-
-        def f(obs, i=None):
-            h = torch.tanh(obs.to(dtype) @ w1.t() + b1)                          # [E, H]
-            o = torch.tanh(h @ w2f.t() + b2f)                                    # [E, present heads]
-            a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
-            out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
-            out[rows] = a.t().to(torch.float32)
-            return out
-        return f
-
-    # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
-    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None) -> CentralStoragePolicyTables:
-        """Split the first layer as `CentralMLPPolicy.pack` splits it (the same function), over the central-agent vector of `layout` (built with
-        ``central_agent=True``) and the thermal kind's FIVE terms: the env-independent columns of every table row go into ``pre
-        [n_sets, n_rows, H]``, ``W1[j][c] * col_scale[c]`` of the env-dependent columns (every building's own storage socs and
-        ``net_electricity_consumption``) into ``dep`` in the kernel's order (`CentralStoragePolicyTables`; the rows of a storage the building
-        lacks stay 0), their table offsets into ``pre``; ``ACT_SCALE`` is folded into both.  Refused with `StorageMLPPolicy.pack`'s messages: a
-        column fed by any other device plane (the LSTM stage's indoor temperature among them), a reset value its table row does not hold, a
-        building with a cooling / heating device ACTION column; with `CentralMLPPolicy.pack`'s: a layout built with ``central_agent=False``, a
-        vector of another length."""
-        self._check_layout(layout)
-        w1, b1, w2, b2 = self._full(len(layout.building_names))
-        pre, dep, rest = self._pack_thermal_front(layout, tab, w1, b1, device, set_of_block)
-        out = torch.cat([torch.from_numpy(np.array(v, dtype=np.float64)).to(pre.device) for v in (w2, b2[..., None])], dim=-1)
-        return CentralStoragePolicyTables(pre, dep, out.to(torch.float32).contiguous(), *rest, self.version)
-
-    def _pack_thermal_front(self, layout: ObservationLayout, tab, w1, b1, device, set_of_block):
-        """`_pack_front` over the thermal kind's five terms, with what a thermal district adds: the refusal of device ACTION columns, and zero
-        weights for the terms of a storage a building lacks.  What `CentralStorageMLPPolicy.pack` and `DeepCentralStorageMLPPolicy.pack` share."""
-        kind = self.kind
-        pre, dep, rest = self._pack_front(layout, tab, w1, b1, device, set_of_block)
-        params_i = np.ascontiguousarray(tab.params).view(np.int32)
-        bflags = np.ascontiguousarray(tab.params).view(np.uint32)[:, abi.CLP_FLAGS]
-        for i in range(len(layout.building_names)):
-            for dname, slot in _DEVICE_SLOTS:
-                if params_i[i, slot] >= 0:
-                    raise ValueError(f'action {dname!r} of building {i} (column {int(params_i[i, slot])}): the thermal policy kernel has storage heads '
-                                     f'only {HEAD_NAMES}; a district with device actions runs through capture_rollout')
-        # a storage the building lacks: its plane stays 0 in the kernel, its weights are 0 here
-        has = np.array([[flag is None or bool(int(bflags[i]) & flag) for _, flag in kind.terms] for i in range(len(layout.building_names))])
-        dep = dep * torch.from_numpy(has.astype(np.float32)).to(dep.device)[None, None, :, :, None]
-        return pre, dep.contiguous(), rest
+        return self._actions_thermal(obs, tables, noise, set_index)
 
 
-class DeepCentralStorageMLPPolicy:
+class DeepCentralStorageMLPPolicy(_DeepCentralBase):
     """`CentralStorageMLPPolicy` with TWO hidden layers -- a SAC / PPO actor trained with ``central_agent=True`` on a THERMAL district:
 
         h1 = tanh(W1 obs + b1),   h2 = tanh(W2 h1 + b2),   act[b][a] = clamp(mid + half tanh(w3[b][a] . h2 + b3[b][a]) + sigma z, low, high)
@@ -1419,7 +1350,7 @@ class DeepCentralStorageMLPPolicy:
     for every head (`HEAD_NAMES`, `CLPF_A_*` order) whose building has that action column.  `obs`, the bounds, sigma, z, the noise stream -- Philox
     keyed by the head's action column -- and the env-dependent inputs (EVERY building's own storage socs and ``net_electricity_consumption``) are
     `CentralStorageMLPPolicy`'s.  Thermal districts without the LSTM stage and without device actions (the 2020 / 2021 schemas) of up to 16
-    buildings: one launch of `cl_rollout_full_policy_central_deep_kernel` (csrc/cl_policy_full_central_deep.h,
+    buildings: one launch of `cl_rollout_full_policy_central_deep_kernel` (csrc/cl_policy_full_central.h at DEEP = true,
     ``libcitylearn_amd_policy_full_central_deep.so``), layer 2 in exact fp32.
 
     ``w1 [n_sets, H1, n_cols]``, ``b1 [n_sets, H1]``, ``w2 [n_sets, H2, H1]``, ``b2 [n_sets, H2]``, ``w3 [n_sets, n_bldg, 4, H2]``,
@@ -1428,90 +1359,13 @@ class DeepCentralStorageMLPPolicy:
 
     The packed tables are a snapshot, as `MLPPolicy`'s: change the weights through :meth:`update` / :meth:`invalidate`, which bump `version`."""
     kind = _CENTRAL_DEEP_THERMAL
-    _NAMES = ('w1', 'b1', 'w2', 'b2', 'w3', 'b3')
+    _SHAPES_MSG = (f'w1 [n_sets, H1, n_cols], b1 [n_sets, H1], w2 [n_sets, H2, H1], b2 [n_sets, H2], w3 [n_sets, n_bldg, {CLPF_NA}, H2], '
+                   f'b3 [n_sets, n_bldg, {CLPF_NA}]')
+    _WIDTH_MSG = '{name}={h}: the deep central thermal policy kernel takes 4, 8, .. {max} units per hidden layer'
+    _MISMATCH = ((('b1', 'w2'), 'b1 / w2 disagree with w1 about H1'),
+                 (('b2', 'w3', 'b3'), f'b2 / w3 disagree with w2 about H2, b3 with w3 about n_bldg, or w3 / b3 do not have {CLPF_NA} heads'))
 
-    def __init__(self, w1, b1, w2, b2, w3, b3, sigma=None):
-        self.w1, self.b1, self.w2, self.b2, self.w3, self.b3 = (np.asarray(x, dtype=np.float64) for x in (w1, b1, w2, b2, w3, b3))
-        if [getattr(self, n).ndim for n in self._NAMES] != [3, 2, 3, 2, 4, 3]:
-            raise ValueError(f'w1 [n_sets, H1, n_cols], b1 [n_sets, H1], w2 [n_sets, H2, H1], b2 [n_sets, H2], w3 [n_sets, n_bldg, {CLPF_NA}, H2], '
-                             f'b3 [n_sets, n_bldg, {CLPF_NA}]')
-        self.n_hidden, self.n_obs, self.n_hidden2, self.n_bldg = (int(self.w1.shape[1]), int(self.w1.shape[2]), int(self.w2.shape[1]),
-                                                                  int(self.w3.shape[1]))
-        for name, h in (('H1', self.n_hidden), ('H2', self.n_hidden2)):
-            if h % 4 or not 4 <= h <= CLPFCD_MAX_HIDDEN:
-                raise ValueError(f'{name}={h}: the deep central thermal policy kernel takes 4, 8, .. {CLPFCD_MAX_HIDDEN} units per hidden layer')
-        if self.b1.shape[1] != self.n_hidden or self.w2.shape[2] != self.n_hidden:
-            raise ValueError('b1 / w2 disagree with w1 about H1')
-        if self.b2.shape[1] != self.n_hidden2 or self.w3.shape[2:] != (CLPF_NA, self.n_hidden2) or self.b3.shape[1:] != (self.n_bldg, CLPF_NA):
-            raise ValueError(f'b2 / w3 disagree with w2 about H2, b3 with w3 about n_bldg, or w3 / b3 do not have {CLPF_NA} heads')
-        self.n_sets = max(getattr(self, n).shape[0] for n in self._NAMES)
-        self.sigma = None if sigma is None else np.asarray(sigma, dtype=np.float64)
-        self.version = 0
-
-    invalidate = DeepMLPPolicy.invalidate
-    update = DeepMLPPolicy.update
-    _check_layout = CentralMLPPolicy._check_layout
-    _pack_front = CentralMLPPolicy._pack_front
-    _pack_thermal_front = CentralStorageMLPPolicy._pack_thermal_front
-
-    def _full(self, n_bldg: Optional[int] = None):
-        S, H1, H2, B = self.n_sets, self.n_hidden, self.n_hidden2, self.n_bldg
-        if n_bldg is not None and n_bldg != B:
-            raise ValueError(f'w3 has heads for {B} buildings, the district has {n_bldg}')
-        shapes = ((S, H1, self.n_obs), (S, H1), (S, H2, H1), (S, H2), (S, B, CLPF_NA, H2), (S, B, CLPF_NA))
-        try:
-            return tuple(np.broadcast_to(getattr(self, n), sh) for n, sh in zip(self._NAMES, shapes))
-        except ValueError as e:
-            raise ValueError(f'the weights do not broadcast to {S} sets: {e}') from None
-
-    # ---- the reference: the UNSPLIT MLP in float64 ------------------------------------------------------------------------------
     def actions_host(self, obs, tables: DeepCentralStoragePolicyTables, noise=None, set_index: int = 0) -> np.ndarray:
         """float64 numpy evaluation of the plain MLP: ``obs [..., n_cols]`` (the central-agent vector) -> actions ``[..., n_bldg, 4]`` (0 for a
         head whose column the building lacks); the other arguments are `CentralStorageMLPPolicy.actions_host`'s."""
-        x = np.asarray(obs, dtype=np.float64)
-        w1, b1, w2, b2, w3, b3 = (v[set_index] for v in self._full())
-        h1 = np.tanh(np.einsum('jc,...c->...j', w1, x) + b1)
-        h2 = np.tanh(np.einsum('ij,...j->...i', w2, h1) + b2)
-        lo, hi = tables.low_bldg, tables.high_bldg
-        a = 0.5 * (hi + lo) + 0.5 * (hi - lo) * np.tanh(np.einsum('bai,...i->...ba', w3, h2) + b3)
-        if noise is not None:
-            a = a + tables.sigma_bldg * np.asarray(noise, dtype=np.float64)
-        return np.where(tables.cols >= 0, np.clip(a, lo, hi), 0.0)
-
-    def torch_policy(self, layout: ObservationLayout, tab, device, dtype=torch.float32, set_index: int = 0):
-        """The same MLP (no noise) written in torch over the env's observation TENSOR of a ``central_agent=True`` env: a
-        `VectorCityLearnEnv.capture_rollout` policy ``f(obs [n_envs, n_cols], i=None) -> actions [n_act_cols, n_envs]``."""
-        self._check_layout(layout)
-        w1, b1, w2, b2, w3, b3 = (torch.as_tensor(np.array(v[set_index]), dtype=dtype, device=device) for v in self._full(len(layout.building_names)))
-        hc = _head_columns(tab, self.kind)
-        low, high = layout.spec.action_limits()
-        sel = np.nonzero(hc >= 0)                                                # the heads that have a column
-        rows = torch.as_tensor(hc[sel], device=device)
-        lo = torch.as_tensor(np.asarray(low)[hc[sel]], dtype=dtype, device=device)
-        hi = torch.as_tensor(np.asarray(high)[hc[sel]], dtype=dtype, device=device)
-        flat = torch.as_tensor(np.ravel_multi_index(sel, hc.shape), device=device)
-        w3f, b3f = w3.reshape(-1, w3.shape[-1])[flat], b3.reshape(-1)[flat]     # [present heads, H2], [present heads]
-        n_act = len(low)
-
-        def f(obs, i=None):
-            h1 = torch.tanh(obs.to(dtype) @ w1.t() + b1)                         # [E, H1]
-            h2 = torch.tanh(h1 @ w2.t() + b2)                                    # [E, H2]
-            o = torch.tanh(h2 @ w3f.t() + b3f)                                   # [E, present heads]
-            a = torch.clamp(0.5 * (hi + lo) + 0.5 * (hi - lo) * o, lo, hi)
-            out = torch.zeros((n_act, obs.shape[0]), dtype=torch.float32, device=obs.device)
-            out[rows] = a.t().to(torch.float32)
-            return out
-        return f
-
-    # ---- the kernel's tables ----------------------------------------------------------------------------------------------------
-    def pack(self, layout: ObservationLayout, tab, device='cpu', set_of_block=None) -> DeepCentralStoragePolicyTables:
-        """The first layer split exactly as `CentralStorageMLPPolicy.pack` splits it (the same function: the same refusals of device actions and
-        the LSTM stage, the same zero rows for a storage a building lacks), then ``l2`` as `DeepCentralMLPPolicy.pack` builds it and ``out``
-        as `DeepCentralStoragePolicyTables` describes it, in float64 rounded once."""
-        self._check_layout(layout)
-        w1, b1, w2, b2, w3, b3 = self._full(len(layout.building_names))
-        pre, dep, rest = self._pack_thermal_front(layout, tab, w1, b1, device, set_of_block)
-        f64 = lambda v: torch.from_numpy(np.array(v, dtype=np.float64)).to(pre.device)
-        l2 = (torch.cat([f64(w2).transpose(1, 2), f64(b2)[:, None, :]], dim=1) * ACT_SCALE).to(torch.float32)
-        out = torch.cat([f64(w3), f64(b3)[..., None]], dim=-1)
-        return DeepCentralStoragePolicyTables(pre, dep, l2.contiguous(), out.to(torch.float32).contiguous(), *rest, self.version)
+        return self._actions_thermal(obs, tables, noise, set_index)

@@ -473,7 +473,7 @@ class VectorCityLearnEnv:
 
         A `policy.DeepCentralStorageMLPPolicy` (the central agent's MLP with TWO hidden layers of 4 .. 64 units each, up to four storage heads
         per building) drives the same thermal districts of an env built with ``central_agent=True`` through
-        `cl_rollout_full_policy_central_deep_kernel`; record, noise stream, MARL and every refusal are the `CentralStorageMLPPolicy`'s."""
+        `cl_rollout_full_policy_central_deep_kernel` (csrc/cl_policy_full_central.h at DEEP = true); record, noise stream, MARL and every refusal are the `CentralStorageMLPPolicy`'s."""
         chunked =(policy.kind.ext_chunk or policy.kind.ext_chunk_pair) is not None and self.engine.n_bldg > policy.kind.one_row_max
         if policy.kind.central and not self.central_agent:
             raise ValueError(f'a {type(policy).__name__} needs an env built with central_agent=True: this env hands out one observation vector per '

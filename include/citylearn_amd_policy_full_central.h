@@ -1,7 +1,7 @@
 /* citylearn_amd_policy_full_central.h -- C interface of libcitylearn_amd_policy_full_central.so: the fused K-step rollout of a THERMAL district
  * (cooling / heating / DHW storage beside the battery: the 2020 / 2021 schemas) driven by a CLOSED-LOOP CENTRAL-AGENT policy -- ONE tanh MLP with
  * one hidden layer over the district's observation vector that returns every building's storage actions, up to four heads per building --
- * evaluated inside the rollout kernel (csrc/cl_policy_full_central.h).
+ * evaluated inside the rollout kernel (csrc/cl_policy_full_central.h at DEEP = false).
  *
  * A library of its own beside libcitylearn_amd.so and the other policy libraries (whose symbol lists, structs and kernels it leaves untouched);
  * it shares cl_dims / cl_tuning, the plane layouts and the error codes with citylearn_amd.h, and the terms (CLPF_ND, CLPF_D_*), the heads

@@ -1,7 +1,7 @@
 /* citylearn_amd_policy_full_central_deep.h -- C interface of libcitylearn_amd_policy_full_central_deep.so: the fused K-step rollout of a THERMAL
  * district (cooling / heating / DHW storage beside the battery: the 2020 / 2021 schemas) driven by a CLOSED-LOOP CENTRAL-AGENT policy with TWO
  * hidden tanh layers -- ONE MLP of the shape of a SAC / PPO actor over the district's observation vector that returns every building's storage
- * actions, up to four heads per building -- evaluated inside the rollout kernel (csrc/cl_policy_full_central_deep.h).
+ * actions, up to four heads per building -- evaluated inside the rollout kernel (csrc/cl_policy_full_central.h at DEEP = true).
  *
  * A library of its own beside libcitylearn_amd.so and the twelve other policy libraries (whose symbol lists, structs and kernels it leaves
  * untouched); it shares cl_dims / cl_tuning, the plane layouts and the error codes with citylearn_amd.h, and the terms (CLPF_ND, CLPF_D_*), the
@@ -66,7 +66,7 @@ const char* clpfcd_last_error(void);
  * CLD_F64_CHAIN, every reward kind but CLR_EV (CLR_MARL included: the kernel's last barrier of a step carries it), env_row0 / env_offset as in
  * cl_rollout_f32; no CLD_F64_MAPS, CLD_KPI, CLD_WRITE_DETAIL, no env_pitch.  One building per wave (cl_tuning.nw: 0 or n_bldg), one env per lane
  * (cl_tuning.vec: 0 or 1).
- * Dynamic LDS per workgroup, in floats (csrc/cl_policy_full_central_deep.h; the launch opts in above 64 KiB, a CU's 160 KiB are never reached:
+ * Dynamic LDS per workgroup, in floats (csrc/cl_policy_full_central.h; the launch opts in above 64 KiB, a CU's 160 KiB are never reached:
  * 125 184 bytes at sixteen buildings and 64 x 64 units):
  *     nw x 4 x 64  +  5 x n_bldg x 64  +  n_hidden x 64  +  n_hidden2 x 64  +  5 x n_hidden x n_bldg  +  (n_hidden + 1) x n_hidden2  +  nw x (4 x CLPFCD_MAX_HIDDEN + 4 x 8)
  *     reduction rows  X (soc, cs, hs, ds, net)  Hh (layer 1)   Hh2 (layer 2)     staged dep                staged l2                      staged head rows

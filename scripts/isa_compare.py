@@ -13,8 +13,9 @@ instantiation differs or has no partner.
 
 A kernel whose name differs between the trees is paired through `--map`: `OLD=NEW` pairs `OLD<args>` with `NEW<args>`, and
 `OLD=NEW<*, true>` pairs `OLD<args>` with `NEW<args, true>` (`NEW<1, *, true>`: with `NEW<1, args, true>`).  DEFAULT_MAP holds the renames of the
-latest one-source change, the four thermal per-building rollouts in one template (profiles/policy_full_one_source_isa.md); the map of the change
-before it is written down in profiles/policy_one_source_isa.md as the `--map` arguments that make that note again."""
+latest one-source change, the two thermal central-agent rollouts in one template (profiles/policy_full_central_one_source_isa.md); the maps of
+the changes before it are written down in profiles/policy_full_one_source_isa.md and profiles/policy_one_source_isa.md as the `--map` arguments
+that make those notes again."""
 import argparse
 import importlib.util
 import re
@@ -25,10 +26,8 @@ from pathlib import Path
 
 # parent name -> name in this tree (`*`: the parent's template arguments)
 DEFAULT_MAP = {
-    'cl_rollout_full_policy_kernel': 'cl_rollout_full_policy_kernel<*, false, false>',
-    'cl_rollout_full_policy_kpi_kernel': 'cl_rollout_full_policy_kernel<1, *, true, false>',
-    'cl_rollout_full_policy_chunk_kernel': 'cl_rollout_full_policy_kernel<*, false, false, true>',
-    'cl_rollout_full_policy_chunk_kpi_kernel': 'cl_rollout_full_policy_kernel<1, *, false, true, true>',
+    'cl_rollout_full_policy_central_kernel': 'cl_rollout_full_policy_central_kernel<*, false>',
+    'cl_rollout_full_policy_central_deep_kernel': 'cl_rollout_full_policy_central_kernel<*, true>',
 }
 
 

@@ -1,6 +1,6 @@
 """us per env step of the closed-loop rollout of a THERMAL district under a CENTRAL-AGENT policy with TWO hidden layers
-(cl_rollout_full_policy_central_deep_kernel) at (H1, H2) = (16, 16), (32, 32), (64, 64) and (64, 4), against the one-hidden-layer central thermal
-kernel (cl_rollout_full_policy_central_kernel) at H = H1 -- what the second layer, its LDS and its barrier add -- and against `capture_rollout`
+(cl_rollout_full_policy_central_deep_kernel: csrc/cl_policy_full_central.h at DEEP = true) at (H1, H2) = (16, 16), (32, 32), (64, 64) and (64, 4), against the one-hidden-layer central thermal
+kernel (cl_rollout_full_policy_central_kernel: the same template at DEEP = false) at H = H1 -- what the second layer, its LDS and its barrier add -- and against `capture_rollout`
 with the same two-layer MLP in torch -- the only way to run such an actor on such a district without the kernel: the 2020 schema's 9 buildings x
 32 768 envs, K = 24, with the record, float64 chain and fp32 map.  The protocol of scripts/policy_full_central_probe.py: one process, the legs
 alternating round by round, round 0 discarded; every timed window is `--launches` rollouts between two device events.  Prints one JSON line per

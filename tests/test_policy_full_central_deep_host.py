@@ -1,8 +1,8 @@
 """The closed-loop rollout of THERMAL districts under a CENTRAL-AGENT policy with TWO hidden layers (`clpfcd_rollout_mlp_f32`, kernel
-`cl_rollout_full_policy_central_deep_kernel` in csrc/cl_policy_full_central_deep.h, library ``libcitylearn_amd_policy_full_central_deep.so``) as far
-as it can be checked without a GPU: the library's symbol list and struct, every refusal of the host entry (before any HIP call), the LDS formula,
-the packer against the unsplit MLP in float64, the conditioning of the closed loop the GPU tests run
-(tests/test_gpu_policy_full_central_deep_rollout.py), and the resource figures of every instantiation."""
+`cl_rollout_full_policy_central_kernel<PREC, MARL, true>` in csrc/cl_policy_full_central.h, library
+``libcitylearn_amd_policy_full_central_deep.so``) as far as it can be checked without a GPU: the library's symbol list and struct, every refusal of
+the host entry (before any HIP call), the LDS formula, the packer against the unsplit MLP in float64, the conditioning of the closed loop the GPU
+tests run (tests/test_gpu_policy_full_central_deep_rollout.py), and the resource figures of every instantiation."""
 import ctypes
 import re
 
@@ -36,10 +36,12 @@ def test_library_exports_exactly_the_header(entry):
     assert not isinstance(src, tuple) and src.name == 'cl_policy_full_central_deep.hip'     # the library's common flags, with SLP vectorisation
     assert 'compiled WITH SLP vectorisation' in src.read_text().split('#define')[0]
     assert EXT.path.name == 'libcitylearn_amd_policy_full_central_deep.so' and EXT.header.name == 'citylearn_amd_policy_full_central_deep.h'
-    # the kernel is a source of its own, which this unit includes and nobody else; the one-hidden-layer pair is not touched by it
-    users = sorted(p.name for p in _lib.CSRC.glob('*.hip') if '#include "cl_policy_full_central_deep.h"' in p.read_text())
-    assert users == ['cl_policy_full_central_deep.hip']
-    assert 'central_deep' not in (_lib.CSRC / 'cl_policy_full_central.h').read_text() + (_lib.CSRC / 'cl_policy_full_central.hip').read_text()
+    # the kernel is ONE template source with the one-hidden-layer kernel, which the two units include and nobody else; this unit instantiates
+    # DEEP = true only
+    assert not (_lib.CSRC / 'cl_policy_full_central_deep.h').exists()
+    users = sorted(p.name for p in _lib.CSRC.glob('*.hip') if '#include "cl_policy_full_central.h"' in p.read_text())
+    assert users == ['cl_policy_full_central.hip', 'cl_policy_full_central_deep.hip']
+    assert 'CL_POLICY_LAUNCH(cl_rollout_full_policy_central_kernel<P, M, true>)' in src.read_text() and '<P, M, false>' not in src.read_text()
 
 
 def test_struct_is_the_deep_thermal_policy_struct():
@@ -197,13 +199,14 @@ def test_lds_formula():
     assert '125 184 bytes' in EXT.header.read_text()
     assert _lib.policy_full_central_deep_lds_bytes(16, 4, 4) == 58704 < 64 * 1024 < _lib.policy_full_central_deep_lds_bytes(16, 32, 32) == 86144
     assert _lib.policy_full_central_deep_lds_bytes(9, 32, 16) == 4 * (9 * 256 + 45 * 64 + 32 * 64 + 16 * 64 + 160 * 9 + 33 * 16 + 9 * 288) == 51264
-    head, unit = (_lib.CSRC / 'cl_policy_full_central_deep.h').read_text(), (_lib.CSRC / 'cl_policy_full_central_deep.hip').read_text()
+    head, unit = (_lib.CSRC / 'cl_policy_full_central.h').read_text(), (_lib.CSRC / 'cl_policy_full_central_deep.hip').read_text()
     assert ('return (size_t)nw * NQ * 64 + (size_t)CLPF_ND * n_bldg * 64 + (size_t)h1 * 64 + (size_t)h2 * 64 + (size_t)CLPF_ND * h1 * n_bldg + '
-            '(size_t)(h1 + 1) * h2\n           + (size_t)nw * CLPFCD_ROW;' in head
-            and 'CLPFCD_HEADS = CLPF_NA * CLPFCD_MAX_HIDDEN;' in head and 'CLPFCD_ROW = CLPFCD_HEADS + 8 * CLPF_NA;' in head
+            '(size_t)(h1 + 1) * h2\n           + (size_t)nw * CLPFC_ROW;' in head
+            and 'CLPFC_MAX_HIDDEN = 64;' in head and 'CLPFC_HEADS = CLPF_NA * CLPFC_MAX_HIDDEN;' in head and 'CLPFC_ROW = CLPFC_HEADS + 8 * CLPF_NA;' in head
+            and 'static_assert(CLPFCD_MAX_HIDDEN == CLPFC_MAX_HIDDEN,' in unit and policy.CLPFCD_MAX_HIDDEN == 64
             and abi.CL_NQ == 4 and (CLPF_ND, CLPF_NA) == (5, 4))
     assert ('check_policy_lds(lds, "deep central thermal policy", a.nw, 1)' in unit
-            and 'CL_POLICY_LAUNCH(cl_rollout_full_policy_central_deep_kernel<P, M>)' in unit)
+            and 'CL_POLICY_LAUNCH(cl_rollout_full_policy_central_kernel<P, M, true>)' in unit)
     shared = (_lib.CSRC / 'cl_policy_common.h').read_text()
     assert 'if (lds > 64 * 1024) if (hipError_t e = ensure_dynamic_lds(' in shared and 'if (lds > CL_LDS_PER_CU) return fail(' in shared
 
@@ -451,13 +454,13 @@ def central_deep_unit(tmp_path_factory):
 
 
 def test_central_deep_thermal_kernel_resources(central_deep_unit):
-    """Every instantiation of cl_rollout_full_policy_central_deep_kernel<PREC, MARL> -- the fp32 map and the float64 chain, with and without the
+    """Every instantiation of cl_rollout_full_policy_central_kernel<PREC, MARL, true> -- the fp32 map and the float64 chain, with and without the
     MARL exchange: no scratch memory and at most 128 registers, a 1024-thread workgroup's limit.  The unit holds no other rollout or step kernel."""
     kernels, meta = central_deep_unit
-    names = [k for k in kernels if 'cl_rollout_full_policy_central_deep_kernel' in k]
+    names = [k for k in kernels if 'cl_rollout_full_policy_central_kernel' in k]
     by = {}
     for k in names:
-        m = re.search(r'cl_rollout_full_policy_central_deep_kernelILi(\d)ELb(\d)EE', k)
+        m = re.search(r'cl_rollout_full_policy_central_kernelILi(\d)ELb(\d)ELb1EE', k)
         by[(int(m.group(1)), bool(int(m.group(2))))] = k
     assert sorted(by) == [(0, False), (0, True), (2, False), (2, True)] and len(names) == 4
     assert not [k for k in kernels if k not in names and ('cl_rollout' in k or 'cl_step' in k)]

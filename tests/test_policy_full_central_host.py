@@ -1,6 +1,6 @@
 """The closed-loop rollout of THERMAL districts under a CENTRAL-AGENT policy (`clpfca_rollout_mlp_f32`, kernel
-`cl_rollout_full_policy_central_kernel` in csrc/cl_policy_full_central.h, library ``libcitylearn_amd_policy_full_central.so``) as far as it can be
-checked without a GPU: the library's symbol list and struct, every refusal of the host entry (before any HIP call), the LDS formula, the packer
+`cl_rollout_full_policy_central_kernel<PREC, MARL, false>` in csrc/cl_policy_full_central.h, library ``libcitylearn_amd_policy_full_central.so``)
+as far as it can be checked without a GPU: the library's symbol list and struct, every refusal of the host entry (before any HIP call), the LDS formula, the packer
 against the unsplit MLP in float64, the conditioning of the closed loop the GPU tests run (tests/test_gpu_policy_full_central_rollout.py), and the
 resource figures of every instantiation."""
 import ctypes
@@ -166,10 +166,12 @@ def test_lds_formula():
     assert _lib.policy_full_central_lds_bytes(16, 4) == 57600 < 64 * 1024 < _lib.policy_full_central_lds_bytes(16, 32) == 73728
     assert _lib.policy_full_central_lds_bytes(9, 32) == 4 * (9 * 256 + 45 * 64 + 32 * 64 + 160 * 9 + 9 * 288) == 45056
     head, unit = (_lib.CSRC / 'cl_policy_full_central.h').read_text(), (_lib.CSRC / 'cl_policy_full_central.hip').read_text()
-    assert ('return (size_t)nw * NQ * 64 + (size_t)CLPF_ND * n_bldg * 64 + (size_t)h * 64 + (size_t)CLPF_ND * h * n_bldg + (size_t)nw * CLPFCA_ROW;' in head
-            and 'CLPFCA_HEADS = CLPF_NA * CLPFCA_MAX_HIDDEN;' in head and 'CLPFCA_ROW = CLPFCA_HEADS + 8 * CLPF_NA;' in head
+    assert ('return (size_t)nw * NQ * 64 + (size_t)CLPF_ND * n_bldg * 64 + (size_t)h * 64 + (size_t)CLPF_ND * h * n_bldg + (size_t)nw * CLPFC_ROW;' in head
+            and 'CLPFC_MAX_HIDDEN = 64;' in head and 'CLPFC_HEADS = CLPF_NA * CLPFC_MAX_HIDDEN;' in head and 'CLPFC_ROW = CLPFC_HEADS + 8 * CLPF_NA;' in head
+            and 'static_assert(CLPFCA_MAX_HIDDEN == CLPFC_MAX_HIDDEN,' in unit and policy.CLPFCA_MAX_HIDDEN == 64
             and abi.CL_NQ == 4 and (CLPF_ND, CLPF_NA) == (5, 4))
-    assert 'check_policy_lds(lds, "central thermal policy", a.nw, 1)' in unit and 'CL_POLICY_LAUNCH(cl_rollout_full_policy_central_kernel<P, M>)' in unit
+    assert ('check_policy_lds(lds, "central thermal policy", a.nw, 1)' in unit
+            and 'CL_POLICY_LAUNCH(cl_rollout_full_policy_central_kernel<P, M, false>)' in unit and '<P, M, true>' not in unit)
     shared = (_lib.CSRC / 'cl_policy_common.h').read_text()
     assert 'if (lds > 64 * 1024) if (hipError_t e = ensure_dynamic_lds(' in shared and 'if (lds > CL_LDS_PER_CU) return fail(' in shared
 
@@ -403,7 +405,7 @@ def test_central_thermal_kernel_resources(central_unit):
     names = [k for k in kernels if 'cl_rollout_full_policy_central_kernel' in k]
     by = {}
     for k in names:
-        m = re.search(r'cl_rollout_full_policy_central_kernelILi(\d)ELb(\d)EE', k)
+        m = re.search(r'cl_rollout_full_policy_central_kernelILi(\d)ELb(\d)ELb0EE', k)
         by[(int(m.group(1)), bool(int(m.group(2))))] = k
     assert sorted(by) == [(0, False), (0, True), (2, False), (2, True)] and len(names) == 4
     assert not [k for k in kernels if k not in names and ('cl_rollout' in k or 'cl_step' in k)]
